@@ -17,7 +17,10 @@ GPUs"): rank r scans the trait block sharding.trait_shard(m, r, N); no data-path
 north_star's optional final step -- an RCCL all-gather of the LOD column blocks over xGMI -- is timed separately
 (`allgather_ms`) and a second timed loop with the gather inside the step gives `gathered_ms_per_step`; `weak` holds the
 weak-scaling figure (every rank scans a full BXD-shaped batch) measured in the same run.  `--scaling weak` makes that
-one the headline instead.  Rank 0 prints ONE JSON line."""
+one the headline instead.  Rank 0 prints ONE JSON line.
+
+`--dump-outputs DIR`: after the timed steps, rank 0 writes what the last timed step returned to its caller as DIR/<name>.npy
+(see dump_outputs), so that two builds can be compared output for output on the same seeded inputs."""
 import argparse
 import json
 import os
@@ -33,6 +36,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 FP64_MFMA_PEAK_TFLOPS = 78.6   # AMD MI355X datasheet, FP64 matrix (dense); measured sustained: see DESIGN.md
 FP32_MFMA_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: FP32 matrix, v_mfma_f32_32x32x2_f32 (exact fp32)
 HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_BYTES = 60 << 20          # --dump-outputs: array data in all, under the 64 MB a dump may take with its .npy headers
+DUMP_SEED = 20240
 
 
 def synth(n, p, m, seed):
@@ -85,6 +90,41 @@ def cpu_baseline(Y, G, K, budget_s=15.0):
         v16, s16, d16 = run(16, min(budget_s, 8.0))
         out["threads16"] = {"value": v16, "cores": 16, "sample": f"first {s16} traits, 16 threads, {d16:.1f} s (the reference's published run used 16 Julia threads)"}
     return out
+
+
+def dump_outputs(out_dir, whole, sampled):
+    """Writes out_dir/<name>.npy, float32 for an fp32 output and float64 for everything else (indices and counts included).
+    whole {name: array or tensor}: written as it is.  sampled {group: {name: array or tensor}}: the arrays of a group share their
+    first axis (the traits of an (m, p) trait-major device matrix, written as the caller's p x m; the rows of a triplet list).
+    Where the DUMP_BYTES left over by `whole` do not hold a group, it is cut to one fixed, seeded sample of that axis, the same rows
+    for every array of the group, and the indices kept are written as <group>.npy."""
+    import torch
+
+    def fp32(x):
+        return x.dtype == (torch.float32 if torch.is_tensor(x) else np.float32)
+
+    def host(x):
+        x = x.cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+        return x if fp32(x) else x.astype(np.float64)
+
+    out = {name: host(x) for name, x in whole.items()}
+    room = DUMP_BYTES - sum(x.nbytes for x in out.values())
+    for group, arrays in sampled.items():
+        rows = len(next(iter(arrays.values())))
+        per_row = 8 + sum((4 if fp32(x) else 8) * int(np.prod(x.shape[1:])) for x in arrays.values())
+        k = min(rows, max(room // len(sampled), 0) // per_row)
+        if rows and not k:
+            raise SystemExit(f"--dump-outputs: not one row of `{group}` fits in {DUMP_BYTES} bytes")
+        keep = np.arange(rows) if k == rows else np.sort(np.random.default_rng(DUMP_SEED).choice(rows, k, replace=False))
+        out[group] = keep.astype(np.float64)
+        for name, x in arrays.items():
+            x = x.index_select(0, torch.from_numpy(keep).to(x.device)) if torch.is_tensor(x) else np.asarray(x)[keep]
+            out[name] = np.ascontiguousarray(host(x).T)
+    assert sum(x.nbytes for x in out.values()) <= DUMP_BYTES
+    os.makedirs(out_dir, exist_ok=True)
+    for name, x in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), x)
+    print("bench.py: wrote " + ", ".join(f"{name}{list(x.shape)}" for name, x in out.items()) + " to " + out_dir, file=sys.stderr)
 
 
 def workload_name(a, n, p, m_total, m_local, f32, world):
@@ -141,7 +181,12 @@ def main():
     ap.add_argument("--no-all-rank-form", action="store_true",
                     help="skip the extra timed loop with every trait in the rank-R form (profiling runs: its launches would be averaged into the kernel statistics)")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the outputs of the last one to DIR/<name>.npy (at most 64 MB: a fixed, seeded "
+                         "sample of a larger output)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps: at least one timed step")
     if a.reduced and (a.method not in ("null-exact", "null-grid") or a.gpus > 1 or a.streams > 1):
         raise SystemExit("--reduced: null-exact / null-grid on one GPU, one stream")
 
@@ -452,6 +497,25 @@ def main():
     if world == 1 and a.streams == 1:
         dt_nomarks, _, _ = timed(work, a.gather, a.steps, 1, marks=False)
     dt, phases, ncalls = timed(work, a.gather, a.steps, a.warmup)
+    if a.dump_outputs and rank == 0:
+        # the outputs of the last timed step (its context's, with --streams > 1), as its caller receives them; N > 1: rank 0's block
+        k = (step_no[0] - 1) % (1 + len(extra))
+        L, H = (work.dL, work.dH) if k == 0 else extra[k - 1][1:]
+        if perms:
+            dump_outputs(a.dump_outputs, {"scalars": work.dsc, "lod": work.dlod}, {"permutations": {"L_perms": L}})
+        elif a.reduced:
+            # the triplets in (trait, marker) order: the kernels append them in no fixed order
+            cnt = int(work.tc.item())
+            ti, tj, tl = (t[: min(cnt, t.shape[0])].cpu().numpy() for t in (work.ti, work.tj, work.tl))
+            o = np.lexsort((ti, tj))
+            dump_outputs(a.dump_outputs, {"lod_colmax": work.rmax[: work.m], "lod_argmax": work.rarg[: work.m], "h2": H[: work.m],
+                                          "triplet_count": [cnt]},
+                         {"triplets": {"triplet_marker": ti[o], "triplet_trait": tj[o], "triplet_lod": tl[o]}})
+        else:
+            mats = {"L": L, "h2_panel": H} if alt else {"L": L}
+            if work.dP is not None:
+                mats["log10p"] = work.dP
+            dump_outputs(a.dump_outputs, {} if alt else {"h2": H[: work.m]}, {"traits": mats})
     lr_rank = lr_resid = lr_fallback = lr_shared = lr_profile = None
     if a.method == "null-exact":   # one extra (untimed) call with a status read-back: the weight basis and its guard
         st = B.bulkscan_dev(ctx, work.dY, dG, dK, work.dL, work.dH, method=a.method, h2_grid=grid, status=True)

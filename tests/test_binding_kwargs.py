@@ -1,17 +1,17 @@
 """Drop-in check of the host bindings against the reference's own signatures, read as TEXT: every keyword argument of
 bulkscan / bulkscan_null / bulkscan_null_grid / bulkscan_alt_grid (src/bulkscan.jl:81-124,188-219,321-346,428-451) and of
 the four scan methods (src/scan.jl:94-199) must be accepted by the Julia binding (bulklmm.jl_amd/julia/BulkLMMHIP.jl, the
-method with the same positional arity) and by the Python mirror (bulklmm.jl_amd/api.py).  Skipped where the reference tree
-is absent (the GPU box)."""
+method with the same positional arity) and by the Python mirror (bulklmm.jl_amd/api.py).  The reference's signatures are
+stored as data, tests/golden/reference_signatures.json ({file: {function: [[n_positional, [keywords]], ...]}}), which this
+module's parser wrote from the reference's sources:  python tests/test_binding_kwargs.py <reference checkout>"""
 import inspect
+import json
 import os
 import re
-
-import pytest
+import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/src"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present")
+SIGS = os.path.join(ROOT, "tests", "golden", "reference_signatures.json")
 
 
 def julia_methods(path):
@@ -56,18 +56,25 @@ def julia_methods(path):
 REF_FUNCS = {"bulkscan.jl": ["bulkscan", "bulkscan_null", "bulkscan_null_grid", "bulkscan_alt_grid"], "scan.jl": ["scan"]}
 
 
+def reference_methods(fname):
+    """The stored form of julia_methods(<reference>/src/<fname>), restricted to REF_FUNCS[fname]."""
+    sigs = json.load(open(SIGS))[fname]
+    return {f: [(npos, set(kws)) for npos, kws in methods] for f, methods in sigs.items()}
+
+
 def test_reference_signatures_parse():
-    ref = julia_methods(os.path.join(REF, "bulkscan.jl"))
+    ref = reference_methods("bulkscan.jl")
     assert {"method", "h2_grid", "nb", "nt_blas", "weights", "prior_variance", "prior_sample_size", "reml", "optim_interval",
             "decomp_scheme", "output_pvals", "chisq_df"} <= ref["bulkscan"][0][1]
-    sc = julia_methods(os.path.join(REF, "scan.jl"))
+    assert set(ref) == set(REF_FUNCS["bulkscan.jl"])
+    sc = reference_methods("scan.jl")
     assert len(sc["scan"]) == 4 and all({"profileLL", "markerID", "h2_grid", "method"} <= kw for _, kw in sc["scan"])
 
 
 def test_julia_binding_accepts_every_reference_keyword():
     mine = julia_methods(os.path.join(ROOT, "bulklmm.jl_amd", "julia", "BulkLMMHIP.jl"))
     for fname, funcs in REF_FUNCS.items():
-        ref = julia_methods(os.path.join(REF, fname))
+        ref = reference_methods(fname)
         for f in funcs:
             assert f in mine, f
             for npos, kws in ref[f]:
@@ -79,9 +86,20 @@ def test_julia_binding_accepts_every_reference_keyword():
 
 def test_python_mirror_accepts_every_reference_keyword(blmm):
     for fname, funcs in REF_FUNCS.items():
-        ref = julia_methods(os.path.join(REF, fname))
+        ref = reference_methods(fname)
         for f in funcs:
             params = set(inspect.signature(getattr(blmm, f)).parameters)
             for _, kws in ref[f]:
                 missing = kws - params
                 assert not missing, f"api.{f} lacks keyword(s) {sorted(missing)}"
+
+
+if __name__ == "__main__":
+    # regenerate the fixture from a checkout of the reference
+    src = os.path.join(sys.argv[1], "src")
+    out = {fname: {f: [[npos, sorted(kws)] for npos, kws in julia_methods(os.path.join(src, fname))[f]] for f in funcs}
+           for fname, funcs in REF_FUNCS.items()}
+    with open(SIGS, "w") as fh:
+        fh.write("{\n" + ",\n".join(
+            f"  {json.dumps(fname)}: {{\n" + ",\n".join(f"    {json.dumps(f)}: {json.dumps(ms)}" for f, ms in fs.items()) + "\n  }"
+            for fname, fs in out.items()) + "\n}\n")

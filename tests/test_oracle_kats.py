@@ -242,30 +242,6 @@ def test_oracle_equals_dense_gls_model(ncov):
     assert np.allclose(ells, dense, rtol=1e-10, atol=1e-9)
 
 
-BXD_PHENO = "/root/reference/data/bxdData/spleen-pheno-nomissing.csv"
-BXD_GENO = "/root/reference/data/bxdData/spleen-bxd-genoprob.csv"
-
-
-@pytest.mark.skipif(not (os.path.exists(BXD_PHENO) and os.path.exists(BXD_GENO)),
-                    reason="the BXD spleen CSVs are listed in the reference's .MISSING_LARGE_BLOBS; this KAT activates when they appear")
-def test_bxd_readme_and_lmmlite_kats():
-    """End-to-end known answers of the reference, usable the moment its two data files exist: README.md:215
-    (sigma2_e, h2) = (0.0942525841453798, 0.850587848871709) for trait 1112 and the R/lmmlite LODs of trait 7919
-    (test/run-lmmlite_R/output/result.lmmlite_{ML,REML}.csv; tolerance of test/scan_test_lmmlite.jl:27-32).
-    Loader as test/generate_test_bxdData.jl:4-14."""
-    import csv
-    ph = np.genfromtxt(BXD_PHENO, delimiter=",", skip_header=1)[:, 1:-1]
-    ge = np.genfromtxt(BXD_GENO, delimiter=",", skip_header=1)[:, 0::2]
-    K = np.round(O.calcKinship(ge), 12)
-    r = O.scan(ph[:, 1111], ge, K)
-    assert abs(r["sigma2_e"] - 0.0942525841453798) <= 1e-8 and abs(r["h2_null"] - 0.850587848871709) <= 1e-6
-    for reml, name in ((False, "ML"), (True, "REML")):
-        rows = list(csv.reader(open(f"/root/reference/test/run-lmmlite_R/output/result.lmmlite_{name}.csv")))[2:]
-        lods = np.array([float(x[4]) for x in rows])
-        got = O.scan(ph[:, 7918], ge, K, reml=reml)["lod"]
-        assert np.max((got - lods) ** 2) <= 1e-9 and np.sum((got - lods) ** 2) <= np.sqrt(1e-9)
-
-
 @pytest.mark.skipif(__import__("shutil").which("gcc") is None, reason="no gcc")
 @pytest.mark.parametrize("ncov,reml,prior,oi", [(0, False, (1.0, 0.0), 1), (2, True, (1.0, 0.1), 1), (1, False, (0.0, 0.0), 3)])
 def test_c_openmp_restatement_equals_numpy_restatement(ncov, reml, prior, oi):
