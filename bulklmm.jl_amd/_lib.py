@@ -28,6 +28,7 @@ EXPORTS = [
     "blmm_kinship_rounded", "blmm_scan_alt", "blmm_scan_alt_dev", "blmm_bulkscan_alt_exact", "blmm_bulkscan_alt_exact_dev",
     "blmm_prepare_dev", "blmm_rotated_rows", "blmm_rotate_block_dev", "blmm_bulkscan_prerotated_dev", "blmm_scan_perms_prerotated_dev",
     "blmm_set_tuning", "blmm_get_tuning", "blmm_lowrank_columns", "blmm_bulkscan_reduced", "blmm_bulkscan_reduced_dev", "blmm_last_reduced_route",
+    "blmm_bulkscan_reduced_async",
     "blmm_last_dims", "blmm_last_lod_colmax", "blmm_last_lod_columns", "blmm_multi_last_colmax", "blmm_multi_last_lod_threshold",
 ]
 
@@ -37,6 +38,10 @@ BLMM_COMPAT_ALT_COUNTER = 1
 BLMM_COMPAT_ALT_TRUE_WEIGHTS = 2
 BLMM_FLAG_H2_AUDIT = 4
 BLMM_GATHER_NONE, BLMM_GATHER_HOST_SHARDS, BLMM_GATHER_ALLGATHER = 0, 1, 2
+# blmm_bulkscan_reduced_async's info block (include/bulklmm_hip.h: BLMM_RINFO_*)
+BLMM_RINFO_LEN = 9
+RINFO_FIELDS = ("route", "lowrank_rescan", "illcond_rescan", "nan_lod", "zero_norm", "neg_eig", "nonpos_weight", "triplets",
+                "device_error")
 
 ERR_ZERO_NORM_MSG = "Dividing by zeros: the input vector can not contain any zeros!"
 
@@ -185,6 +190,7 @@ def load():
     lib.blmm_bulkscan_reduced.argtypes = [vp, op, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, i64, rp, vp, sp]
     lib.blmm_bulkscan_reduced_dev.argtypes = [vp, op, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, i64, rp, vp, sp]
     lib.blmm_last_reduced_route.argtypes = [vp]
+    lib.blmm_bulkscan_reduced_async.argtypes = [vp, op, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, i64, rp, vp, vp]
     lib.blmm_last_dims.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     lib.blmm_last_lod_colmax.argtypes = [vp, vp, vp]
     lib.blmm_last_lod_columns.argtypes = [vp, vp, i64, vp]

@@ -962,6 +962,47 @@ def bulkscan_reduced_dev(ctx: Context, Y, G, K, max_out, argmax_out, h2_out, *, 
     return st
 
 
+def bulkscan_reduced_async(ctx: Context, Y, G, K, max_out, argmax_out, h2_out, info_out, *, method: str = "null-exact", h2_grid=None,
+                           Covar=None, weights=None, addIntercept: bool = True, prior_variance: float = 1.0, prior_sample_size: float = 0.0,
+                           reml: bool = False, optim_interval: int = 1, decomp_scheme: str = "eigen", threshold: Optional[float] = None,
+                           trip_i=None, trip_j=None, trip_lod=None, trip_count=None):
+    """blmm_bulkscan_reduced_async on torch CUDA tensors (layouts as bulkscan_reduced_dev; info_out: int64, BLMM_RINFO_LEN = 9, or
+    None).  Only enqueues on the context's stream and returns: the outputs are valid after ctx.synchronize() or a sync of that
+    stream.  Flagged traits are re-scanned on the device (route 3) instead of a second run; reduced_info() decodes info_out."""
+    m, n = Y.shape
+    p = G.shape[0]
+    grid, ngrid = None, 0
+    if method != "null-exact":
+        grid = np.ascontiguousarray(np.asarray(h2_grid if h2_grid is not None else [i / 10.0 for i in range(10)], dtype=np.float64))
+        ngrid = grid.shape[0]
+    ncov = 0 if Covar is None else Covar.shape[0]
+    if Covar is None:
+        addIntercept = True
+    if info_out is not None and info_out.numel() < L.BLMM_RINFO_LEN:
+        raise BulkLMMError(f"info_out holds {info_out.numel()} entries, the info block {L.BLMM_RINFO_LEN}")
+    o = _opts(_METHODS[method], reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
+    want = threshold is not None
+    r = L.blmm_reduced(None if max_out is None else max_out.data_ptr(), None if argmax_out is None else argmax_out.data_ptr(),
+                       1 if want else 0, float(threshold) if want else 0.0, int(trip_i.numel()) if want else 0,
+                       trip_i.data_ptr() if want else None, trip_j.data_ptr() if want else None,
+                       trip_lod.data_ptr() if want else None, trip_count.data_ptr() if want else None)
+    ctx.check(ctx.lib.blmm_bulkscan_reduced_async(ctx.h, C.byref(o), Y.data_ptr(), n, m, G.data_ptr(), p,
+                                                  None if Covar is None else Covar.data_ptr(), ncov, K.data_ptr(),
+                                                  None if weights is None else weights.data_ptr(), _p(grid), ngrid, C.byref(r),
+                                                  None if h2_out is None else h2_out.data_ptr(),
+                                                  None if info_out is None else info_out.data_ptr()))
+
+
+def reduced_info(info) -> dict:
+    """The info block of bulkscan_reduced_async (host copy: a numpy array or list of BLMM_RINFO_LEN int64) as a dict:
+    route (1 fused, 2 resident matrix, 3 fused + on-device re-scans), lowrank_rescan, illcond_rescan, nan_lod, zero_norm, neg_eig,
+    nonpos_weight, triplets (the exact count of LOD > threshold), device_error (0, or as blmm_status' failure)."""
+    a = np.asarray(info, dtype=np.int64).ravel()
+    if a.size < L.BLMM_RINFO_LEN:
+        raise BulkLMMError(f"an info block holds {L.BLMM_RINFO_LEN} entries, got {a.size}")
+    return {k: int(a[i]) for i, k in enumerate(L.RINFO_FIELDS)}
+
+
 def prepare_dev(ctx: Context, K, *, Covar=None, weights=None, addIntercept: bool = True, decomp_scheme: str = "eigen", status: bool = False):
     """blmm_prepare_dev on torch CUDA tensors (K (n, n); Covar (ncov, n) = n x ncov column-major): design, eigen-decomposition and
     rotation matrix; the context then serves rotate_block_dev / bulkscan_prerotated_dev (one process per GPU: the marker

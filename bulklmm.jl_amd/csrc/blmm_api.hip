@@ -424,7 +424,31 @@ int grid_to_device(blmm_ctx* ctx, const double* h2_grid_host, int64_t ngrid, dou
   }
   int rc = ensure(ctx, ctx->gridd, sizeof(double) * ngrid);
   if (rc) return rc;
-  BLMM_HIP(hipMemcpyAsync(ctx->gridd.p, h2_grid_host, sizeof(double) * ngrid, hipMemcpyHostToDevice, ctx->stream));
+  const size_t bytes = sizeof(double) * (size_t)ngrid;
+  if (ctx->grid_async) {
+    // blmm_bulkscan_reduced_async: through a pinned slot of the context, no wait.  A slot whose copy has not run yet (its event
+    // is pending: back-to-back calls) is left alone and the ring grows instead -- to the depth of the caller's queue at most.
+    blmm_ctx::GridSlot* slot = nullptr;
+    for (auto& g : ctx->gstage)
+      if (g.cap >= bytes && (!g.used || hipEventQuery(g.ev) == hipSuccess)) { slot = &g; break; }
+    if (!slot) {
+      blmm_ctx::GridSlot g;
+      g.cap = bytes < 4096 ? 4096 : bytes;
+      void* h = nullptr;
+      BLMM_HIP(hipHostMalloc(&h, g.cap, hipHostMallocDefault));
+      g.h = static_cast<double*>(h);
+      if (hipEventCreateWithFlags(&g.ev, hipEventDisableTiming) != hipSuccess) { (void)hipHostFree(h); return fail(ctx, BLMM_ERR_HIP, "hipEventCreate failed"); }
+      ctx->gstage.push_back(g);
+      slot = &ctx->gstage.back();
+    }
+    std::memcpy(slot->h, h2_grid_host, bytes);
+    BLMM_HIP(hipMemcpyAsync(ctx->gridd.p, slot->h, bytes, hipMemcpyHostToDevice, ctx->stream));
+    BLMM_HIP(hipEventRecord(slot->ev, ctx->stream));
+    slot->used = true;
+    *out = ptr<double>(ctx->gridd);
+    return BLMM_OK;
+  }
+  BLMM_HIP(hipMemcpyAsync(ctx->gridd.p, h2_grid_host, bytes, hipMemcpyHostToDevice, ctx->stream));
   // the source is caller memory: make sure the copy has left it before we return
   BLMM_HIP(hipStreamSynchronize(ctx->stream));
   *out = ptr<double>(ctx->gridd);
@@ -548,13 +572,15 @@ int lr_region_panels(blmm_ctx* ctx, const Pipe& P, const NullModel& nm, const do
 }
 int lr_region_resid(blmm_ctx* ctx, const Pipe& P, const NullModel& nm, const double* dh2, const LrRegion& rg) {
   return launch_lr_resid(ctx, nm, P.m, lr_tolerance(ctx), P.lam, dh2, ptr<double>(ctx->wbQ), ptr<int>(ctx->wbRk), lr_segments(ctx, P.n), ptr<int>(ctx->lrPerm), rg,
-                         ptr<double>(ctx->lrC), 2 * lr_ldq(P), ptr<int>(ctx->lrFlag), ptr<double>(ctx->lrPart), P.stat);
+                         ptr<double>(ctx->lrC), 2 * lr_ldq(P), ptr<int>(ctx->lrFlag), ptr<double>(ctx->lrPart), P.stat, ctx->red_cur.flags);
 }
 int lr_fix(blmm_ctx* ctx, const Pipe& P, const NullModel& nm, const double* dh2, double* dL, int64_t ldL) {
   // flagged traits (normally none: the kernel reads the count on the device and returns): full-length sums
-  if (ctx->red_cur.pmax) return BLMM_OK;   // reduce-in-epilogue: there is no L to patch -- reduced_impl() reads the count and re-runs
+  // reduce-in-epilogue: there is no L to patch -- reduced_impl() reads the count and re-runs; reduced_async_impl() (red_cur.flags)
+  // has the reduced form of the kernel patch the slot partials instead
+  if (ctx->red_cur.pmax && !ctx->red_cur.flags) return BLMM_OK;
   return launch_scan_fix(ctx, nm, P.Xt, P.ldx, P.p, ptr<double>(ctx->panels), ptr<double>(ctx->lrL), 2 * lr_ldq(P), P.Z0, P.lam, dh2,
-                         ptr<int>(ctx->lrFlag), ptr<int>(ctx->lrPerm), dL, ldL, P.stat);
+                         ptr<int>(ctx->lrFlag), ptr<int>(ctx->lrPerm), dL, ldL, P.stat, ctx->red_cur);
 }
 }  // namespace
 
@@ -565,9 +591,10 @@ int illcond_rescan(blmm_ctx* ctx, const Pipe& P, const NullModel& nm, int64_t m,
   if (P.c < 2 || m <= 0 || P.p <= 0) return BLMM_OK;
   int rc = ensure(ctx, ctx->illList, sizeof(int) * (size_t)m);
   if (rc) return rc;
-  if ((rc = launch_illcond_flag(ctx, nm, m, P.Z0, P.lam, dh2, ptr<int>(ctx->illList), P.stat))) return rc;
-  if (ctx->red_cur.pmax) return BLMM_OK;   // (as lr_fix)
-  return launch_scan_qr(ctx, nm, P.Yt, P.ldy, P.Xt, P.ldx, P.p, P.Z0, P.lam, dh2, ptr<int>(ctx->illList), dL, ldL, P.stat);
+  const bool patch = ctx->red_cur.pmax && ctx->red_cur.flags;   // reduced_async_impl(): flagged beside the scan (lr_finish) already
+  if (!patch && (rc = launch_illcond_flag(ctx, nm, m, P.Z0, P.lam, dh2, ptr<int>(ctx->illList), P.stat))) return rc;
+  if (ctx->red_cur.pmax && !patch) return BLMM_OK;   // (as lr_fix)
+  return launch_scan_qr(ctx, nm, P.Yt, P.ldy, P.Xt, P.ldx, P.p, P.Z0, P.lam, dh2, ptr<int>(ctx->illList), dL, ldL, P.stat, ctx->red_cur);
 }
 
 // every trait's h2 is final: one region
@@ -581,13 +608,19 @@ int lr_finish(blmm_ctx* ctx, const Pipe& P, const NullModel& nm, const double* d
   if ((rc = lr_region_panels(ctx, P, nm, dh2, rg))) return rc;
   tm.mark();
   // residual guard of the weight basis, every trait: side stream, beside the scan kernel; joined below
+  // (reduced_async_impl, red_cur.flags: the conditioning guard joins it there, and when triplets are wanted the scan waits for
+  // both -- its epilogue appends none for a flagged trait, the re-scan kernels append those)
+  const bool ahead = ctx->red_cur.flags != nullptr;
+  if (ahead && P.c >= 2 && (rc = ensure(ctx, ctx->illList, sizeof(int) * (size_t)P.m))) return rc;
   BLMM_HIP(hipEventRecord(ctx->ev_fork, main_stream));
   BLMM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
   ctx->stream = ctx->side;
   rc = lr_region_resid(ctx, P, nm, dh2, rg);
+  if (!rc && ahead && P.c >= 2) rc = launch_illcond_flag(ctx, nm, P.m, P.Z0, P.lam, dh2, ptr<int>(ctx->illList), P.stat, ctx->red_cur.flags);
   ctx->stream = main_stream;
   if (rc) return rc;
   BLMM_HIP(hipEventRecord(ctx->ev_join, ctx->side));
+  if (ahead && ctx->red_cur.want_trip) BLMM_HIP(hipStreamWaitEvent(main_stream, ctx->ev_join, 0));
   if ((rc = lr_region_scan(ctx, P, rg, dL, ldL))) return rc;
   BLMM_HIP(hipStreamWaitEvent(main_stream, ctx->ev_join, 0));
   if ((rc = lr_fix(ctx, P, nm, dh2, dL, ldL))) return rc;
@@ -637,6 +670,12 @@ int lr_finish_split(blmm_ctx* ctx, const Pipe& P, const NullModel& nm, double* d
   rc = lr_region_resid(ctx, P, nm, dh2, r0);
   ctx->stream = main_stream;
   if (rc) return rc;
+  // (reduced_async_impl with triplets: each region's scan waits for its guard -- see lr_finish; it splits only at c = 1)
+  const bool ahead = ctx->red_cur.flags != nullptr && ctx->red_cur.want_trip;
+  if (ahead) {
+    BLMM_HIP(hipEventRecord(ctx->ev_join, ctx->side));
+    BLMM_HIP(hipStreamWaitEvent(main_stream, ctx->ev_join, 0));
+  }
   if ((rc = lr_region_scan(ctx, P, r0, dL, ldL))) return rc;
   // ---- region 1: its guard on the first side stream (behind region 0's), its scan on the main stream
   BLMM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_b2, 0));
@@ -646,6 +685,7 @@ int lr_finish_split(blmm_ctx* ctx, const Pipe& P, const NullModel& nm, double* d
   if (rc) return rc;
   BLMM_HIP(hipEventRecord(ctx->ev_join, ctx->side));
   BLMM_HIP(hipStreamWaitEvent(main_stream, ctx->ev_b2, 0));
+  if (ahead) BLMM_HIP(hipStreamWaitEvent(main_stream, ctx->ev_join, 0));
   if ((rc = lr_region_scan(ctx, P, r1, dL, ldL))) return rc;
   BLMM_HIP(hipStreamWaitEvent(main_stream, ctx->ev_join, 0));
   if ((rc = lr_fix(ctx, P, nm, dh2, dL, ldL))) return rc;
@@ -714,7 +754,8 @@ int blmm_create(int device_id, void* hip_stream, blmm_ctx** out) {
       hipEventCreateWithFlags(&ctx->ev_wb, hipEventDisableTiming) != hipSuccess ||
       hipStreamCreateWithFlags(&ctx->copy, hipStreamNonBlocking) != hipSuccess ||
       hipEventCreateWithFlags(&ctx->ev_in, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->ev_inY, hipEventDisableTiming) != hipSuccess) {
+      hipEventCreateWithFlags(&ctx->ev_inY, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&ctx->ev_call, hipEventDisableTiming) != hipSuccess) {
     blmm_destroy(ctx);
     return BLMM_ERR_HIP;
   }
@@ -747,7 +788,7 @@ void blmm_destroy(blmm_ctx* ctx) {
                     &ctx->iyy, &ctx->h2, &ctx->h2idx, &ctx->sig2, &ctx->ell, &ctx->isx, &ctx->stat, &ctx->gridd, &ctx->misc,
                     &ctx->EllTab, &ctx->inY, &ctx->inG, &ctx->inK, &ctx->inCov, &ctx->inW, &ctx->outL, &ctx->outH2,
                     &ctx->tmpA, &ctx->tmpB, &ctx->tmpC, &ctx->perm, &ctx->r0, &ctx->altbuf, &ctx->logtab, &ctx->lraw,
-                    &ctx->wbQ, &ctx->wbW, &ctx->wbRk, &ctx->lrT, &ctx->lrC, &ctx->lrL, &ctx->lrFlag, &ctx->lrPart, &ctx->lrPerm, &ctx->lrDen0, &ctx->eigW, &ctx->xf32, &ctx->pf32, &ctx->brSt, &ctx->brList, &ctx->illList, &ctx->qrSlab, &ctx->lodtab, &ctx->dynFac, &ctx->pvtab, &ctx->outP, &ctx->redbuf, &ctx->redtrip, &ctx->altC, &ctx->rf32, &ctx->btG};
+                    &ctx->wbQ, &ctx->wbW, &ctx->wbRk, &ctx->lrT, &ctx->lrC, &ctx->lrL, &ctx->lrFlag, &ctx->lrPart, &ctx->lrPerm, &ctx->lrDen0, &ctx->eigW, &ctx->xf32, &ctx->pf32, &ctx->brSt, &ctx->brList, &ctx->illList, &ctx->qrSlab, &ctx->lodtab, &ctx->dynFac, &ctx->pvtab, &ctx->outP, &ctx->redbuf, &ctx->redtrip, &ctx->altC, &ctx->rf32, &ctx->btG, &ctx->redflag};
   for (DevBuf* b : bufs) if (b->p) hipFree(b->p);
   for (auto& s : ctx->evsets) for (auto& e : s.e) (void)hipEventDestroy(e);
   if (ctx->side) { (void)hipStreamSynchronize(ctx->side); (void)hipStreamDestroy(ctx->side); }
@@ -761,6 +802,11 @@ void blmm_destroy(blmm_ctx* ctx) {
   if (ctx->ev_wb) (void)hipEventDestroy(ctx->ev_wb);
   if (ctx->ev_in) (void)hipEventDestroy(ctx->ev_in);
   if (ctx->ev_inY) (void)hipEventDestroy(ctx->ev_inY);
+  if (ctx->ev_call) (void)hipEventDestroy(ctx->ev_call);
+  for (auto& g : ctx->gstage) {
+    if (g.ev) { (void)hipEventSynchronize(g.ev); (void)hipEventDestroy(g.ev); }
+    if (g.h) (void)hipHostFree(g.h);
+  }
   if (ctx->copy) { (void)hipStreamSynchronize(ctx->copy); (void)hipStreamDestroy(ctx->copy); }
   if (ctx->side2) { (void)hipStreamSynchronize(ctx->side2); (void)hipStreamDestroy(ctx->side2); }
   if (ctx->own_stream) hipStreamDestroy(ctx->stream);
@@ -1113,7 +1159,10 @@ static int scan_pipeline(blmm_ctx* ctx, const blmm_opts* opts, Pipe& P, Timer& t
       // with their ramps, and one region wins (m = 4445, a rank's share of the BXD problem on 8 GPUs: 0.651 against 0.677 ms per
       // step; m = 8889: 0.777 against 0.776; m = 35554: the split is worth 2.7 %).  BLMM_LR_SPLIT=1: always
       const char* split_env = dev_env("BLMM_LR_SPLIT");                // tuning key "lr_split" (tests hold the two forms against each other)
-      const bool split_on = split_env ? split_env[0] != '0' : (ctx->tune.lr_split < 0 ? m >= 8192 : ctx->tune.lr_split != 0);
+      // (reduced_async_impl at c >= 2: one region -- its conditioning guard runs ahead of the scan over every trait's final h2;
+      // the split and the single-region forms give the same bits, tests/test_gpu_guard.py)
+      const bool split_on = (ctx->red_cur.flags && P.c >= 2) ? false
+                          : split_env ? split_env[0] != '0' : (ctx->tune.lr_split < 0 ? m >= 8192 : ctx->tune.lr_split != 0);
       BrentSplit sp;
       if ((rc = launch_brent(ctx, nm, P.Yt, P.ldy, m, P.Z0, P.lam, dh2_out, nullptr, nullptr, P.stat, split_on ? 1 : 0, &sp))) return rc;
       tm.mark();
@@ -1536,6 +1585,87 @@ int blmm_bulkscan_reduced(blmm_ctx* ctx, const blmm_opts* opts, const double* Y,
 }
 
 int blmm_last_reduced_route(const blmm_ctx* ctx) { return ctx ? ctx->last_reduced_route : 0; }
+
+// ---------------------------------------------------------------------------------------------------
+// Stream-ordered reduced bulkscan (include/bulklmm_hip.h: blmm_bulkscan_reduced_async).  The fused route does not speculate: the
+// per-trait guards write flags (RedArgs::flags), the reduced forms of k_scan_fix / k_scan_qr write the flagged traits' slot
+// partials over the epilogue's before k_red_final and append their triplets, and the epilogue appends none for a flagged trait
+// (when triplets are wanted the guards run ahead of the scan: lr_finish) -- so *count is exact with no second run and no host
+// round trip.  Routes without a fused instantiation go through the resident L as reduced_impl's route 2 does.
+static int reduced_async_impl(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG, int64_t p,
+                              const double* dCovar, int64_t ncov, const double* dK, const double* dweights, const double* h2_grid_host,
+                              int64_t ngrid, const blmm_reduced* out, double* dh2_out, int64_t* dinfo) {
+  int rc = check_opts(ctx, opts);
+  if (rc) return rc;
+  if (!out || !dY || !dG || !dK || (!dh2_out && opts->method != BLMM_ALT_GRID)) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_reduced_async: NULL buffer");
+  if (out->cap < 0 || (out->cap > 0 && (!out->ti || !out->tj || !out->tlod)) || (out->want_triplets && !out->count))
+    return fail(ctx, BLMM_ERR_INVALID, "bulkscan_reduced_async: triplet buffers");
+  if (opts->method != BLMM_NULL_EXACT && opts->method != BLMM_NULL_GRID && opts->method != BLMM_ALT_GRID)
+    return fail(ctx, BLMM_ERR_METHOD, "Unknown method; choose null-exact, null-grid or alt-grid.");
+  if (n < 1 || m < 0 || p < 0 || p > 0x7fffffffLL || m > 0x7fffffffLL) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
+  if (opts->method != BLMM_NULL_EXACT) {       // (grid_to_device checks it again; here: before anything is enqueued)
+    if (!h2_grid_host || ngrid < 1) return fail(ctx, BLMM_ERR_INVALID, "h2 grid is empty");
+    for (int64_t g = 0; g < ngrid; ++g)
+      if (std::isinf(h2_grid_host[g] / (1.0 - h2_grid_host[g]))) return fail(ctx, BLMM_ERR_H2_ONE, "Heritability of 1 is not allowed.");
+  }
+  BLMM_HIP(hipSetDevice(ctx->device));
+  if ((rc = check_sticky(ctx))) return rc;
+  // the side streams start behind everything already on the stream (a previous call's readers of the shared workspace)
+  BLMM_HIP(hipEventRecord(ctx->ev_call, ctx->stream));
+  BLMM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_call, 0));
+  BLMM_HIP(hipStreamWaitEvent(ctx->side2, ctx->ev_call, 0));
+  const bool fused = p > 0 && m > 0 && (opts->method == BLMM_NULL_GRID || wants_lowrank(ctx, opts, n, dCovar, ncov));
+  if (fused) {
+    const int nslot = 2 * (int)((p + 127) / 128);
+    const int64_t ldm = round_up(m, 64);
+    if ((rc = ensure(ctx, ctx->redbuf, (sizeof(double) + sizeof(int)) * (size_t)nslot * (size_t)ldm))) return rc;
+    if ((rc = ensure(ctx, ctx->redflag, sizeof(int) * (size_t)m))) return rc;
+    RedArgs r;
+    r.pmax = ptr<double>(ctx->redbuf); r.parg = reinterpret_cast<int*>(r.pmax + (size_t)nslot * ldm); r.ldm = ldm;
+    r.want_trip = out->want_triplets ? 1 : 0; r.thr = out->thr; r.cap = out->cap;
+    r.ti = out->ti; r.tj = out->tj; r.tl = out->tlod; r.cnt = reinterpret_cast<unsigned long long*>(out->count);
+    r.flags = ptr<int>(ctx->redflag);
+    if (out->count) BLMM_HIP(hipMemsetAsync(out->count, 0, sizeof(int64_t), ctx->stream));
+    BLMM_HIP(hipMemsetAsync(r.flags, 0, sizeof(int) * (size_t)m, ctx->stream));
+    ctx->red_cur = r;
+    ctx->grid_async = true;
+    rc = bulkscan_dev_impl(ctx, opts, dY, n, m, dG, p, dCovar, ncov, dK, dweights, h2_grid_host, ngrid, nullptr, p, dh2_out, nullptr, PvReq());
+    ctx->red_cur = RedArgs();
+    ctx->grid_async = false;
+    if (rc) return rc;
+    if ((rc = launch_red_final(ctx, r, nslot, m, out->colmax, out->argmax))) return rc;
+    ctx->last_L = nullptr;                    // no matrix of this call: an earlier one is not served as its result
+    return dinfo ? launch_red_info(ctx, ptr<int64_t>(ctx->stat), 0, out->want_triplets ? out->count : nullptr, dinfo) : BLMM_OK;
+  }
+  // through a resident L
+  if ((rc = ensure(ctx, ctx->outL, sizeof(double) * (size_t)(p > 0 ? p : 1) * (size_t)(m > 0 ? m : 1)))) return rc;
+  double* dL = ptr<double>(ctx->outL);
+  double* dH = dh2_out;
+  if (opts->method == BLMM_ALT_GRID) {
+    if ((rc = ensure(ctx, ctx->altbuf, sizeof(double) * (size_t)(p > 0 ? p : 1) * (size_t)(m > 0 ? m : 1)))) return rc;
+    dH = ptr<double>(ctx->altbuf);
+  }
+  ctx->grid_async = true;
+  rc = bulkscan_dev_impl(ctx, opts, dY, n, m, dG, p, dCovar, ncov, dK, dweights, h2_grid_host, ngrid, dL, p > 0 ? p : 1, dH, nullptr, PvReq());
+  ctx->grid_async = false;
+  if (rc) return rc;
+  if (m > 0) { ctx->last_L = dL; ctx->last_p = p; ctx->last_m = m; ctx->last_f32 = false; }
+  if (out->colmax && m > 0 && (rc = launch_colmax(ctx, dL, p, m, p > 0 ? p : 1, out->colmax, out->argmax))) return rc;
+  if (out->want_triplets && (rc = launch_threshold(ctx, dL, p, m, p > 0 ? p : 1, out->thr, out->cap, out->ti, out->tj, out->tlod, out->count))) return rc;
+  if (!dinfo) return BLMM_OK;
+  if (!ctx->stat.p && (rc = ensure(ctx, ctx->stat, sizeof(int64_t) * NSTAT))) return rc;
+  return launch_red_info(ctx, ptr<int64_t>(ctx->stat), 2, out->want_triplets ? out->count : nullptr, dinfo);
+}
+
+int blmm_bulkscan_reduced_async(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG,
+                                int64_t p, const double* dCovar, int64_t ncov, const double* dK, const double* dweights,
+                                const double* h2_grid_host, int64_t ngrid, const blmm_reduced* out, double* dh2_out,
+                                int64_t* dinfo) {
+  if (!ctx) return BLMM_ERR_INVALID;
+  // a -log10 p request has nothing to attach to here (no matrix): refused, and consumed like every entry point's
+  if (pv_take(ctx).armed) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_reduced_async: a blmm_set_log10p_output request is pending (the reduced call writes no matrix)");
+  return reduced_async_impl(ctx, opts, dY, n, m, dG, p, dCovar, ncov, dK, dweights, h2_grid_host, ngrid, out, dh2_out, dinfo);
+}
 
 // ---------------------------------------------------------------------------------------------------
 // dLperms_out (fp64) or dLperms32_out (fp32, kernels_scan_f32.hip): exactly one of them when nperms > 0

@@ -80,6 +80,10 @@ struct RedArgs {
   double* pmax = nullptr; int* parg = nullptr; int64_t ldm = 0;
   int want_trip = 0; double thr = 0.0; int64_t cap = 0;
   int32_t* ti = nullptr; int32_t* tj = nullptr; double* tl = nullptr; unsigned long long* cnt = nullptr;
+  // blmm_bulkscan_reduced_async: per-trait guard flags (bit 0: the weight-basis residual guard, bit 1: the conditioning guard).
+  // Non-null: the re-scan kernels (k_scan_fix, k_scan_qr) patch the flagged traits' partials and append their triplets on the
+  // device, and the scan epilogues append none for a flagged trait (the guards have run before them when triplets are wanted).
+  int* flags = nullptr;
 };
 }  // namespace blmm
 
@@ -93,7 +97,7 @@ struct blmm_ctx {
   std::string err;
   // grow-only workspace
   blmm::DevBuf Ks, V, lam, U, Zs, Z0, Rp, Yt, Xt, panels, iyy, h2, h2idx, sig2, ell, isx, stat, gridd, misc, EllTab,
-      inY, inG, inK, inCov, inW, outL, outH2, tmpA, tmpB, tmpC, perm, r0, altbuf, logtab, lraw, wbQ, wbW, wbRk, lrT, lrC, lrL, lrFlag, lrPart, lrPerm, lrDen0, eigW, xf32, pf32, brSt, brList, illList, qrSlab, lodtab, dynFac, pvtab, outP, redbuf, redtrip, altC, rf32, btG;
+      inY, inG, inK, inCov, inW, outL, outH2, tmpA, tmpB, tmpC, perm, r0, altbuf, logtab, lraw, wbQ, wbW, wbRk, lrT, lrC, lrL, lrFlag, lrPart, lrPerm, lrDen0, eigW, xf32, pf32, brSt, brList, illList, qrSlab, lodtab, dynFac, pvtab, outP, redbuf, redtrip, altC, rf32, btG, redflag;
   // event sets: one per timed call since the last blmm_read_timings (grown on demand, reused afterwards)
   struct EvSet { hipEvent_t e[8]; int n; };
   std::vector<EvSet> evsets;
@@ -128,6 +132,13 @@ struct blmm_ctx {
   // blmm_bulkscan_reduced: set while that call's scan kernels run (blmm_api.hip: scan_args); last_reduced_route: 1 = the
   // reduce-in-epilogue kernels stood, 2 = through a resident L (no fused instantiation, or a trait needed a re-scan)
   blmm::RedArgs red_cur; int last_reduced_route = 0;
+  // blmm_bulkscan_reduced_async: no host-blocking call in steady state.  grid_async: grid_to_device stages the caller's grid in
+  // a pinned slot (gstage: a slot is reused once its event says its copy has run; a new slot is added otherwise) instead of
+  // waiting for a pageable upload.  ev_call: recorded on the stream where a call starts; the side streams wait for it.
+  bool grid_async = false;
+  struct GridSlot { double* h = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool used = false; };
+  std::vector<GridSlot> gstage;
+  hipEvent_t ev_call = nullptr;
   blmm::Tuning tune;                   // blmm_set_tuning
   bool perm_ready = false; int perm_ready_n = 0; int64_t perm_ready_nperms = 0; uint64_t perm_ready_seed = 0;   // launch_perm_gen -> launch_perm_panel
   int64_t lr_last_ldq = 0, lr_last_m = 0;   // panel-region width / trait count of the last low-rank null-exact scan (blmm_lowrank_columns)
@@ -278,6 +289,9 @@ struct ScanArgs {
 int launch_threshold(blmm_ctx* ctx, const double* dL, int64_t p, int64_t m, int64_t ldL, double thr, int64_t cap,
                      int32_t* di, int32_t* dj, double* dlod, int64_t* dcount);
 int launch_red_final(blmm_ctx* ctx, const RedArgs& r, int nslot, int64_t m, double* mx, int64_t* arg);
+// blmm_bulkscan_reduced_async: the info block (BLMM_RINFO_*) from the status counters, in stream order; route 0: 3 when a guard
+// flagged a trait, else 1.  Also raises the context's sticky word on a device-side failure (as k_sticky).
+int launch_red_info(blmm_ctx* ctx, const int64_t* stat, int route, const int64_t* count, int64_t* info);
 int launch_scan_exact(blmm_ctx* ctx, const ScanArgs& a, int c);
 // A region of the panel arrays of the low-rank form: columns [col0, col0 + ncol), the shared-weights class at its front
 // (counts[0] traits) and the other class at its back (counts[1]); counts live on the device.
@@ -323,10 +337,11 @@ struct LrArgs {
 int launch_scan_lr(blmm_ctx* ctx, const LrArgs& la);
 int launch_lr_resid(blmm_ctx* ctx, const NullModel& nm, int64_t m, double tol, const double* lam, const double* h2,
                     const double* Q, const int* rk, const LrSeg& seg, const int* perm, const LrRegion& rg, const double* Cp, int64_t ldp,
-                    int* flag_list, double* part, int64_t* stat);
+                    int* flag_list, double* part, int64_t* stat, int* flags = nullptr);
+// red.pmax != nullptr: the reduced form (k_scan_fix<C, true>): the flagged traits' slot partials and triplets instead of L's columns
 int launch_scan_fix(blmm_ctx* ctx, const NullModel& nm, const double* Xt, int64_t ldx, int64_t p, const double* P0,
                     const double* Ls, int64_t ldp, const double* Z0, const double* lam, const double* h2,
-                    const int* flag_list, const int* perm, double* L, int64_t ldL, int64_t* stat);
+                    const int* flag_list, const int* perm, double* L, int64_t ldL, int64_t* stat, const RedArgs& red = RedArgs());
 // shared-weights class: column order of the panels (perm, info) and the per-marker denominators of the unweighted model
 int launch_lr_classify(blmm_ctx* ctx, int n, int64_t m, double tol, const double* lam, const double* h2, const int* fin,
                        const int* list, const unsigned int* list_cnt, int* perm, const LrRegion& rg, const LrSeg& seg);
@@ -360,9 +375,10 @@ int launch_dyn_perm(blmm_ctx* ctx, const NullModel& nm, const double* Yt, int64_
                     const int32_t* perm, int64_t ncols, int orig, double* r0, double* panel, int64_t ldp, int64_t* stat);
 // kernels_dyn.hip: conditioning guard of the null-exact scan (c >= 2) and the QR-grade re-scan of the flagged traits
 int launch_illcond_flag(blmm_ctx* ctx, const NullModel& nm, int64_t m, const double* Z0, const double* lam, const double* h2,
-                        int* list, int64_t* stat);
+                        int* list, int64_t* stat, int* flags = nullptr);
 int launch_scan_qr(blmm_ctx* ctx, const NullModel& nm, const double* Yt, int64_t ldy, const double* Xt, int64_t ldx, int64_t p,
-                   const double* Z0, const double* lam, const double* h2, const int* list, double* L, int64_t ldL, int64_t* stat);
+                   const double* Z0, const double* lam, const double* h2, const int* list, double* L, int64_t ldL, int64_t* stat,
+                   const RedArgs& red = RedArgs());
 // kernels_lowrank.hip
 // the segments a call with n individuals uses (one when the basis comes from the multi-workgroup / LDS kernels: n > 80)
 LrSeg lr_segments(const blmm_ctx* ctx, int n);

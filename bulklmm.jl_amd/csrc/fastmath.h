@@ -262,4 +262,35 @@ __device__ __forceinline__ void wave_count(int64_t* cnt, bool flag) {
 // h2 estimates on a boundary of [0, 1] (blmm_status.n_h2_boundary)
 __device__ __forceinline__ bool h2_on_boundary(double h2) { return h2 <= 1e-6 || h2 >= 1.0 - 1e-6; }
 
+// Reduced form of the per-trait re-scans (RedArgs, blmm_internal.h; blmm_bulkscan_reduced_async): a wave's 64 consecutive markers
+// i0 .. i0 + 63 of one trait (lane = marker - i0) -> the trait's slot partial (maximum, lowest marker: k_colmax's rule, a NaN never
+// wins) and, `trip` set, its LOD > thr triplets behind the device counter.  Every lane of the wave must call it.
+__device__ __forceinline__ void red_wave64(const RedArgs& R, int64_t trait, int64_t i0, int lane, double lod, bool valid, bool trip) {
+  double best = -INFINITY; int bi = -1;
+  if (valid && lod > best) { best = lod; bi = lane; }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double ob = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (ob > best || (ob == best && oi >= 0 && (bi < 0 || oi < bi))) { best = ob; bi = oi; }   // k_colmax's rule
+  }
+  if (lane == 0) {
+    const int64_t at = (i0 >> 6) * R.ldm + trait;
+    R.pmax[at] = best;
+    R.parg[at] = bi < 0 ? -1 : (int)(i0 + bi);
+  }
+  if (!trip || !R.want_trip) return;
+  const bool hit = valid && lod > R.thr;
+  const unsigned long long mask = __ballot(hit);
+  if (mask == 0ull) return;
+  const int leader = (int)__builtin_ctzll(mask);
+  unsigned long long base = 0;
+  if (lane == leader) base = atomicAdd(R.cnt, (unsigned long long)__builtin_popcountll(mask));
+  base = __shfl(base, leader, 64);
+  if (hit) {
+    const unsigned long long slot = base + (unsigned long long)__builtin_popcountll(mask & ((1ull << lane) - 1ull));
+    if ((int64_t)slot < R.cap) { R.ti[slot] = (int32_t)(i0 + lane); R.tj[slot] = (int32_t)trait; R.tl[slot] = lod; }
+  }
+}
+
 }  // namespace blmm

@@ -31,7 +31,7 @@ namespace blmm {
 template <int C>
 __global__ void __launch_bounds__(256) k_illcond_flag(int n, int64_t m, const double* __restrict__ Z0,
                                                       const double* __restrict__ lam, const double* __restrict__ h2v,
-                                                      double rho_min, int* __restrict__ list, int64_t* stat) {
+                                                      double rho_min, int* __restrict__ list, int64_t* stat, int* __restrict__ flags) {
   extern __shared__ __attribute__((aligned(16))) double sh[];
   double* sLam = sh;
   double* sZ = sh + n;
@@ -75,6 +75,7 @@ __global__ void __launch_bounds__(256) k_illcond_flag(int n, int64_t m, const do
   if (!(rho >= rho_min)) {
     const unsigned long long slot = atomicAdd((unsigned long long*)&stat[ST_ILLCOND], 1ull);
     list[slot] = (int)j;
+    if (flags) atomicOr(&flags[j], 2);     // (blmm_bulkscan_reduced_async) per trait
   }
 }
 
@@ -121,13 +122,15 @@ __device__ __forceinline__ void project_out(double* tgt, const double* Qb, int n
 // CQ: compile-time bound of the per-marker coefficient arrays (c <= CQ).  buf: (c + 2) * n doubles per workgroup -- the
 // weights' square roots S, the orthonormal basis Qb (c columns) and the normalised trait residual yb -- in LDS when it fits
 // (`slab` == nullptr) and in a per-workgroup slab of global memory otherwise.
-template <int CQ>
+// RED (blmm_bulkscan_reduced_async): the same LODs reduced per wave to the trait's slot partials (over what the scan epilogue
+// and k_scan_fix left there, before k_red_final) plus the LOD > thr triplets (k_scan_fix's reduced form appended none for these).
+template <int CQ, bool RED = false>
 __global__ void __launch_bounds__(256) k_scan_qr(int n, int c, const double* __restrict__ Yt, int64_t ldy,
                                                  const double* __restrict__ Xt, int64_t ldx, int64_t p,
                                                  const double* __restrict__ Z0, const double* __restrict__ lam,
                                                  const double* __restrict__ h2v, const int* __restrict__ list,
                                                  double* slab, double* __restrict__ L, int64_t ldL, int64_t* stat,
-                                                 double* __restrict__ Pv, int64_t ldPv, const double* __restrict__ pvtab) {
+                                                 double* __restrict__ Pv, int64_t ldPv, const double* __restrict__ pvtab, RedArgs red) {
   extern __shared__ __attribute__((aligned(16))) double sh[];
   __shared__ double s_red[4 * 8];
   const int64_t cnt = stat[ST_ILLCOND];
@@ -171,9 +174,13 @@ __global__ void __launch_bounds__(256) k_scan_qr(int n, int c, const double* __r
       for (int k = threadIdx.x; k < n; k += 256) yb[k] *= inv;
     }
     __syncthreads();                            // basis and trait residual complete: from here every thread reads all rows
-    for (int64_t i0 = 0; i0 < p; i0 += 256) {
+    const int64_t iend = RED ? 128 * ((p + 127) / 128) : p;   // RED: whole waves up to the last slot
+    for (int64_t i0 = 0; i0 < iend; i0 += 256) {
       const int64_t i = i0 + threadIdx.x;
-      if (i >= p) continue;
+      if constexpr (RED) {
+        if (i - (threadIdx.x & 63) >= iend) continue;          // a slot that does not exist: the whole wave
+        // (lanes beyond p compute on Xt's zero padding, i < ldx, and are masked: the whole wave reaches the reduction)
+      } else if (i >= p) continue;
       double t[CQ], t2[CQ];
 #pragma unroll
       for (int q = 0; q < CQ; ++q) { t[q] = 0.0; t2[q] = 0.0; }
@@ -201,11 +208,15 @@ __global__ void __launch_bounds__(256) k_scan_qr(int n, int c, const double* __r
         xx = fma(xp, xp, xx);
         num = fma(xp, yb[k], num);
       }
-      if (!(sqrt(xx) > 2.220446049250313e-16)) atomicAdd((unsigned long long*)&stat[ST_ZERO_NORM], 1ull);
+      if ((!RED || i < p) && !(sqrt(xx) > 2.220446049250313e-16)) atomicAdd((unsigned long long*)&stat[ST_ZERO_NORM], 1ull);
       const double r = num / sqrt(xx);
       const double u1 = 1.0 - r * r;            // r2lod, src/bulkscan_helpers.jl:22-24
       double lod = scale * log10(u1);
       if (!(u1 > 0.0)) lod = (u1 == 0.0) ? INFINITY : NAN;
+      if constexpr (RED) {
+        red_wave64(red, j, i - (threadIdx.x & 63), threadIdx.x & 63, lod, i < p, true);
+        continue;
+      }
       L[j * ldL + i] = lod;
       if (Pv) Pv[j * ldPv + i] = fast_log10p1(lod, reinterpret_cast<const dpair*>(pvtab));   // the fused `output_pvals` column
     }
@@ -850,7 +861,7 @@ double illcond_rho_min(const blmm_ctx* ctx) {
 }
 
 int launch_illcond_flag(blmm_ctx* ctx, const NullModel& nm, int64_t m, const double* Z0, const double* lam, const double* h2,
-                        int* list, int64_t* stat) {
+                        int* list, int64_t* stat, int* flags) {
   if (m <= 0 || nm.c < 2) return BLMM_OK;
   const double rho = illcond_rho_min(ctx);
   if (!(rho > 0.0)) return BLMM_OK;
@@ -865,7 +876,7 @@ int launch_illcond_flag(blmm_ctx* ctx, const NullModel& nm, int64_t m, const dou
     return BLMM_OK;
   }
 #define IF(C) do { if (lds > 48 * 1024) BLMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_illcond_flag<C>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    hipLaunchKernelGGL(k_illcond_flag<C>, dim3(blocks), dim3(256), lds, ctx->stream, nm.n, m, Z0, lam, h2, rho, list, stat); } while (0)
+    hipLaunchKernelGGL(k_illcond_flag<C>, dim3(blocks), dim3(256), lds, ctx->stream, nm.n, m, Z0, lam, h2, rho, list, stat, flags); } while (0)
   switch (nm.c) {
     BLMM_FOR_EACH_C(IF)
     default: return fail(ctx, BLMM_ERR_UNSUPPORTED, BLMM_C_ERR);
@@ -877,8 +888,9 @@ int launch_illcond_flag(blmm_ctx* ctx, const NullModel& nm, int64_t m, const dou
 
 int launch_scan_qr(blmm_ctx* ctx, const NullModel& nm, const double* Yt, int64_t ldy, const double* Xt, int64_t ldx, int64_t p,
                    const double* Z0, const double* lam, const double* h2, const int* list, double* L, int64_t ldL,
-                   int64_t* stat) {
+                   int64_t* stat, const RedArgs& red) {
   if (p <= 0 || nm.c < 2 || !(illcond_rho_min(ctx) > 0.0)) return BLMM_OK;
+  if (red.pmax && nm.c > 8) return fail(ctx, BLMM_ERR_UNSUPPORTED, "k_scan_qr: the reduced form takes c <= 8");
   const size_t per = (size_t)(nm.c + 2) * nm.n;
   const unsigned grid = (unsigned)(2 * (ctx->num_cus > 0 ? ctx->num_cus : 256));
   double* slab = nullptr;
@@ -889,12 +901,15 @@ int launch_scan_qr(blmm_ctx* ctx, const NullModel& nm, const double* Yt, int64_t
     slab = ptr<double>(ctx->qrSlab);
     lds = 0;
   }
-  if (nm.c <= 8) {
+  if (red.pmax) {
+    if (lds > 48 * 1024) BLMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scan_qr<8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((k_scan_qr<8, true>), dim3(grid), dim3(256), lds, ctx->stream, nm.n, nm.c, Yt, ldy, Xt, ldx, p, Z0, lam, h2, list, slab, nullptr, ldL, stat, nullptr, 0, nullptr, red);
+  } else if (nm.c <= 8) {
     if (lds > 48 * 1024) BLMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scan_qr<8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_scan_qr<8>, dim3(grid), dim3(256), lds, ctx->stream, nm.n, nm.c, Yt, ldy, Xt, ldx, p, Z0, lam, h2, list, slab, L, ldL, stat, ctx->pv_cur, ctx->pv_cur_ld, ptr<double>(ctx->pvtab));
+    hipLaunchKernelGGL(k_scan_qr<8>, dim3(grid), dim3(256), lds, ctx->stream, nm.n, nm.c, Yt, ldy, Xt, ldx, p, Z0, lam, h2, list, slab, L, ldL, stat, ctx->pv_cur, ctx->pv_cur_ld, ptr<double>(ctx->pvtab), red);
   } else {
     if (lds > 48 * 1024) BLMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scan_qr<32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_scan_qr<32>, dim3(grid), dim3(256), lds, ctx->stream, nm.n, nm.c, Yt, ldy, Xt, ldx, p, Z0, lam, h2, list, slab, L, ldL, stat, ctx->pv_cur, ctx->pv_cur_ld, ptr<double>(ctx->pvtab));
+    hipLaunchKernelGGL(k_scan_qr<32>, dim3(grid), dim3(256), lds, ctx->stream, nm.n, nm.c, Yt, ldy, Xt, ldx, p, Z0, lam, h2, list, slab, L, ldL, stat, ctx->pv_cur, ctx->pv_cur_ld, ptr<double>(ctx->pvtab), red);
   }
   KCHECK();
   return BLMM_OK;

@@ -1147,7 +1147,7 @@ __global__ void __launch_bounds__(256) k_lr_resid(int n, int64_t m, const double
 __global__ void __launch_bounds__(256) k_lr_resid2(int nslice, int64_t m, double tol2, const double* __restrict__ part,
                                                    int64_t ldp, const int* __restrict__ rk, const int* __restrict__ perm,
                                                    int64_t col0, int64_t ncol, const int64_t* __restrict__ counts,
-                                                   int* __restrict__ flag_list, int64_t* stat) {
+                                                   int* __restrict__ flag_list, int64_t* stat, int* __restrict__ flags) {
   if (rk[0] < 0) return;
   const int64_t j = col0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // panel column
   double rel2 = 0.0;
@@ -1159,6 +1159,7 @@ __global__ void __launch_bounds__(256) k_lr_resid2(int nslice, int64_t m, double
     if (!(rel2 <= tol2)) {
       const unsigned long long slot = atomicAdd((unsigned long long*)&stat[10], 1ull);
       flag_list[slot] = (int)j;            // panel column; order of the list is immaterial: k_scan_fix recomputes whole columns
+      if (flags) atomicOr(&flags[perm[j]], 1);   // (blmm_bulkscan_reduced_async) per trait
     }
   }
   // largest squared residual of the block -> stat[9] (bit pattern of a non-negative double orders like an integer)
@@ -1172,14 +1173,17 @@ __global__ void __launch_bounds__(256) k_lr_resid2(int nslice, int64_t m, double
 //   r^2 = num^2 / (Sxx - |u|^2) ,  LOD = -(n/2) log10(1 - r^2)
 // with plain fp64 VALU arithmetic and libm log10.  A fixed grid walks (flagged trait, 256-marker tile) pairs; it reads
 // the count on the device (no host round trip) and exits at once when nothing was flagged (the normal case).
-template <int C>
+// RED (blmm_bulkscan_reduced_async): the same LODs, but each wave reduces its 64 markers to the trait's slot partial (pmax /
+// parg, written over what the scan epilogue left there, before k_red_final) and appends the LOD > thr triplets -- except for a
+// trait the conditioning guard flagged as well (flags bit 1): k_scan_qr re-scans it next and its values are the final ones.
+template <int C, bool RED = false>
 __global__ void __launch_bounds__(256) k_scan_fix(NullModel nm, const double* __restrict__ Xt, int64_t ldx, int64_t p,
                                                    const double* __restrict__ P0, const double* __restrict__ Ls, int64_t ldp,
                                                    const double* __restrict__ Z0, const double* __restrict__ lam,
                                                    const double* __restrict__ h2v, const int* __restrict__ flag_list,
                                                    const int* __restrict__ perm, double* __restrict__ L, int64_t ldL,
                                                    int64_t* stat, double* __restrict__ Pv, int64_t ldPv,
-                                                   const double* __restrict__ pvtab) {
+                                                   const double* __restrict__ pvtab, RedArgs red) {
   constexpr int KC = 256, NL = C * (C + 1) / 2;
   __shared__ double s_a0[KC], s_w[KC], s_wz[C][KC];
   const int64_t cnt = stat[10];
@@ -1219,7 +1223,30 @@ __global__ void __launch_bounds__(256) k_scan_fix(NullModel nm, const double* __
         }
       }
     }
-    if (i < p) {
+    if constexpr (RED) {
+      // whole waves: every lane takes part in the slot's reduction; slots from 2 ceil(p / 128) on do not exist
+      const int64_t iw = i - (threadIdx.x & 63);
+      if (iw >= 128 * ((p + 127) / 128)) continue;
+      double lod = -INFINITY;
+      if (i < p) {
+        double li[NL];
+#pragma unroll
+        for (int e = 0; e < NL; ++e) li[e] = Ls[(int64_t)e * ldp + j];
+        double xx = sxx;
+#pragma unroll
+        for (int q = 0; q < C; ++q) {
+          double u = 0.0;
+#pragma unroll
+          for (int e = 0; e <= q; ++e) u = fma(li[q * (q + 1) / 2 + e], sq[e], u);
+          xx = fma(-u, u, xx);
+        }
+        const double r2 = (num * num) / xx;
+        const double u1 = 1.0 - r2;
+        lod = scale * log10(u1);
+        if (!(u1 > 0.0)) { lod = (u1 == 0.0) ? INFINITY : NAN; nnan += (u1 != 0.0); }
+      }
+      red_wave64(red, jt, iw, threadIdx.x & 63, lod, i < p, !(red.flags && (red.flags[jt] & 2)));
+    } else if (i < p) {
       double li[NL];
 #pragma unroll
       for (int e = 0; e < NL; ++e) li[e] = Ls[(int64_t)e * ldp + j];
@@ -1420,7 +1447,7 @@ int launch_lr_panels(blmm_ctx* ctx, const NullModel& nm, const double* Yt, int64
 // The guard (all traits): the caller runs it on the side stream beside the scan kernel, then launch_scan_fix.
 int launch_lr_resid(blmm_ctx* ctx, const NullModel& nm, int64_t m, double tol, const double* lam, const double* h2,
                     const double* Q, const int* rk, const LrSeg& seg, const int* perm, const LrRegion& rg, const double* Cp, int64_t ldp,
-                    int* flag_list, double* part, int64_t* stat) {
+                    int* flag_list, double* part, int64_t* stat, int* flags) {
   if (m <= 0) return BLMM_OK;
   const int nslice = (nm.n + LRR_KS - 1) / LRR_KS;
   const size_t lds = sizeof(double) * ((size_t)LRR_KS * (1 + (size_t)LRR_QC));
@@ -1430,17 +1457,18 @@ int launch_lr_resid(blmm_ctx* ctx, const NullModel& nm, int64_t m, double tol, c
   hipLaunchKernelGGL(k_lr_resid, dim3((unsigned)((rg.ncol + rthreads - 1) / rthreads), (unsigned)nslice), dim3(rthreads), lds, ctx->stream, nm.n, m, lam, h2, Q,
                      rk, perm, rg.col0, rg.ncol, rg.counts, Cp, ldp, part, rg.segcnt, seg.S, (int64_t)nm.npad * nm.n);
   hipLaunchKernelGGL(k_lr_resid2, dim3((unsigned)((rg.ncol + 255) / 256)), dim3(256), 0, ctx->stream, nslice, m, tol * tol, part, ldp, rk,
-                     perm, rg.col0, rg.ncol, rg.counts, flag_list, stat);
+                     perm, rg.col0, rg.ncol, rg.counts, flag_list, stat, flags);
   KCHECK();
   return BLMM_OK;
 }
 
 int launch_scan_fix(blmm_ctx* ctx, const NullModel& nm, const double* Xt, int64_t ldx, int64_t p, const double* P0,
                     const double* Ls, int64_t ldp, const double* Z0, const double* lam, const double* h2,
-                    const int* flag_list, const int* perm, double* L, int64_t ldL, int64_t* stat) {
+                    const int* flag_list, const int* perm, double* L, int64_t ldL, int64_t* stat, const RedArgs& red) {
   if (p <= 0) return BLMM_OK;
   const unsigned grid = (unsigned)(8 * (ctx->num_cus > 0 ? ctx->num_cus : 256));
-#define FX(C) hipLaunchKernelGGL(k_scan_fix<C>, dim3(grid), dim3(256), 0, ctx->stream, nm, Xt, ldx, p, P0, Ls, ldp, Z0, lam, h2, flag_list, perm, L, ldL, stat, ctx->pv_cur, ctx->pv_cur_ld, ptr<double>(ctx->pvtab))
+#define FX(C) do { if (red.pmax) hipLaunchKernelGGL((k_scan_fix<C, true>), dim3(grid), dim3(256), 0, ctx->stream, nm, Xt, ldx, p, P0, Ls, ldp, Z0, lam, h2, flag_list, perm, nullptr, ldL, stat, nullptr, 0, nullptr, red); \
+    else hipLaunchKernelGGL(k_scan_fix<C>, dim3(grid), dim3(256), 0, ctx->stream, nm, Xt, ldx, p, P0, Ls, ldp, Z0, lam, h2, flag_list, perm, L, ldL, stat, ctx->pv_cur, ctx->pv_cur_ld, ptr<double>(ctx->pvtab), red); } while (0)
   switch (nm.c) {
     case 1: FX(1); break;
     case 2: FX(2); break;

@@ -151,6 +151,36 @@ __global__ void __launch_bounds__(256) k_red_final(const double* __restrict__ pm
   if (arg) arg[j] = bi;
 }
 
+// The info block of blmm_bulkscan_reduced_async (include/bulklmm_hip.h: BLMM_RINFO_*), written in stream order behind the call's
+// work.  A device-side failure (stat[8] < 0: the weight-basis kernel timed out at its grid barrier; stat[11]: the eigensolver's abort
+// code) also raises the context's sticky word, as k_sticky does, so that blmm_synchronize reports it.
+__global__ void k_red_info(const int64_t* __restrict__ stat, int route, const int64_t* __restrict__ count, int64_t* __restrict__ info,
+                           int64_t* hflag) {
+  const int64_t nfix = stat[10], nqr = stat[ST_ILLCOND];
+  info[BLMM_RINFO_ROUTE] = route ? route : ((nfix > 0 || nqr > 0) ? 3 : 1);
+  info[BLMM_RINFO_LOWRANK_RESCAN] = nfix;
+  info[BLMM_RINFO_ILLCOND_RESCAN] = nqr;
+  info[BLMM_RINFO_NAN_LOD] = stat[ST_NAN_LOD];
+  info[BLMM_RINFO_ZERO_NORM] = stat[ST_ZERO_NORM];
+  info[BLMM_RINFO_NEG_EIG] = stat[ST_NEG_EIG];
+  info[BLMM_RINFO_NONPOS_WEIGHT] = stat[ST_NONPOS_W];
+  info[BLMM_RINFO_TRIPLETS] = count ? *count : 0;
+  int64_t f = 0, code = 0;
+  if (stat[8] < 0) f |= 1;
+  if (stat[11] != 0) { f |= 2; code = stat[11]; }
+  info[BLMM_RINFO_DEVICE_ERROR] = f ? ((f & 2) ? code : -1) : 0;
+  if (f && hflag) {
+    if (f & 2) hflag[1] = code;
+    __hip_atomic_fetch_or(hflag, f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
+int launch_red_info(blmm_ctx* ctx, const int64_t* stat, int route, const int64_t* count, int64_t* info) {
+  hipLaunchKernelGGL(k_red_info, dim3(1), dim3(1), 0, ctx->stream, stat, route, count, info, const_cast<int64_t*>(ctx->hflag));
+  KCHECK();
+  return BLMM_OK;
+}
+
 int launch_red_final(blmm_ctx* ctx, const RedArgs& r, int nslot, int64_t m, double* mx, int64_t* arg) {
   if (m <= 0 || (!mx && !arg)) return BLMM_OK;
   hipLaunchKernelGGL(k_red_final, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, r.pmax, r.parg, r.ldm, nslot, m, mx, arg);

@@ -148,9 +148,11 @@ __device__ __forceinline__ void red_row(const RedArgs& R, int64_t trait, int64_t
     R.parg[at] = bi < 0 ? -1 : (int)i0 + bi;
   }
   if (R.want_trip) {                                           // kernel argument: a scalar branch
+    // a trait a guard flagged gets its triplets from the re-scan kernels instead (blmm_bulkscan_reduced_async)
+    const int live = (!R.flags || R.flags[trait] == 0) ? vl : 0;
     bool h[NB]; int my = 0;
 #pragma unroll
-    for (int nb = 0; nb < NB; ++nb) { h[nb] = (NB * c + nb < vl) && out[nb] > R.thr; my += h[nb] ? 1 : 0; }
+    for (int nb = 0; nb < NB; ++nb) { h[nb] = (NB * c + nb < live) && out[nb] > R.thr; my += h[nb] ? 1 : 0; }
     const unsigned long long any = __ballot(my != 0);
     if (any != 0ull) {                                         // rare: one wave-aggregated atomic reserves the slots (as k_threshold)
       const unsigned long long b0 = __ballot((my & 1) != 0), b1 = __ballot((my & 2) != 0), b2 = __ballot((my & 4) != 0);

@@ -11,7 +11,7 @@
 # every `ccall`'s symbol, return type and argument tuple (arity and types) against the prototype in include/bulklmm_hip.h.
 module BulkLMMHIP
 
-export bulkscan_reduced, DeviceLOD, lod_columns, set_tuning, calcKinship, bulkscan, bulkscan_null, bulkscan_null_grid, bulkscan_alt_grid, bulkscan_alt_exact, scan, bulkscan_multi, lod2log10p, get_thresholds,
+export bulkscan_reduced, bulkscan_reduced_async!, synchronize, DeviceLOD, lod_columns, set_tuning, calcKinship, bulkscan, bulkscan_null, bulkscan_null_grid, bulkscan_alt_grid, bulkscan_alt_exact, scan, bulkscan_multi, lod2log10p, get_thresholds,
        lod_threshold, lod_colmax, pinned_matrix, host_register, host_unregister
 
 const libblmm = get(ENV, "BULKLMM_HIP_LIB", joinpath(@__DIR__, "..", "csrc", "libbulklmm_hip.so"))
@@ -205,6 +205,32 @@ function bulkscan_reduced(Y::Array{Float64, 2}, G::Array{Float64, 2}, Covar::Uni
     end
 end
 bulkscan_reduced(Y::Array{Float64, 2}, G::Array{Float64, 2}, K::Array{Float64, 2}; kwargs...) = bulkscan_reduced(Y, G, nothing, K; kwargs...)
+
+# ---- the stream-ordered form (blmm_bulkscan_reduced_async) on DEVICE buffers (e.g. AMDGPU.jl arrays' pointers): it enqueues and
+# returns; `out`'s buffers, dh2 and the info block (RINFO_LEN Int64 in device memory: route, re-scan counts, status counts, the
+# triplet count, device error; include/bulklmm_hip.h) are valid after `synchronize()`.  0-based markers / traits, as the C ABI.
+const RINFO_LEN = 9
+function bulkscan_reduced_async!(dY::Ptr{Float64}, n::Int64, m::Int64, dG::Ptr{Float64}, p::Int64, dK::Ptr{Float64},
+                                 out::BlmmReduced, dh2::Ptr{Float64}, dinfo::Ptr{Int64}; method::String = "null-exact",
+                                 h2_grid::Array{Float64, 1} = collect(0.0:0.1:0.9), dCovar::Ptr{Float64} = Ptr{Float64}(C_NULL),
+                                 ncov::Int64 = 0, dweights::Ptr{Float64} = Ptr{Float64}(C_NULL), addIntercept::Bool = true,
+                                 prior_variance::Float64 = 1.0, prior_sample_size::Float64 = 0.0, reml::Bool = false,
+                                 optim_interval::Int64 = 1, decomp_scheme::String = "eigen")
+    meth = method == "null-exact" ? NULL_EXACT : method == "null-grid" ? NULL_GRID : method == "alt-grid" ? ALT_GRID :
+           error("Unknown method `$method`; choose null-exact, null-grid or alt-grid.")
+    check_n(n)
+    o = BlmmOpts(meth, reml, ncov == 0 ? true : addIntercept, decomp(decomp_scheme), optim_interval, 0, prior_variance, prior_sample_size)
+    grid = meth == NULL_EXACT ? Float64[] : h2_grid
+    GC.@preserve grid begin
+        check(ccall((:blmm_bulkscan_reduced_async, libblmm), Cint,
+                    (Ptr{Cvoid}, Ref{BlmmOpts}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64,
+                     Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ref{BlmmReduced}, Ptr{Float64}, Ptr{Int64}),
+                    context(), o, dY, n, m, dG, p, dCovar, ncov, dK, dweights, grid, length(grid), out, dh2, dinfo))
+    end
+    return nothing
+end
+# waits for the context's stream and reports a device-side failure of the calls before it
+synchronize() = check(ccall((:blmm_synchronize, libblmm), Cint, (Ptr{Cvoid},), context()))
 
 # nb / nt_blas are accepted and ignored (thread blocking knobs of the CPU implementation)
 function bulkscan_null(Y::Array{Float64, 2}, G::Array{Float64, 2}, K::Array{Float64, 2};

@@ -29,7 +29,8 @@ extern "C" {
 #endif
 
 #define BLMM_VERSION 210 /* 0.2.3: L_out == NULL keeps the matrix in HBM (blmm_bulkscan, blmm_bulkscan_multi), blmm_last_lod_colmax /
-                            blmm_last_lod_columns / blmm_last_dims, blmm_bulkscan_reduced[_dev] (no L at all), blmm_tuning;
+                            blmm_last_lod_columns / blmm_last_dims, blmm_bulkscan_reduced[_dev] (no L at all), blmm_tuning,
+                            blmm_bulkscan_reduced_async + BLMM_RINFO_* (stream-ordered, flagged traits re-scanned on the device);
                             205 (0.2.2): blmm_status.n_h2_boundary / n_h2_multimodal / n_illcond_rescan (appended), BLMM_FLAG_H2_AUDIT;
                             201: lowrank_shared, readers, blmm_scan_alt; 200: lowrank_fallback, BLMM_STREAM_NULL, multi-GPU */
 
@@ -243,6 +244,38 @@ int blmm_bulkscan_reduced_dev(blmm_ctx* ctx, const blmm_opts* opts, const double
                               const double* h2_grid_host, int64_t ngrid, const blmm_reduced* out, double* dh2_out,
                               blmm_status* status);
 int blmm_last_reduced_route(const blmm_ctx* ctx);
+
+/* Stream-ordered form of blmm_bulkscan_reduced_dev (same arguments; `out` and dh2_out hold DEVICE pointers): the call only
+ * enqueues on the context's stream and returns -- in steady state (the shapes of the previous call on this context) it makes
+ * no host-blocking HIP call, so a caller can enqueue step k+1 while step k runs.  The results, *out->count and the info block
+ * are valid once that stream has reached the end of the call (blmm_synchronize, or a wait on the caller's stream).  When a
+ * workspace buffer has to grow the call may synchronise, as every entry point does.
+ * Routes (dinfo[BLMM_RINFO_ROUTE]):
+ *   1  fused: the scan epilogues reduce (as route 1 of blmm_bulkscan_reduced_dev); no trait was flagged;
+ *   2  through the context's resident matrix + k_colmax / k_threshold (alt-grid, c >= 4 null covariates, tuning
+ *      exact_full_rank, p = 0 or m = 0); the blmm_last_* consumers then serve that matrix;
+ *   3  fused, and the traits a guard flagged (weight-basis residual: k_scan_fix; conditioning: k_scan_qr) were re-scanned on
+ *      the device into the reduction -- no second run, no host round trip.
+ * Routes 1 and 3 leave no resident matrix (blmm_last_dims reports none).  Maxima, arg-maxima, the triplet count and the stored
+ * triplets are bit-identical to blmm_lod_colmax_dev / blmm_lod_threshold_dev on the matrix blmm_bulkscan_dev writes under the
+ * same tuning; *count is exact also when it exceeds cap (then `cap` genuine, distinct triplets are stored; order unspecified).
+ * A pending blmm_set_log10p_output request is refused (BLMM_ERR_INVALID) and consumed.  Argument errors return before anything
+ * is enqueued.  The conditions blmm_status reports arrive in the info block instead (dinfo may be NULL):
+ *   dinfo[BLMM_RINFO_LEN] (int64, device memory), written on the stream when the call's work completes:
+ *     ROUTE             1 / 2 / 3 above
+ *     LOWRANK_RESCAN    traits re-scanned because the weight-basis expansion residual was above lr_tol (blmm_status.lowrank_fallback)
+ *     ILLCOND_RESCAN    traits re-scanned because the weighted null design was ill-conditioned (blmm_status.n_illcond_rescan)
+ *     NAN_LOD, ZERO_NORM, NEG_EIG, NONPOS_WEIGHT   as blmm_status.n_nan_lod / n_zero_norm / n_neg_eig / n_nonpos_weight
+ *     TRIPLETS          *count (0 when no triplets were asked for)
+ *     DEVICE_ERROR      0; -1: the weight-basis kernel timed out at its grid barrier; -7 / -8: the eigensolver gave up (as
+ *                       blmm_status' failure); the next blmm_synchronize / call on the context then returns BLMM_ERR_HIP */
+#define BLMM_RINFO_LEN 9
+enum { BLMM_RINFO_ROUTE = 0, BLMM_RINFO_LOWRANK_RESCAN, BLMM_RINFO_ILLCOND_RESCAN, BLMM_RINFO_NAN_LOD, BLMM_RINFO_ZERO_NORM,
+       BLMM_RINFO_NEG_EIG, BLMM_RINFO_NONPOS_WEIGHT, BLMM_RINFO_TRIPLETS, BLMM_RINFO_DEVICE_ERROR };
+int blmm_bulkscan_reduced_async(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG,
+                                int64_t p, const double* dCovar, int64_t ncov, const double* dK, const double* dweights,
+                                const double* h2_grid_host, int64_t ngrid, const blmm_reduced* out, double* dh2_out,
+                                int64_t* dinfo);
 
 /* ---- the pipeline in three calls, for hosts that run ONE PROCESS PER GPU (torch.distributed, MPI; bench.py --gpus N):
  * blmm_bulkscan_dev on every rank repeats the rotation of the whole G (10-25 % of a rank's step at n >= 500).  Instead every
