@@ -120,7 +120,7 @@ def test_fullsize_config3_alt_grid_sampled_columns(blmm, bxd):
     assert set(np.unique(a.h2_panel[:, ::97])).issubset(set(GRID16))
     cols = [0, 63, 64, 17777, M - 1]
     ref, tab = O.bulkscan_alt_grid(Y[:, cols], G, K, GRID16, return_tables=True)
-    assert_lod_close(a.L[:, cols], ref.L, atol=1e-9)
+    assert_lod_close(a.L[:, cols], ref.L)
     nt = assert_h2_panel_ties_only(a.h2_panel[:, cols], ref.h2_panel, tab, GRID16)
     print(f"configs[3] alt-grid: {nt} of {ref.h2_panel.size} sampled h2_panel entries differ from the oracle's (all ties)")
     assert nt <= 1e-3 * ref.h2_panel.size

@@ -198,7 +198,7 @@ def test_bulkscan_alt_grid_matches_oracle(blmm, ncov):
     grid = [i / 10.0 for i in range(10)]
     got = blmm.bulkscan_alt_grid(Y, G, K, grid, Cov)
     ref, tab = O.bulkscan_alt_grid(Y, G, K, grid, Covar=Cov, return_tables=True)
-    assert_lod_close(got.L, ref.L, atol=1e-9)
+    assert_lod_close(got.L, ref.L)
     # the arg-max grid value: equal, or a tie in the oracle's own logL1 table (strict `<` decides those at rounding level)
     nt = assert_h2_panel_ties_only(got.h2_panel, ref.h2_panel, tab, grid)
     assert nt <= 1e-3 * ref.h2_panel.size
@@ -206,7 +206,7 @@ def test_bulkscan_alt_grid_matches_oracle(blmm, ncov):
     rq = O.bulkscan_alt_grid(Y, G, K, grid, Covar=Cov, compat_counter_quirk=True)
     nq = assert_h2_panel_ties_only(qk.h2_panel, rq.h2_panel, tab, grid, quirk=True)
     assert nq <= 1e-3 * rq.h2_panel.size
-    assert_lod_close(qk.L, rq.L, atol=1e-9)
+    assert_lod_close(qk.L, rq.L)
 
 
 def test_bulkscan_dispatcher(blmm):
@@ -379,7 +379,7 @@ def test_indefinite_kinship_warns_and_matches(blmm):
         warnings.simplefilter("ignore")
         al = blmm.bulkscan_alt_grid(Y, G, Kn, grid)
         ar = O.bulkscan_alt_grid(Y, G, Kn, grid)
-    assert_lod_close(al.L, ar.L, atol=1e-9)
+    assert_lod_close(al.L, ar.L)
     # exact LOD kernel with the identity weight basis (negative eigenvalues leave the smooth weight family): the seam
     # with per-trait h2 on the grid
     h2 = np.asarray(got.h2_null_list)
@@ -428,7 +428,7 @@ def test_golden_fixture(blmm):
     assert np.array_equal(gr.h2_null_list, z["grid_h2"])
     assert_lod_close(gr.L, z["grid_L"])
     al = blmm.bulkscan_alt_grid(Y, G, K, grid)
-    assert_lod_close(al.L, z["alt_L"], atol=1e-9)
+    assert_lod_close(al.L, z["alt_L"])
     _, tab = O.bulkscan_alt_grid(Y, G, K, grid, return_tables=True)
     assert assert_h2_panel_ties_only(al.h2_panel, z["alt_h2"], tab, grid) <= 1e-3 * al.h2_panel.size
 
@@ -997,7 +997,7 @@ def test_many_covariates_every_method(blmm, ncov):
     assert_lod_close(gg.L, gr.L)
     ag = blmm.bulkscan_alt_grid(Y[:, :11], G, K, grid, Cov)
     ar, atab = O.bulkscan_alt_grid(Y[:, :11], G, K, grid, Covar=Cov, return_tables=True)
-    assert_lod_close(ag.L, ar.L, atol=1e-9)
+    assert_lod_close(ag.L, ar.L)
     assert assert_h2_panel_ties_only(ag.h2_panel, ar.h2_panel, atab, grid) <= 1e-3 * ar.h2_panel.size
     # scan: null, alt and the permutation test
     y = Y[:, 0]
@@ -1047,7 +1047,7 @@ def test_runtime_covariate_counts_every_method(blmm, ncov, n):
     assert_lod_close(gg.L, gr.L)
     ag = blmm.bulkscan_alt_grid(Y[:, :7], G, K, grid, Cov)
     ar, atab = O.bulkscan_alt_grid(Y[:, :7], G, K, grid, Covar=Cov, return_tables=True)
-    assert_lod_close(ag.L, ar.L, atol=1e-9)
+    assert_lod_close(ag.L, ar.L)
     assert assert_h2_panel_ties_only(ag.h2_panel, ar.h2_panel, atab, grid) <= 1e-3 * ar.h2_panel.size
     y = Y[:, 0]
     nperms = 19

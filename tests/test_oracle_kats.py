@@ -296,3 +296,51 @@ def test_oracle_scan_alt_is_the_profile_likelihood_ratio_and_restates_the_closin
         q0 = O.wls(y0, X0[:, :1], np.sqrt(O.makeweights(null.h2, lam)), prior).ell
         assert abs(a_ref["lod"][i] - (q1 - q0) / np.log(10)) < 1e-10
     assert np.all(a_true["lod"] >= -1e-9)          # a likelihood ratio of nested models
+
+
+@pytest.mark.skipif(__import__("shutil").which("gcc") is None, reason="no gcc")
+@pytest.mark.parametrize("ncov,reml,prior,weighted,ngrid", [(0, False, (1.0, 0.0), False, 16), (2, True, (1.0, 0.1), False, 16),
+                                                            (2, True, (1.0, 0.1), True, 16), (0, False, (1.0, 0.0), True, 256)])
+def test_composed_grid_and_permutation_oracles_equal_the_numpy_restatement(ncov, reml, prior, weighted, ngrid):
+    """oracle/grid_ref.py -- the oracles the every-entry GPU tests use for null-grid, alt-grid and the permutation test, composed
+    from the C restatement at fixed heritabilities, the NumPy Ell table and tmax!'s fold -- against bulklmm_oracle's own
+    bulkscan_null_grid, bulkscan_alt_grid (both h2_panel rules) and scan: L to 1e-12 absolute, grid choices and h2_panel equal.
+    c = 1 and c = 3, ML and REML with a prior, weights (pre-scaled inputs), and a 256-point grid."""
+    from oracle import grid_ref as R
+    p, m = (200, 33) if ngrid == 16 else (64, 9)
+    Y, G, K, Cov = make_data(p=p, m=m, seed=1201 + ncov + 10 * weighted, ncov=ncov)
+    n = Y.shape[0]
+    w = np.random.default_rng(12).uniform(0.5, 2.0, n) if weighted else None
+    grid = [i / 16.0 for i in range(16)] if ngrid == 16 else list(np.linspace(0.0, 0.95, ngrid))
+    kw = dict(Covar=Cov, weights=w, prior_variance=prior[0], prior_sample_size=prior[1], reml=reml)
+    ng = O.bulkscan_null_grid(Y, G, K, grid, **kw)
+    L, pick, Ell = R.null_grid(Y, G, K, grid, Cov, w, prior, reml, nthreads=2)
+    assert np.array_equal(pick, ng.h2_null_list)
+    assert np.abs(L - ng.L).max() <= 1e-12
+    assert len(np.unique(pick)) >= 2                           # the case really has several bins
+    for quirk in (False, True):
+        al = O.bulkscan_alt_grid(Y, G, K, grid, compat_counter_quirk=quirk, **kw)
+        La, panel, mism = R.alt_grid(Y, G, K, grid, Cov, w, prior, reml, quirk=quirk, dev_panel=al.h2_panel, block=13 if ngrid == 16 else m, nthreads=2, Ell=Ell)
+        assert np.abs(La - al.L).max() <= 1e-12
+        assert np.array_equal(panel, al.h2_panel) and mism == []
+        assert len(np.unique(panel)) >= 3
+        if not quirk:
+            first = panel
+    if ngrid != 16:
+        return
+    # the mismatch report: a panel moved to another grid value is reported, with a gap that is not a tie
+    moved = first.copy()
+    moved[5, 7] = grid[0] if first[5, 7] != grid[0] else grid[-1]
+    _, _, mism = R.alt_grid(Y, G, K, grid, Cov, w, prior, reml, dev_panel=moved, block=64, nthreads=2, Ell=Ell)
+    assert [(i, j) for i, j, _ in mism] == [(5, 7)] and mism[0][2] > 1e-12
+    if weighted or ncov:
+        return
+    # permutations, chunked over the markers, against one unchunked oracle call on the same rotation
+    y = Y[:, 0]
+    pidx = O.make_perm_idx(n, 9, 3)
+    rot = O.transform_rotation(y, G, K)
+    h2 = 0.37
+    lod, Lp = R.perms(y, G, K, pidx, h2, rot, chunk=37)
+    one = O.scan(y, G, K, covar=np.ones((n, 1)), addIntercept=False, permutation_test=True, nperms=9, perm_idx=pidx, h2_override=h2,
+                 rotation_override=rot)
+    assert np.abs(lod - one["lod"]).max() <= 1e-12 and np.abs(Lp - one["L_perms"]).max() <= 1e-12
