@@ -370,7 +370,7 @@ int prepare(blmm_ctx* ctx, const blmm_opts* o, const double* dY, int64_t n, int6
   int rc = prepare_eigen(ctx, o, n, dCovar, ncov, dK, dweights, centered, P, tm);
   const bool xt_recorded = ctx->stop_event_used;
   ctx->stop_event_next = nullptr; ctx->stop_event_used = false;
-  if (rc) { ctx->up_pending = false; return rc; }
+  if (rc) return rc;
   // (host entry points) the eigen phase is queued: now the traits and the markers go up, beside it; this stream reads them next
   if (ctx->up_pending) {
     if ((rc = flush_upload(ctx))) return rc;
@@ -960,39 +960,27 @@ int blmm_kinship_dev(blmm_ctx* ctx, const double* dG, int64_t n, int64_t p, doub
   return launch_kinship(ctx, dG, n, p, dK_out, ptr<double>(ctx->tmpA));
 }
 
-int blmm_kinship(blmm_ctx* ctx, const double* G, int64_t n, int64_t p, double* K_out) {
-  if (!ctx) return BLMM_ERR_INVALID;
-  if (!G || !K_out || n < 1 || p < 1) return fail(ctx, BLMM_ERR_INVALID, "calcKinship: bad arguments");
-  BLMM_HIP(hipSetDevice(ctx->device));
-  int rc;
-  if ((rc = ensure(ctx, ctx->inG, sizeof(double) * n * p))) return rc;
-  if ((rc = ensure(ctx, ctx->inK, sizeof(double) * n * n))) return rc;
-  BLMM_HIP(hipMemcpyAsync(ctx->inG.p, G, sizeof(double) * n * p, hipMemcpyHostToDevice, ctx->stream));
-  if ((rc = blmm_kinship_dev(ctx, ptr<double>(ctx->inG), n, p, ptr<double>(ctx->inK)))) return rc;
-  BLMM_HIP(hipMemcpyAsync(K_out, ctx->inK.p, sizeof(double) * n * n, hipMemcpyDeviceToHost, ctx->stream));
-  BLMM_HIP(hipStreamSynchronize(ctx->stream));
-  return BLMM_OK;
-}
-
 __global__ void k_round_digits(double* __restrict__ v, int64_t cnt, double scale) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < cnt) v[i] = rint(v[i] * scale) / scale;
 }
 
+// digits < 0: blmm_kinship
 int blmm_kinship_rounded(blmm_ctx* ctx, const double* G, int64_t n, int64_t p, int64_t digits, double* K_out) {
   if (!ctx) return BLMM_ERR_INVALID;
   if (!G || !K_out || n < 1 || p < 1 || digits > 300) return fail(ctx, BLMM_ERR_INVALID, "calcKinship: bad arguments");
-  BLMM_HIP(hipSetDevice(ctx->device));
+  HostCall hc(ctx);
   int rc;
-  if ((rc = ensure(ctx, ctx->inG, sizeof(double) * n * p))) return rc;
-  if ((rc = ensure(ctx, ctx->inK, sizeof(double) * n * n))) return rc;
-  BLMM_HIP(hipMemcpyAsync(ctx->inG.p, G, sizeof(double) * n * p, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = hc.begin()) || (rc = ensure(ctx, ctx->inK, sizeof(double) * n * n)) || (rc = hc.up(ctx->inG, G, sizeof(double) * n * p))) return rc;
   if ((rc = blmm_kinship_dev(ctx, ptr<double>(ctx->inG), n, p, ptr<double>(ctx->inK)))) return rc;
   if (digits >= 0 && digits <= 17)   // beyond 17 digits rounding a double changes nothing (and 10^digits would overflow)
     hipLaunchKernelGGL(k_round_digits, dim3((unsigned)((n * n + 255) / 256)), dim3(256), 0, ctx->stream, ptr<double>(ctx->inK), n * n, std::pow(10.0, (double)digits));
-  BLMM_HIP(hipMemcpyAsync(K_out, ctx->inK.p, sizeof(double) * n * n, hipMemcpyDeviceToHost, ctx->stream));
-  BLMM_HIP(hipStreamSynchronize(ctx->stream));
-  return BLMM_OK;
+  if ((rc = hc.down(K_out, ctx->inK.p, sizeof(double) * n * n))) return rc;
+  return hc.finish();
+}
+
+int blmm_kinship(blmm_ctx* ctx, const double* G, int64_t n, int64_t p, double* K_out) {
+  return blmm_kinship_rounded(ctx, G, n, p, -1, K_out);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1006,18 +994,16 @@ int blmm_lod_colmax_dev(blmm_ctx* ctx, const double* dL, int64_t p, int64_t m, i
 int blmm_lod_colmax(blmm_ctx* ctx, const double* L, int64_t p, int64_t m, double* max_out, int64_t* argmax_out) {
   if (!ctx) return BLMM_ERR_INVALID;
   if (!L || !max_out || p < 1 || m < 0) return fail(ctx, BLMM_ERR_INVALID, "lod_colmax: bad arguments");
-  BLMM_HIP(hipSetDevice(ctx->device));
+  HostCall hc(ctx);
+  const size_t mm = m > 0 ? m : 1;
   int rc;
-  if ((rc = ensure(ctx, ctx->outL, sizeof(double) * (size_t)p * (m > 0 ? m : 1)))) return rc;
-  if ((rc = ensure(ctx, ctx->tmpA, sizeof(double) * (size_t)(m > 0 ? m : 1)))) return rc;
-  if ((rc = ensure(ctx, ctx->tmpB, sizeof(int64_t) * (size_t)(m > 0 ? m : 1)))) return rc;
-  BLMM_HIP(hipMemcpyAsync(ctx->outL.p, L, sizeof(double) * (size_t)p * m, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = hc.begin()) || (rc = hc.up(ctx->outL, L, sizeof(double) * (size_t)p * m)) || (rc = ensure(ctx, ctx->tmpA, sizeof(double) * mm)) ||
+      (rc = ensure(ctx, ctx->tmpB, sizeof(int64_t) * mm))) return rc;
   if (m > 0) { ctx->last_L = ptr<double>(ctx->outL); ctx->last_p = p; ctx->last_m = m; ctx->last_f32 = false; }
-  if ((rc = launch_colmax(ctx, ptr<double>(ctx->outL), p, m, p, ptr<double>(ctx->tmpA), ptr<int64_t>(ctx->tmpB)))) return rc;
-  BLMM_HIP(hipMemcpyAsync(max_out, ctx->tmpA.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-  if (argmax_out) BLMM_HIP(hipMemcpyAsync(argmax_out, ctx->tmpB.p, sizeof(int64_t) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-  BLMM_HIP(hipStreamSynchronize(ctx->stream));
-  return BLMM_OK;
+  if ((rc = launch_colmax(ctx, ptr<double>(ctx->outL), p, m, p, ptr<double>(ctx->tmpA), ptr<int64_t>(ctx->tmpB))) ||
+      (rc = hc.down(max_out, ctx->tmpA.p, sizeof(double) * (size_t)m)) || (rc = hc.down(argmax_out, ctx->tmpB.p, sizeof(int64_t) * (size_t)m)))
+    return rc;
+  return hc.finish();
 }
 
 // host-pointer forms of the consumers (upload, reduce on the device, download the small result)
@@ -1025,38 +1011,37 @@ int blmm_lod2log10p(blmm_ctx* ctx, const double* L, int64_t p, int64_t m, int64_
   if (!ctx) return BLMM_ERR_INVALID;
   if (!L || !P_out || p < 0 || m < 0 || chisq_df < 1) return fail(ctx, BLMM_ERR_INVALID, "lod2log10p: bad arguments");
   if ((size_t)p * m == 0) return BLMM_OK;
-  BLMM_HIP(hipSetDevice(ctx->device));
+  HostCall hc(ctx);
   int rc;
-  if ((rc = ensure(ctx, ctx->altbuf, sizeof(double) * (size_t)p * m * 2))) return rc;
+  if ((rc = hc.begin()) || (rc = ensure(ctx, ctx->altbuf, sizeof(double) * (size_t)p * m * 2))) return rc;
   double* dL = ptr<double>(ctx->altbuf);
   double* dP = dL + (size_t)p * m;
-  BLMM_HIP(hipMemcpyAsync(dL, L, sizeof(double) * (size_t)p * m, hipMemcpyHostToDevice, ctx->stream));
-  if ((rc = launch_lod2log10p(ctx, dL, p, m, p, (int)chisq_df, dP, p))) return rc;
-  if ((rc = copy_to_host(ctx, P_out, dP, sizeof(double) * (size_t)p * m))) return rc;
-  return BLMM_OK;
+  if ((rc = hc.up(dL, L, sizeof(double) * (size_t)p * m)) || (rc = launch_lod2log10p(ctx, dL, p, m, p, (int)chisq_df, dP, p)) ||
+      (rc = copy_to_host(ctx, P_out, dP, sizeof(double) * (size_t)p * m))) return rc;
+  return hc.finish(false);
 }
 
 int blmm_lod_threshold(blmm_ctx* ctx, const double* L, int64_t p, int64_t m, double thr, int64_t cap, int32_t* i_out,
                        int32_t* j_out, double* lod_out, int64_t* count_out) {
   if (!ctx) return BLMM_ERR_INVALID;
   if (!L || p < 1 || m < 1) return fail(ctx, BLMM_ERR_INVALID, "lod_threshold: bad arguments");
-  BLMM_HIP(hipSetDevice(ctx->device));
+  HostCall hc(ctx);
   int rc;
-  if ((rc = ensure(ctx, ctx->outL, sizeof(double) * (size_t)p * m))) return rc;
-  BLMM_HIP(hipMemcpyAsync(ctx->outL.p, L, sizeof(double) * (size_t)p * m, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = hc.begin()) || (rc = hc.up(ctx->outL, L, sizeof(double) * (size_t)p * m))) return rc;
   ctx->last_L = ptr<double>(ctx->outL); ctx->last_p = p; ctx->last_m = m; ctx->last_f32 = false;
-  return blmm_last_lod_threshold(ctx, thr, cap, i_out, j_out, lod_out, count_out);
+  if ((rc = blmm_last_lod_threshold(ctx, thr, cap, i_out, j_out, lod_out, count_out))) return rc;
+  return hc.finish(false);
 }
 
 int blmm_get_thresholds(blmm_ctx* ctx, const double* Lperms, int64_t p, int64_t nperms, const double* probs, int64_t nprobs,
                         double* thrs_out) {
   if (!ctx) return BLMM_ERR_INVALID;
   if (!Lperms || p < 1 || nperms < 1) return fail(ctx, BLMM_ERR_INVALID, "get_thresholds: bad arguments");
-  BLMM_HIP(hipSetDevice(ctx->device));
+  HostCall hc(ctx);
   int rc;
-  if ((rc = ensure(ctx, ctx->altbuf, sizeof(double) * (size_t)p * nperms))) return rc;
-  BLMM_HIP(hipMemcpyAsync(ctx->altbuf.p, Lperms, sizeof(double) * (size_t)p * nperms, hipMemcpyHostToDevice, ctx->stream));
-  return blmm_get_thresholds_dev(ctx, ptr<double>(ctx->altbuf), p, nperms, p, probs, nprobs, thrs_out);
+  if ((rc = hc.begin()) || (rc = hc.up(ctx->altbuf, Lperms, sizeof(double) * (size_t)p * nperms)) ||
+      (rc = blmm_get_thresholds_dev(ctx, ptr<double>(ctx->altbuf), p, nperms, p, probs, nprobs, thrs_out))) return rc;
+  return hc.finish(false);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1289,6 +1274,55 @@ int blmm_bulkscan_dev(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, in
 }
 
 // ---------------------------------------------------------------------------------------------------
+// The argument checks of both reduced implementations; `who` prefixes the messages.
+static int reduced_check(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG, int64_t p,
+                         const double* dK, const blmm_reduced* out, const double* dh2_out, const char* who) {
+  int rc = check_opts(ctx, opts);
+  if (rc) return rc;
+  if (!out || !dY || !dG || !dK || (!dh2_out && opts->method != BLMM_ALT_GRID)) return fail(ctx, BLMM_ERR_INVALID, std::string(who) + ": NULL buffer");
+  if (out->cap < 0 || (out->cap > 0 && (!out->ti || !out->tj || !out->tlod)) || (out->want_triplets && !out->count))
+    return fail(ctx, BLMM_ERR_INVALID, std::string(who) + ": triplet buffers");
+  if (opts->method != BLMM_NULL_EXACT && opts->method != BLMM_NULL_GRID && opts->method != BLMM_ALT_GRID)
+    return fail(ctx, BLMM_ERR_METHOD, "Unknown method; choose null-exact, null-grid or alt-grid.");
+  if (n < 1 || m < 0 || p < 0 || p > 0x7fffffffLL || m > 0x7fffffffLL) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
+  return BLMM_OK;
+}
+
+// The fused route's reduction state over ctx->redbuf: per-(trait, 64-marker slot) partials, the triplet outputs of `out`
+static int reduced_args(blmm_ctx* ctx, const blmm_reduced* out, int64_t p, int64_t m, RedArgs* r, int* nslot) {
+  *nslot = 2 * (int)((p + 127) / 128);
+  const int64_t ldm = round_up(m, 64);
+  int rc = ensure(ctx, ctx->redbuf, (sizeof(double) + sizeof(int)) * (size_t)*nslot * (size_t)ldm);
+  if (rc) return rc;
+  r->pmax = ptr<double>(ctx->redbuf); r->parg = reinterpret_cast<int*>(r->pmax + (size_t)*nslot * ldm); r->ldm = ldm;
+  r->want_trip = out->want_triplets ? 1 : 0; r->thr = out->thr; r->cap = out->cap;
+  r->ti = out->ti; r->tj = out->tj; r->tl = out->tlod; r->cnt = reinterpret_cast<unsigned long long*>(out->count);
+  if (out->count) BLMM_HIP(hipMemsetAsync(out->count, 0, sizeof(int64_t), ctx->stream));
+  return BLMM_OK;
+}
+
+// The route through a resident L: the whole bulkscan into the context's outL (alt-grid: h2_panel, p x m, into the workspace -- it is
+// not part of the reduced result), then k_colmax / k_threshold over it; the blmm_last_* consumers serve that matrix afterwards.
+static int reduced_resident(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG, int64_t p,
+                            const double* dCovar, int64_t ncov, const double* dK, const double* dweights, const double* h2_grid_host,
+                            int64_t ngrid, const blmm_reduced* out, double* dh2_out, blmm_status* status) {
+  const int64_t ldL = p > 0 ? p : 1;
+  const size_t pm = (size_t)ldL * (size_t)(m > 0 ? m : 1);
+  int rc;
+  if ((rc = ensure(ctx, ctx->outL, sizeof(double) * pm))) return rc;
+  double* dL = ptr<double>(ctx->outL);
+  double* dH = dh2_out;
+  if (opts->method == BLMM_ALT_GRID) {
+    if ((rc = ensure(ctx, ctx->altbuf, sizeof(double) * pm))) return rc;
+    dH = ptr<double>(ctx->altbuf);
+  }
+  if ((rc = bulkscan_dev_impl(ctx, opts, dY, n, m, dG, p, dCovar, ncov, dK, dweights, h2_grid_host, ngrid, dL, ldL, dH, status, PvReq()))) return rc;
+  if (m > 0) { ctx->last_L = dL; ctx->last_p = p; ctx->last_m = m; ctx->last_f32 = false; }
+  if (out->colmax && m > 0 && (rc = launch_colmax(ctx, dL, p, m, ldL, out->colmax, out->argmax))) return rc;
+  if (out->want_triplets && (rc = launch_threshold(ctx, dL, p, m, ldL, out->thr, out->cap, out->ti, out->tj, out->tlod, out->count))) return rc;
+  return BLMM_OK;
+}
+
 // bulkscan without the LOD matrix (include/bulklmm_hip.h: blmm_bulkscan_reduced).  `out` holds DEVICE pointers here.
 // Native route (null-grid; null-exact in the low-rank weights form): the scan kernels' reduce-in-epilogue instantiations write
 // per-(trait, 64-marker slot) partial maxima and the triplets, k_red_final finishes the maxima -- L is never written.  The rare
@@ -1300,26 +1334,15 @@ int blmm_bulkscan_dev(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, in
 static int reduced_impl(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG, int64_t p,
                         const double* dCovar, int64_t ncov, const double* dK, const double* dweights, const double* h2_grid_host,
                         int64_t ngrid, const blmm_reduced* out, double* dh2_out, blmm_status* status, int* route_out) {
-  int rc = check_opts(ctx, opts);
+  int rc = reduced_check(ctx, opts, dY, n, m, dG, p, dK, out, dh2_out, "bulkscan_reduced");
   if (rc) return rc;
-  if (!out || !dY || !dG || !dK || (!dh2_out && opts->method != BLMM_ALT_GRID)) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_reduced: NULL buffer");
-  if (out->cap < 0 || (out->cap > 0 && (!out->ti || !out->tj || !out->tlod)) || (out->want_triplets && !out->count))
-    return fail(ctx, BLMM_ERR_INVALID, "bulkscan_reduced: triplet buffers");
-  if (opts->method != BLMM_NULL_EXACT && opts->method != BLMM_NULL_GRID && opts->method != BLMM_ALT_GRID)
-    return fail(ctx, BLMM_ERR_METHOD, "Unknown method; choose null-exact, null-grid or alt-grid.");
-  if (n < 1 || m < 0 || p < 0 || p > 0x7fffffffLL || m > 0x7fffffffLL) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
   BLMM_HIP(hipSetDevice(ctx->device));
   const bool native = p > 0 && m > 0 && (opts->method == BLMM_NULL_GRID || wants_lowrank(ctx, opts, n, dCovar, ncov));
   if (route_out) *route_out = 0;
   if (native) {
-    const int nslot = 2 * (int)((p + 127) / 128);
-    const int64_t ldm = round_up(m, 64);
-    if ((rc = ensure(ctx, ctx->redbuf, (sizeof(double) + sizeof(int)) * (size_t)nslot * (size_t)ldm))) return rc;
     RedArgs r;
-    r.pmax = ptr<double>(ctx->redbuf); r.parg = reinterpret_cast<int*>(r.pmax + (size_t)nslot * ldm); r.ldm = ldm;
-    r.want_trip = out->want_triplets ? 1 : 0; r.thr = out->thr; r.cap = out->cap;
-    r.ti = out->ti; r.tj = out->tj; r.tl = out->tlod; r.cnt = reinterpret_cast<unsigned long long*>(out->count);
-    if (out->count) BLMM_HIP(hipMemsetAsync(out->count, 0, sizeof(int64_t), ctx->stream));
+    int nslot;
+    if ((rc = reduced_args(ctx, out, p, m, &r, &nslot))) return rc;
     ctx->red_cur = r;
     rc = bulkscan_dev_impl(ctx, opts, dY, n, m, dG, p, dCovar, ncov, dK, dweights, h2_grid_host, ngrid, nullptr, p, dh2_out, status, PvReq());
     ctx->red_cur = RedArgs();
@@ -1331,21 +1354,10 @@ static int reduced_impl(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, 
     if ((rc = check_sticky(ctx))) return rc;
     if (h[10] == 0 && h[ST_ILLCOND] == 0) { if (route_out) *route_out = 1; return BLMM_OK; }
   }
-  // through a resident L
-  if ((rc = ensure(ctx, ctx->outL, sizeof(double) * (size_t)(p > 0 ? p : 1) * (size_t)(m > 0 ? m : 1)))) return rc;
-  double* dL = ptr<double>(ctx->outL);
-  double* dH = dh2_out;
-  if (opts->method == BLMM_ALT_GRID) {      // h2_panel (p x m) is not part of the reduced result: into the workspace
-    if ((rc = ensure(ctx, ctx->altbuf, sizeof(double) * (size_t)(p > 0 ? p : 1) * (size_t)(m > 0 ? m : 1)))) return rc;
-    dH = ptr<double>(ctx->altbuf);
-  }
-  if ((rc = bulkscan_dev_impl(ctx, opts, dY, n, m, dG, p, dCovar, ncov, dK, dweights, h2_grid_host, ngrid, dL, p > 0 ? p : 1, dH, status, PvReq()))) {
+  if ((rc = reduced_resident(ctx, opts, dY, n, m, dG, p, dCovar, ncov, dK, dweights, h2_grid_host, ngrid, out, dh2_out, status))) {
     (void)hipStreamSynchronize(ctx->stream);
     return rc;
   }
-  if (m > 0) { ctx->last_L = dL; ctx->last_p = p; ctx->last_m = m; ctx->last_f32 = false; }
-  if (out->colmax && m > 0 && (rc = launch_colmax(ctx, dL, p, m, p > 0 ? p : 1, out->colmax, out->argmax))) return rc;
-  if (out->want_triplets && (rc = launch_threshold(ctx, dL, p, m, p > 0 ? p : 1, out->thr, out->cap, out->ti, out->tj, out->tlod, out->count))) return rc;
   BLMM_HIP(hipStreamSynchronize(ctx->stream));
   if (route_out) *route_out = 2;
   return check_sticky(ctx);
@@ -1461,32 +1473,6 @@ int blmm_bulkscan_prerotated_dev(blmm_ctx* ctx, const blmm_opts* opts, const dou
   return scan_pipeline(ctx, opts, P, tm, lowrank, lowrank && m > 0 && p > 0, dgrid, h2_grid_host, ngrid, dL_out, ldL, dh2_out, status, pvreq);
 }
 
-// host inputs of a bulkscan call -> the context's input buffers (asynchronous on the context's stream)
-static int upload_bulk_inputs(blmm_ctx* ctx, const double* Y, int64_t n, int64_t m, const double* G, int64_t p, const double* Covar,
-                              int64_t ncov, const double* K, const double* weights, const double** dCov, const double** dW) {
-  int rc;
-  if ((rc = ensure(ctx, ctx->inY, sizeof(double) * n * (m > 0 ? m : 1)))) return rc;
-  if ((rc = ensure(ctx, ctx->inG, sizeof(double) * n * (p > 0 ? p : 1)))) return rc;
-  if ((rc = ensure(ctx, ctx->inK, sizeof(double) * n * n))) return rc;
-  BLMM_HIP(hipMemcpyAsync(ctx->inK.p, K, sizeof(double) * n * n, hipMemcpyHostToDevice, ctx->stream));
-  // Y and G: left for prepare(), which copies them on ctx->copy once the eigen phase is queued (see blmm_ctx::up_pending)
-  ctx->up_src[0] = Y; ctx->up_dst[0] = ctx->inY.p; ctx->up_bytes[0] = sizeof(double) * (size_t)n * (size_t)m;
-  ctx->up_src[1] = G; ctx->up_dst[1] = ctx->inG.p; ctx->up_bytes[1] = sizeof(double) * (size_t)n * (size_t)p;
-  ctx->up_pending = true; ctx->in_wait = false;
-  *dCov = nullptr; *dW = nullptr;
-  if (Covar && ncov > 0) {
-    if ((rc = ensure(ctx, ctx->inCov, sizeof(double) * n * ncov))) return rc;
-    BLMM_HIP(hipMemcpyAsync(ctx->inCov.p, Covar, sizeof(double) * n * ncov, hipMemcpyHostToDevice, ctx->stream));
-    *dCov = ptr<double>(ctx->inCov);
-  }
-  if (weights) {
-    if ((rc = ensure(ctx, ctx->inW, sizeof(double) * n))) return rc;
-    BLMM_HIP(hipMemcpyAsync(ctx->inW.p, weights, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
-    *dW = ptr<double>(ctx->inW);
-  }
-  return BLMM_OK;
-}
-
 // L_out == NULL: the matrix stays in HBM (2.08 GB at BXD size: 36 of the call's 39 ms are its trip over PCIe) and the blmm_last_*
 // consumers serve it -- peaks, LOD > t triplets, permutation quantiles, -log10 p, single columns (README.md:246-255, 354-359;
 // src/analysis_helpers/single_trait_analysis.jl:13-23 are what the reference's users do with L).  alt-grid: h2_out (the p x m
@@ -1500,24 +1486,23 @@ int blmm_bulkscan(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, int64_t
   const bool alt = opts->method == BLMM_ALT_GRID;
   if (!Y || !G || !K || (!h2_out && !alt)) return fail(ctx, BLMM_ERR_INVALID, "bulkscan: NULL buffer");
   if (n < 1 || m < 0 || p < 0) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
-  BLMM_HIP(hipSetDevice(ctx->device));
+  HostCall hc(ctx);
   int rc;
   const size_t h2_elems = alt ? (size_t)p * m : (size_t)m;
-  if ((rc = ensure(ctx, ctx->outL, sizeof(double) * (size_t)p * m))) return rc;
-  if ((rc = ensure(ctx, ctx->outH2, sizeof(double) * h2_elems))) return rc;
+  if ((rc = hc.begin()) || (rc = ensure(ctx, ctx->outL, sizeof(double) * (size_t)p * m)) || (rc = ensure(ctx, ctx->outH2, sizeof(double) * h2_elems)))
+    return rc;
   // BLMM_HOST_PROF=1: wall-clock of the call's legs on stderr (diagnostic: it synchronises between them)
   static const bool hprof = getenv("BLMM_HOST_PROF") && getenv("BLMM_HOST_PROF")[0] == '1';
   auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double hp0 = hprof ? now() : 0.0;
-  const double* dCov = nullptr; const double* dW = nullptr;
-  if ((rc = upload_bulk_inputs(ctx, Y, n, m, G, p, Covar, ncov, K, weights, &dCov, &dW))) return rc;
+  const double *dCov, *dW;
+  if ((rc = hc.up(ctx->inK, K, sizeof(double) * n * n)) || (rc = hc.defer_yg(Y, sizeof(double) * n * m, G, sizeof(double) * n * p)) ||
+      (rc = hc.up_opt(ctx->inCov, Covar, n * ncov, &dCov)) || (rc = hc.up_opt(ctx->inW, weights, n, &dW))) return rc;
   if (hprof) (void)hipStreamSynchronize(ctx->stream);
   const double hp1 = hprof ? now() : 0.0;
   pv_hand_over(ctx, pvreq);
-  rc = blmm_bulkscan_dev(ctx, opts, ptr<double>(ctx->inY), n, m, ptr<double>(ctx->inG), p, dCov, dCov ? ncov : 0,
-                         ptr<double>(ctx->inK), dW, h2_grid, ngrid, ptr<double>(ctx->outL), p, ptr<double>(ctx->outH2), status);
-  ctx->up_pending = false; ctx->in_wait = false;        // (a call refused before prepare() never uploaded them)
-  if (rc) { hipStreamSynchronize(ctx->stream); return rc; }
+  if ((rc = blmm_bulkscan_dev(ctx, opts, ptr<double>(ctx->inY), n, m, ptr<double>(ctx->inG), p, dCov, dCov ? ncov : 0,
+                              ptr<double>(ctx->inK), dW, h2_grid, ngrid, ptr<double>(ctx->outL), p, ptr<double>(ctx->outH2), status))) return rc;
   const double hp2 = hprof ? now() : 0.0;
   if (hprof) (void)hipStreamSynchronize(ctx->stream);
   const double hp3 = hprof ? now() : 0.0;
@@ -1525,7 +1510,7 @@ int blmm_bulkscan(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, int64_t
   if (L_out && (size_t)p * m > 0 && (rc = copy_to_host(ctx, L_out, ctx->outL.p, sizeof(double) * (size_t)p * m))) return rc;
   const double hp4 = hprof ? now() : 0.0;
   if (h2_out && h2_elems > 0 && (rc = copy_to_host(ctx, h2_out, ctx->outH2.p, sizeof(double) * h2_elems))) return rc;
-  BLMM_HIP(hipStreamSynchronize(ctx->stream));
+  if ((rc = hc.finish())) return rc;
   if (hprof)
     fprintf(stderr, "blmm_bulkscan legs (ms): uploads %.2f | enqueue %.2f | device %.2f | L to host %.2f | h2 to host + sync %.2f\n", hp1 - hp0, hp2 - hp1,
             hp3 - hp2, hp4 - hp3, now() - hp4);
@@ -1544,44 +1529,36 @@ int blmm_bulkscan_reduced(blmm_ctx* ctx, const blmm_opts* opts, const double* Y,
   if (out->cap < 0 || (out->cap > 0 && (!out->ti || !out->tj || !out->tlod)) || (out->want_triplets && !out->count))
     return fail(ctx, BLMM_ERR_INVALID, "bulkscan_reduced: triplet buffers");
   if (n < 1 || m < 0 || p < 0) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
-  BLMM_HIP(hipSetDevice(ctx->device));
+  HostCall hc(ctx);
   int rc;
-  const int64_t cap = out->cap > 0 ? out->cap : 0, mm = m > 0 ? m : 1;
+  const size_t cap = out->cap > 0 ? out->cap : 1, mm = m > 0 ? m : 1;
   // device side of `out`: maxima / arg-maxima (tmpA / tmpB), triplets + count (redtrip), h2 (outH2)
-  if ((rc = ensure(ctx, ctx->tmpA, sizeof(double) * (size_t)mm))) return rc;
-  if ((rc = ensure(ctx, ctx->tmpB, sizeof(int64_t) * (size_t)mm))) return rc;
-  if ((rc = ensure(ctx, ctx->redtrip, (sizeof(double) + 2 * sizeof(int32_t)) * (size_t)(cap > 0 ? cap : 1) + 64))) return rc;
-  if ((rc = ensure(ctx, ctx->outH2, sizeof(double) * (size_t)mm))) return rc;
+  if ((rc = hc.begin()) || (rc = ensure(ctx, ctx->tmpA, sizeof(double) * mm)) || (rc = ensure(ctx, ctx->tmpB, sizeof(int64_t) * mm)) ||
+      (rc = ensure(ctx, ctx->redtrip, (sizeof(double) + 2 * sizeof(int32_t)) * cap + 64)) || (rc = ensure(ctx, ctx->outH2, sizeof(double) * mm)))
+    return rc;
   blmm_reduced d = *out;
   d.colmax = (out->colmax || out->argmax) ? ptr<double>(ctx->tmpA) : nullptr;
   d.argmax = out->argmax ? ptr<int64_t>(ctx->tmpB) : nullptr;
   d.count = ptr<int64_t>(ctx->redtrip);
   d.tlod = reinterpret_cast<double*>(d.count + 8);
-  d.ti = reinterpret_cast<int32_t*>(d.tlod + (cap > 0 ? cap : 1));
-  d.tj = d.ti + (cap > 0 ? cap : 1);
-  const double* dCov = nullptr; const double* dW = nullptr;
-  if ((rc = upload_bulk_inputs(ctx, Y, n, m, G, p, Covar, ncov, K, weights, &dCov, &dW))) return rc;
-  rc = reduced_impl(ctx, opts, ptr<double>(ctx->inY), n, m, ptr<double>(ctx->inG), p, dCov, dCov ? ncov : 0, ptr<double>(ctx->inK), dW,
-                    h2_grid, ngrid, &d, ptr<double>(ctx->outH2), status, &ctx->last_reduced_route);
-  ctx->up_pending = false; ctx->in_wait = false;
-  if (rc) return rc;
-  if (m > 0) {
-    if (out->colmax) BLMM_HIP(hipMemcpyAsync(out->colmax, d.colmax, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-    if (out->argmax) BLMM_HIP(hipMemcpyAsync(out->argmax, d.argmax, sizeof(int64_t) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-    if (h2_out && !alt) BLMM_HIP(hipMemcpyAsync(h2_out, ctx->outH2.p, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-  }
+  d.ti = reinterpret_cast<int32_t*>(d.tlod + cap);
+  d.tj = d.ti + cap;
+  const double *dCov, *dW;
+  if ((rc = hc.up(ctx->inK, K, sizeof(double) * n * n)) || (rc = hc.defer_yg(Y, sizeof(double) * n * m, G, sizeof(double) * n * p)) ||
+      (rc = hc.up_opt(ctx->inCov, Covar, n * ncov, &dCov)) || (rc = hc.up_opt(ctx->inW, weights, n, &dW)) ||
+      (rc = reduced_impl(ctx, opts, ptr<double>(ctx->inY), n, m, ptr<double>(ctx->inG), p, dCov, dCov ? ncov : 0, ptr<double>(ctx->inK), dW,
+                         h2_grid, ngrid, &d, ptr<double>(ctx->outH2), status, &ctx->last_reduced_route))) return rc;
+  if (m > 0 && ((rc = hc.down(out->colmax, d.colmax, sizeof(double) * m)) || (rc = hc.down(out->argmax, d.argmax, sizeof(int64_t) * m)) ||
+                (rc = hc.down(alt ? nullptr : h2_out, ctx->outH2.p, sizeof(double) * m)))) return rc;
   if (out->want_triplets) {
-    BLMM_HIP(hipMemcpyAsync(out->count, d.count, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    // the count first: only what it says is copied back
+    if ((rc = hc.down(out->count, d.count, sizeof(int64_t)))) return rc;
     BLMM_HIP(hipStreamSynchronize(ctx->stream));
-    const int64_t got = *out->count < cap ? *out->count : cap;
-    if (got > 0) {
-      BLMM_HIP(hipMemcpyAsync(out->tlod, d.tlod, sizeof(double) * (size_t)got, hipMemcpyDeviceToHost, ctx->stream));
-      BLMM_HIP(hipMemcpyAsync(out->ti, d.ti, sizeof(int32_t) * (size_t)got, hipMemcpyDeviceToHost, ctx->stream));
-      BLMM_HIP(hipMemcpyAsync(out->tj, d.tj, sizeof(int32_t) * (size_t)got, hipMemcpyDeviceToHost, ctx->stream));
-    }
+    const size_t got = *out->count < out->cap ? *out->count : out->cap;
+    if ((rc = hc.down(out->tlod, d.tlod, sizeof(double) * got)) || (rc = hc.down(out->ti, d.ti, sizeof(int32_t) * got)) ||
+        (rc = hc.down(out->tj, d.tj, sizeof(int32_t) * got))) return rc;
   }
-  BLMM_HIP(hipStreamSynchronize(ctx->stream));
-  return check_sticky(ctx);
+  return (rc = hc.finish()) ? rc : check_sticky(ctx);
 }
 
 int blmm_last_reduced_route(const blmm_ctx* ctx) { return ctx ? ctx->last_reduced_route : 0; }
@@ -1595,14 +1572,8 @@ int blmm_last_reduced_route(const blmm_ctx* ctx) { return ctx ? ctx->last_reduce
 static int reduced_async_impl(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG, int64_t p,
                               const double* dCovar, int64_t ncov, const double* dK, const double* dweights, const double* h2_grid_host,
                               int64_t ngrid, const blmm_reduced* out, double* dh2_out, int64_t* dinfo) {
-  int rc = check_opts(ctx, opts);
+  int rc = reduced_check(ctx, opts, dY, n, m, dG, p, dK, out, dh2_out, "bulkscan_reduced_async");
   if (rc) return rc;
-  if (!out || !dY || !dG || !dK || (!dh2_out && opts->method != BLMM_ALT_GRID)) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_reduced_async: NULL buffer");
-  if (out->cap < 0 || (out->cap > 0 && (!out->ti || !out->tj || !out->tlod)) || (out->want_triplets && !out->count))
-    return fail(ctx, BLMM_ERR_INVALID, "bulkscan_reduced_async: triplet buffers");
-  if (opts->method != BLMM_NULL_EXACT && opts->method != BLMM_NULL_GRID && opts->method != BLMM_ALT_GRID)
-    return fail(ctx, BLMM_ERR_METHOD, "Unknown method; choose null-exact, null-grid or alt-grid.");
-  if (n < 1 || m < 0 || p < 0 || p > 0x7fffffffLL || m > 0x7fffffffLL) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
   if (opts->method != BLMM_NULL_EXACT) {       // (grid_to_device checks it again; here: before anything is enqueued)
     if (!h2_grid_host || ngrid < 1) return fail(ctx, BLMM_ERR_INVALID, "h2 grid is empty");
     for (int64_t g = 0; g < ngrid; ++g)
@@ -1616,16 +1587,11 @@ static int reduced_async_impl(blmm_ctx* ctx, const blmm_opts* opts, const double
   BLMM_HIP(hipStreamWaitEvent(ctx->side2, ctx->ev_call, 0));
   const bool fused = p > 0 && m > 0 && (opts->method == BLMM_NULL_GRID || wants_lowrank(ctx, opts, n, dCovar, ncov));
   if (fused) {
-    const int nslot = 2 * (int)((p + 127) / 128);
-    const int64_t ldm = round_up(m, 64);
-    if ((rc = ensure(ctx, ctx->redbuf, (sizeof(double) + sizeof(int)) * (size_t)nslot * (size_t)ldm))) return rc;
-    if ((rc = ensure(ctx, ctx->redflag, sizeof(int) * (size_t)m))) return rc;
     RedArgs r;
-    r.pmax = ptr<double>(ctx->redbuf); r.parg = reinterpret_cast<int*>(r.pmax + (size_t)nslot * ldm); r.ldm = ldm;
-    r.want_trip = out->want_triplets ? 1 : 0; r.thr = out->thr; r.cap = out->cap;
-    r.ti = out->ti; r.tj = out->tj; r.tl = out->tlod; r.cnt = reinterpret_cast<unsigned long long*>(out->count);
+    int nslot;
+    if ((rc = reduced_args(ctx, out, p, m, &r, &nslot))) return rc;
+    if ((rc = ensure(ctx, ctx->redflag, sizeof(int) * (size_t)m))) return rc;
     r.flags = ptr<int>(ctx->redflag);
-    if (out->count) BLMM_HIP(hipMemsetAsync(out->count, 0, sizeof(int64_t), ctx->stream));
     BLMM_HIP(hipMemsetAsync(r.flags, 0, sizeof(int) * (size_t)m, ctx->stream));
     ctx->red_cur = r;
     ctx->grid_async = true;
@@ -1637,21 +1603,10 @@ static int reduced_async_impl(blmm_ctx* ctx, const blmm_opts* opts, const double
     ctx->last_L = nullptr;                    // no matrix of this call: an earlier one is not served as its result
     return dinfo ? launch_red_info(ctx, ptr<int64_t>(ctx->stat), 0, out->want_triplets ? out->count : nullptr, dinfo) : BLMM_OK;
   }
-  // through a resident L
-  if ((rc = ensure(ctx, ctx->outL, sizeof(double) * (size_t)(p > 0 ? p : 1) * (size_t)(m > 0 ? m : 1)))) return rc;
-  double* dL = ptr<double>(ctx->outL);
-  double* dH = dh2_out;
-  if (opts->method == BLMM_ALT_GRID) {
-    if ((rc = ensure(ctx, ctx->altbuf, sizeof(double) * (size_t)(p > 0 ? p : 1) * (size_t)(m > 0 ? m : 1)))) return rc;
-    dH = ptr<double>(ctx->altbuf);
-  }
   ctx->grid_async = true;
-  rc = bulkscan_dev_impl(ctx, opts, dY, n, m, dG, p, dCovar, ncov, dK, dweights, h2_grid_host, ngrid, dL, p > 0 ? p : 1, dH, nullptr, PvReq());
+  rc = reduced_resident(ctx, opts, dY, n, m, dG, p, dCovar, ncov, dK, dweights, h2_grid_host, ngrid, out, dh2_out, nullptr);
   ctx->grid_async = false;
   if (rc) return rc;
-  if (m > 0) { ctx->last_L = dL; ctx->last_p = p; ctx->last_m = m; ctx->last_f32 = false; }
-  if (out->colmax && m > 0 && (rc = launch_colmax(ctx, dL, p, m, p > 0 ? p : 1, out->colmax, out->argmax))) return rc;
-  if (out->want_triplets && (rc = launch_threshold(ctx, dL, p, m, p > 0 ? p : 1, out->thr, out->cap, out->ti, out->tj, out->tlod, out->count))) return rc;
   if (!dinfo) return BLMM_OK;
   if (!ctx->stat.p && (rc = ensure(ctx, ctx->stat, sizeof(int64_t) * NSTAT))) return rc;
   return launch_red_info(ctx, ptr<int64_t>(ctx->stat), 2, out->want_triplets ? out->count : nullptr, dinfo);
@@ -1841,45 +1796,29 @@ static int scan_perms_host(blmm_ctx* ctx, const blmm_opts* opts, const double* y
   if (nperms < 0) return fail(ctx, BLMM_ERR_NPERMS, "The required number of permutations must be a positive integer.");
   if (!y || !G || !K || !scalars_out || !lod_out || (nperms > 0 && !Lperms_out)) return fail(ctx, BLMM_ERR_INVALID, "scan_perms: NULL buffer");
   if (n < 1 || p < 0) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
-  BLMM_HIP(hipSetDevice(ctx->device));
+  HostCall hc(ctx);
   const size_t esz = f32 ? sizeof(float) : sizeof(double);
   int rc;
-  if ((rc = ensure(ctx, ctx->inY, sizeof(double) * n))) return rc;
-  if ((rc = ensure(ctx, ctx->inG, sizeof(double) * n * (p > 0 ? p : 1)))) return rc;
-  if ((rc = ensure(ctx, ctx->inK, sizeof(double) * n * n))) return rc;
-  if ((rc = ensure(ctx, ctx->outL, sizeof(double) * (size_t)p + esz * (size_t)p * nperms))) return rc;
-  if ((rc = ensure(ctx, ctx->outH2, sizeof(double) * 2))) return rc;
-  BLMM_HIP(hipMemcpyAsync(ctx->inY.p, y, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
-  BLMM_HIP(hipMemcpyAsync(ctx->inG.p, G, sizeof(double) * n * p, hipMemcpyHostToDevice, ctx->stream));
-  BLMM_HIP(hipMemcpyAsync(ctx->inK.p, K, sizeof(double) * n * n, hipMemcpyHostToDevice, ctx->stream));
-  const double* dCov = nullptr; const double* dW = nullptr; const int32_t* dperm = nullptr;
-  if (Covar && ncov > 0) {
-    if ((rc = ensure(ctx, ctx->inCov, sizeof(double) * n * ncov))) return rc;
-    BLMM_HIP(hipMemcpyAsync(ctx->inCov.p, Covar, sizeof(double) * n * ncov, hipMemcpyHostToDevice, ctx->stream));
-    dCov = ptr<double>(ctx->inCov);
-  }
-  if (weights) {
-    if ((rc = ensure(ctx, ctx->inW, sizeof(double) * n))) return rc;
-    BLMM_HIP(hipMemcpyAsync(ctx->inW.p, weights, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
-    dW = ptr<double>(ctx->inW);
-  }
+  if ((rc = hc.begin()) || (rc = ensure(ctx, ctx->outL, sizeof(double) * (size_t)p + esz * (size_t)p * nperms)) ||
+      (rc = ensure(ctx, ctx->outH2, sizeof(double) * 2))) return rc;
+  const double *dCov, *dW;
+  if ((rc = hc.up(ctx->inY, y, sizeof(double) * n)) || (rc = hc.up(ctx->inG, G, sizeof(double) * n * p)) ||
+      (rc = hc.up(ctx->inK, K, sizeof(double) * n * n)) || (rc = hc.up_opt(ctx->inCov, Covar, n * ncov, &dCov)) ||
+      (rc = hc.up_opt(ctx->inW, weights, n, &dW))) return rc;
+  const int32_t* dperm = nullptr;
   if (perm_idx && nperms > 0) {
-    if ((rc = ensure(ctx, ctx->tmpC, sizeof(int32_t) * (size_t)n * nperms))) return rc;
-    BLMM_HIP(hipMemcpyAsync(ctx->tmpC.p, perm_idx, sizeof(int32_t) * (size_t)n * nperms, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = hc.up(ctx->tmpC, perm_idx, sizeof(int32_t) * (size_t)n * nperms))) return rc;
     dperm = ptr<int32_t>(ctx->tmpC);
   }
   double* dL = ptr<double>(ctx->outL);
   void* dLp = dL + p;                       // 8-byte aligned; the fp32 kernel needs 4
-  rc = scan_perms_impl(ctx, opts, ptr<double>(ctx->inY), n, ptr<double>(ctx->inG), p, dCov, dCov ? ncov : 0,
-                       ptr<double>(ctx->inK), dW, nperms, seed, dperm, ptr<double>(ctx->outH2), dL,
-                       f32 ? nullptr : reinterpret_cast<double*>(dLp), f32 ? reinterpret_cast<float*>(dLp) : nullptr, status);
-  if (rc) { hipStreamSynchronize(ctx->stream); return rc; }
+  if ((rc = scan_perms_impl(ctx, opts, ptr<double>(ctx->inY), n, ptr<double>(ctx->inG), p, dCov, dCov ? ncov : 0, ptr<double>(ctx->inK), dW,
+                            nperms, seed, dperm, ptr<double>(ctx->outH2), dL,
+                            f32 ? nullptr : reinterpret_cast<double*>(dLp), f32 ? reinterpret_cast<float*>(dLp) : nullptr, status))) return rc;
   ctx->last_L = reinterpret_cast<const double*>(dLp); ctx->last_p = p; ctx->last_m = nperms; ctx->last_f32 = f32;
-  BLMM_HIP(hipMemcpyAsync(scalars_out, ctx->outH2.p, sizeof(double) * 2, hipMemcpyDeviceToHost, ctx->stream));
-  if (p > 0) BLMM_HIP(hipMemcpyAsync(lod_out, dL, sizeof(double) * p, hipMemcpyDeviceToHost, ctx->stream));
+  if ((rc = hc.down(scalars_out, ctx->outH2.p, sizeof(double) * 2)) || (rc = hc.down(lod_out, dL, sizeof(double) * p))) return rc;
   if (p > 0 && nperms > 0 && (rc = copy_to_host(ctx, Lperms_out, dLp, esz * (size_t)p * nperms))) return rc;
-  BLMM_HIP(hipStreamSynchronize(ctx->stream));
-  return check_sticky(ctx);
+  return (rc = hc.finish()) ? rc : check_sticky(ctx);
 }
 
 int blmm_scan_perms(blmm_ctx* ctx, const blmm_opts* opts, const double* y, int64_t n, const double* G, int64_t p,
@@ -1961,40 +1900,23 @@ int blmm_bulkscan_alt_exact(blmm_ctx* ctx, const blmm_opts* opts, const double* 
   if (!opts) return fail(ctx, BLMM_ERR_INVALID, "opts is NULL");
   if (!Y || !G || !K || !L_out || !h2_panel_out || !h2_null_out) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_alt_exact: NULL buffer");
   if (n < 1 || p < 1 || m < 1) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
-  BLMM_HIP(hipSetDevice(ctx->device));
+  HostCall hc(ctx);
   int rc;
-  if ((rc = ensure(ctx, ctx->inY, sizeof(double) * n * m))) return rc;
-  if ((rc = ensure(ctx, ctx->inG, sizeof(double) * n * p))) return rc;
-  if ((rc = ensure(ctx, ctx->inK, sizeof(double) * n * n))) return rc;
-  if ((rc = ensure(ctx, ctx->outL, sizeof(double) * 2 * (size_t)p * m))) return rc;
-  if ((rc = ensure(ctx, ctx->outH2, sizeof(double) * 2 * (size_t)m))) return rc;
-  BLMM_HIP(hipMemcpyAsync(ctx->inY.p, Y, sizeof(double) * n * m, hipMemcpyHostToDevice, ctx->stream));
-  BLMM_HIP(hipMemcpyAsync(ctx->inG.p, G, sizeof(double) * n * p, hipMemcpyHostToDevice, ctx->stream));
-  BLMM_HIP(hipMemcpyAsync(ctx->inK.p, K, sizeof(double) * n * n, hipMemcpyHostToDevice, ctx->stream));
-  const double* dCov = nullptr; const double* dW = nullptr;
-  if (Covar && ncov > 0) {
-    if ((rc = ensure(ctx, ctx->inCov, sizeof(double) * n * ncov))) return rc;
-    BLMM_HIP(hipMemcpyAsync(ctx->inCov.p, Covar, sizeof(double) * n * ncov, hipMemcpyHostToDevice, ctx->stream));
-    dCov = ptr<double>(ctx->inCov);
-  }
-  if (weights) {
-    if ((rc = ensure(ctx, ctx->inW, sizeof(double) * n))) return rc;
-    BLMM_HIP(hipMemcpyAsync(ctx->inW.p, weights, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
-    dW = ptr<double>(ctx->inW);
-  }
+  if ((rc = hc.begin()) || (rc = ensure(ctx, ctx->outL, sizeof(double) * 2 * (size_t)p * m)) || (rc = ensure(ctx, ctx->outH2, sizeof(double) * 2 * (size_t)m)))
+    return rc;
+  const double *dCov, *dW;
+  if ((rc = hc.up(ctx->inY, Y, sizeof(double) * n * m)) || (rc = hc.up(ctx->inG, G, sizeof(double) * n * p)) ||
+      (rc = hc.up(ctx->inK, K, sizeof(double) * n * n)) || (rc = hc.up_opt(ctx->inCov, Covar, n * ncov, &dCov)) ||
+      (rc = hc.up_opt(ctx->inW, weights, n, &dW))) return rc;
   double* dL = ptr<double>(ctx->outL);
   double* dH = dL + (size_t)p * m;
   double* dh2 = ptr<double>(ctx->outH2);
-  rc = blmm_bulkscan_alt_exact_dev(ctx, opts, ptr<double>(ctx->inY), n, m, ptr<double>(ctx->inG), p, dCov, dCov ? ncov : 0,
-                                   ptr<double>(ctx->inK), dW, dL, p, dH, p, dh2, dh2 + m, status);
-  if (rc) { hipStreamSynchronize(ctx->stream); return rc; }
+  if ((rc = blmm_bulkscan_alt_exact_dev(ctx, opts, ptr<double>(ctx->inY), n, m, ptr<double>(ctx->inG), p, dCov, dCov ? ncov : 0,
+                                        ptr<double>(ctx->inK), dW, dL, p, dH, p, dh2, dh2 + m, status))) return rc;
   ctx->last_L = dL; ctx->last_p = p; ctx->last_m = m; ctx->last_f32 = false;
-  if ((rc = copy_to_host(ctx, L_out, dL, sizeof(double) * (size_t)p * m))) return rc;
-  if ((rc = copy_to_host(ctx, h2_panel_out, dH, sizeof(double) * (size_t)p * m))) return rc;
-  BLMM_HIP(hipMemcpyAsync(h2_null_out, dh2, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-  if (sigma2_out) BLMM_HIP(hipMemcpyAsync(sigma2_out, dh2 + m, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-  BLMM_HIP(hipStreamSynchronize(ctx->stream));
-  return check_sticky(ctx);
+  if ((rc = copy_to_host(ctx, L_out, dL, sizeof(double) * (size_t)p * m)) || (rc = copy_to_host(ctx, h2_panel_out, dH, sizeof(double) * (size_t)p * m)) ||
+      (rc = hc.down(h2_null_out, dh2, sizeof(double) * (size_t)m)) || (rc = hc.down(sigma2_out, dh2 + m, sizeof(double) * (size_t)m))) return rc;
+  return (rc = hc.finish()) ? rc : check_sticky(ctx);
 }
 
 int blmm_scan_alt(blmm_ctx* ctx, const blmm_opts* opts, const double* y, int64_t n, const double* G, int64_t p,
@@ -2004,37 +1926,20 @@ int blmm_scan_alt(blmm_ctx* ctx, const blmm_opts* opts, const double* y, int64_t
   if (!opts) return fail(ctx, BLMM_ERR_INVALID, "opts is NULL");
   if (!y || !G || !K || !scalars_out || !lod_out || !h2_each_out) return fail(ctx, BLMM_ERR_INVALID, "scan_alt: NULL buffer");
   if (n < 1 || p < 1) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
-  BLMM_HIP(hipSetDevice(ctx->device));
+  HostCall hc(ctx);
   int rc;
-  if ((rc = ensure(ctx, ctx->inY, sizeof(double) * n))) return rc;
-  if ((rc = ensure(ctx, ctx->inG, sizeof(double) * n * p))) return rc;
-  if ((rc = ensure(ctx, ctx->inK, sizeof(double) * n * n))) return rc;
-  if ((rc = ensure(ctx, ctx->outL, sizeof(double) * 2 * (size_t)p))) return rc;
-  if ((rc = ensure(ctx, ctx->outH2, sizeof(double) * 2))) return rc;
-  BLMM_HIP(hipMemcpyAsync(ctx->inY.p, y, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
-  BLMM_HIP(hipMemcpyAsync(ctx->inG.p, G, sizeof(double) * n * p, hipMemcpyHostToDevice, ctx->stream));
-  BLMM_HIP(hipMemcpyAsync(ctx->inK.p, K, sizeof(double) * n * n, hipMemcpyHostToDevice, ctx->stream));
-  const double* dCov = nullptr; const double* dW = nullptr;
-  if (Covar && ncov > 0) {
-    if ((rc = ensure(ctx, ctx->inCov, sizeof(double) * n * ncov))) return rc;
-    BLMM_HIP(hipMemcpyAsync(ctx->inCov.p, Covar, sizeof(double) * n * ncov, hipMemcpyHostToDevice, ctx->stream));
-    dCov = ptr<double>(ctx->inCov);
-  }
-  if (weights) {
-    if ((rc = ensure(ctx, ctx->inW, sizeof(double) * n))) return rc;
-    BLMM_HIP(hipMemcpyAsync(ctx->inW.p, weights, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
-    dW = ptr<double>(ctx->inW);
-  }
+  if ((rc = hc.begin()) || (rc = ensure(ctx, ctx->outL, sizeof(double) * 2 * (size_t)p)) || (rc = ensure(ctx, ctx->outH2, sizeof(double) * 2))) return rc;
+  const double *dCov, *dW;
+  if ((rc = hc.up(ctx->inY, y, sizeof(double) * n)) || (rc = hc.up(ctx->inG, G, sizeof(double) * n * p)) ||
+      (rc = hc.up(ctx->inK, K, sizeof(double) * n * n)) || (rc = hc.up_opt(ctx->inCov, Covar, n * ncov, &dCov)) ||
+      (rc = hc.up_opt(ctx->inW, weights, n, &dW))) return rc;
   double* dL = ptr<double>(ctx->outL);
-  rc = blmm_scan_alt_dev(ctx, opts, ptr<double>(ctx->inY), n, ptr<double>(ctx->inG), p, dCov, dCov ? ncov : 0,
-                         ptr<double>(ctx->inK), dW, ptr<double>(ctx->outH2), dL, dL + p, status);
-  if (rc) { hipStreamSynchronize(ctx->stream); return rc; }
+  if ((rc = blmm_scan_alt_dev(ctx, opts, ptr<double>(ctx->inY), n, ptr<double>(ctx->inG), p, dCov, dCov ? ncov : 0,
+                              ptr<double>(ctx->inK), dW, ptr<double>(ctx->outH2), dL, dL + p, status))) return rc;
   ctx->last_L = dL; ctx->last_p = p; ctx->last_m = 1; ctx->last_f32 = false;
-  BLMM_HIP(hipMemcpyAsync(scalars_out, ctx->outH2.p, sizeof(double) * 2, hipMemcpyDeviceToHost, ctx->stream));
-  BLMM_HIP(hipMemcpyAsync(lod_out, dL, sizeof(double) * p, hipMemcpyDeviceToHost, ctx->stream));
-  BLMM_HIP(hipMemcpyAsync(h2_each_out, dL + p, sizeof(double) * p, hipMemcpyDeviceToHost, ctx->stream));
-  BLMM_HIP(hipStreamSynchronize(ctx->stream));
-  return check_sticky(ctx);
+  if ((rc = hc.down(scalars_out, ctx->outH2.p, sizeof(double) * 2)) || (rc = hc.down(lod_out, dL, sizeof(double) * p)) ||
+      (rc = hc.down(h2_each_out, dL + p, sizeof(double) * p))) return rc;
+  return (rc = hc.finish()) ? rc : check_sticky(ctx);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -2048,60 +1953,41 @@ int blmm_rotate(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, int64_t n
   if (rc) return rc;
   if (!Y || !G || !K || !Y0_out || !X0_out || !lambda_out) return fail(ctx, BLMM_ERR_INVALID, "rotate: NULL buffer");
   if (n < 1 || m < 1 || p < 1) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
-  BLMM_HIP(hipSetDevice(ctx->device));
-  if ((rc = ensure(ctx, ctx->inY, sizeof(double) * n * m))) return rc;
-  if ((rc = ensure(ctx, ctx->inG, sizeof(double) * n * p))) return rc;
-  if ((rc = ensure(ctx, ctx->inK, sizeof(double) * n * n))) return rc;
-  BLMM_HIP(hipMemcpyAsync(ctx->inY.p, Y, sizeof(double) * n * m, hipMemcpyHostToDevice, ctx->stream));
-  BLMM_HIP(hipMemcpyAsync(ctx->inG.p, G, sizeof(double) * n * p, hipMemcpyHostToDevice, ctx->stream));
-  BLMM_HIP(hipMemcpyAsync(ctx->inK.p, K, sizeof(double) * n * n, hipMemcpyHostToDevice, ctx->stream));
-  const double* dCov = nullptr;
-  if (Covar && ncov > 0) {
-    if ((rc = ensure(ctx, ctx->inCov, sizeof(double) * n * ncov))) return rc;
-    BLMM_HIP(hipMemcpyAsync(ctx->inCov.p, Covar, sizeof(double) * n * ncov, hipMemcpyHostToDevice, ctx->stream));
-    dCov = ptr<double>(ctx->inCov);
-  }
+  HostCall hc(ctx);
+  const double* dCov;
+  if ((rc = hc.begin()) || (rc = hc.up(ctx->inY, Y, sizeof(double) * n * m)) || (rc = hc.up(ctx->inG, G, sizeof(double) * n * p)) ||
+      (rc = hc.up(ctx->inK, K, sizeof(double) * n * n)) || (rc = hc.up_opt(ctx->inCov, Covar, n * ncov, &dCov))) return rc;
   Timer tm(ctx);
   Pipe P;
   if ((rc = prepare(ctx, opts, ptr<double>(ctx->inY), n, m, ptr<double>(ctx->inG), p, dCov, dCov ? ncov : 0,
                     ptr<double>(ctx->inK), nullptr, 0, P, tm))) return rc;
   if ((rc = ensure(ctx, ctx->outL, sizeof(double) * n * (size_t)(m > p ? m : p)))) return rc;
   double* tmp = ptr<double>(ctx->outL);
-  if ((rc = launch_untranspose(ctx, P.Yt, P.ldy, (int)n, m, tmp))) return rc;
-  BLMM_HIP(hipMemcpyAsync(Y0_out, tmp, sizeof(double) * n * m, hipMemcpyDeviceToHost, ctx->stream));
-  BLMM_HIP(hipStreamSynchronize(ctx->stream));
-  if ((rc = launch_untranspose(ctx, P.Xt, P.ldx, (int)n, p, tmp))) return rc;
-  BLMM_HIP(hipMemcpyAsync(X0_out + (size_t)n * P.c, tmp, sizeof(double) * n * p, hipMemcpyDeviceToHost, ctx->stream));
-  BLMM_HIP(hipMemcpyAsync(X0_out, P.Z0, sizeof(double) * n * P.c, hipMemcpyDeviceToHost, ctx->stream));
-  BLMM_HIP(hipMemcpyAsync(lambda_out, P.lam, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-  BLMM_HIP(hipStreamSynchronize(ctx->stream));
-  return finish_status(ctx, status, nullptr);
+  if ((rc = launch_untranspose(ctx, P.Yt, P.ldy, (int)n, m, tmp)) || (rc = hc.down(Y0_out, tmp, sizeof(double) * n * m))) return rc;
+  BLMM_HIP(hipStreamSynchronize(ctx->stream));      // tmp is reused for the markers
+  if ((rc = launch_untranspose(ctx, P.Xt, P.ldx, (int)n, p, tmp)) || (rc = hc.down(X0_out + (size_t)n * P.c, tmp, sizeof(double) * n * p)) ||
+      (rc = hc.down(X0_out, P.Z0, sizeof(double) * n * P.c)) || (rc = hc.down(lambda_out, P.lam, sizeof(double) * n))) return rc;
+  return (rc = hc.finish()) ? rc : finish_status(ctx, status, nullptr);
 }
 
 namespace {
 // uploads rotated host inputs into the pipeline's internal layouts (no eigen / rotation)
-int upload_rotated(blmm_ctx* ctx, const double* Y0, int64_t n, int64_t m, const double* Z0, int64_t c, const double* X0m,
+int upload_rotated(HostCall& hc, const double* Y0, int64_t n, int64_t m, const double* Z0, int64_t c, const double* X0m,
                    int64_t p, const double* lambda, Pipe& P) {
+  blmm_ctx* ctx = hc.ctx;
   if (n < 1 || m < 1 || c < 1 || c > CMAX || c >= n) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
   ctx->prep_valid = false;   // Z0 / lambda / the status block of a blmm_prepare_dev are overwritten below
   P.n = (int)n; P.c = (int)c; P.npad = (int)round_up(n, 8); P.ldr = (int)round_up(P.npad, 16);
   P.m = m; P.p = p; P.ldy = round_up(m, 128); P.ldx = round_up(p > 0 ? p : 1, 128);
   int rc;
-  if ((rc = ensure(ctx, ctx->inY, sizeof(double) * n * m))) return rc;
-  if ((rc = ensure(ctx, ctx->Yt, sizeof(double) * (size_t)P.npad * P.ldy))) return rc;
-  if ((rc = ensure(ctx, ctx->Z0, sizeof(double) * n * c))) return rc;
-  if ((rc = ensure(ctx, ctx->lam, sizeof(double) * n))) return rc;
-  if ((rc = reset_stat(ctx, &P.stat))) return rc;
+  if ((rc = ensure(ctx, ctx->Yt, sizeof(double) * (size_t)P.npad * P.ldy)) || (rc = reset_stat(ctx, &P.stat)) ||
+      (rc = hc.up(ctx->inY, Y0, sizeof(double) * n * m)) || (rc = hc.up(ctx->Z0, Z0, sizeof(double) * n * c)) ||
+      (rc = hc.up(ctx->lam, lambda, sizeof(double) * n))) return rc;
   P.Yt = ptr<double>(ctx->Yt); P.Z0 = ptr<double>(ctx->Z0); P.lam = ptr<double>(ctx->lam);
-  BLMM_HIP(hipMemcpyAsync(ctx->inY.p, Y0, sizeof(double) * n * m, hipMemcpyHostToDevice, ctx->stream));
-  BLMM_HIP(hipMemcpyAsync(P.Z0, Z0, sizeof(double) * n * c, hipMemcpyHostToDevice, ctx->stream));
-  BLMM_HIP(hipMemcpyAsync(P.lam, lambda, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
   if ((rc = to_rowmajor(ctx, ptr<double>(ctx->inY), (int)n, m, P.Yt, P.npad, P.ldy))) return rc;
   if (X0m && p > 0) {
-    if ((rc = ensure(ctx, ctx->inG, sizeof(double) * n * p))) return rc;
-    if ((rc = ensure(ctx, ctx->Xt, sizeof(double) * (size_t)P.npad * P.ldx))) return rc;
+    if ((rc = ensure(ctx, ctx->Xt, sizeof(double) * (size_t)P.npad * P.ldx)) || (rc = hc.up(ctx->inG, X0m, sizeof(double) * n * p))) return rc;
     P.Xt = ptr<double>(ctx->Xt);
-    BLMM_HIP(hipMemcpyAsync(ctx->inG.p, X0m, sizeof(double) * n * p, hipMemcpyHostToDevice, ctx->stream));
     if ((rc = to_rowmajor(ctx, ptr<double>(ctx->inG), (int)n, p, P.Xt, P.npad, P.ldx))) return rc;
   }
   return BLMM_OK;
@@ -2112,38 +1998,33 @@ int blmm_null_h2_brent(blmm_ctx* ctx, const blmm_opts* opts, const double* Y0, i
                        int64_t c, const double* lambda, double* h2_out, double* sigma2_out, double* ell_out, blmm_status* status) {
   if (!ctx) return BLMM_ERR_INVALID;
   if (!opts || !Y0 || !Z0 || !lambda || !h2_out) return fail(ctx, BLMM_ERR_INVALID, "null_h2_brent: NULL buffer");
-  BLMM_HIP(hipSetDevice(ctx->device));
+  HostCall hc(ctx);
   Pipe P;
-  int rc = upload_rotated(ctx, Y0, n, m, Z0, c, nullptr, 0, lambda, P);
-  if (rc) return rc;
+  int rc;
+  if ((rc = hc.begin()) || (rc = upload_rotated(hc, Y0, n, m, Z0, c, nullptr, 0, lambda, P))) return rc;
   const NullModel nm = null_model(P, opts);
-  if ((rc = ensure(ctx, ctx->h2, sizeof(double) * m))) return rc;
-  if ((rc = ensure(ctx, ctx->sig2, sizeof(double) * m))) return rc;
-  if ((rc = ensure(ctx, ctx->ell, sizeof(double) * m))) return rc;
-  if ((rc = launch_brent(ctx, nm, P.Yt, P.ldy, m, P.Z0, P.lam, ptr<double>(ctx->h2), ptr<double>(ctx->sig2), ptr<double>(ctx->ell), P.stat))) return rc;
-  BLMM_HIP(hipMemcpyAsync(h2_out, ctx->h2.p, sizeof(double) * m, hipMemcpyDeviceToHost, ctx->stream));
-  if (sigma2_out) BLMM_HIP(hipMemcpyAsync(sigma2_out, ctx->sig2.p, sizeof(double) * m, hipMemcpyDeviceToHost, ctx->stream));
-  if (ell_out) BLMM_HIP(hipMemcpyAsync(ell_out, ctx->ell.p, sizeof(double) * m, hipMemcpyDeviceToHost, ctx->stream));
-  BLMM_HIP(hipStreamSynchronize(ctx->stream));
-  return finish_status(ctx, status, nullptr);
+  if ((rc = ensure(ctx, ctx->h2, sizeof(double) * m)) || (rc = ensure(ctx, ctx->sig2, sizeof(double) * m)) || (rc = ensure(ctx, ctx->ell, sizeof(double) * m)) ||
+      (rc = launch_brent(ctx, nm, P.Yt, P.ldy, m, P.Z0, P.lam, ptr<double>(ctx->h2), ptr<double>(ctx->sig2), ptr<double>(ctx->ell), P.stat)) ||
+      (rc = hc.down(h2_out, ctx->h2.p, sizeof(double) * m)) || (rc = hc.down(sigma2_out, ctx->sig2.p, sizeof(double) * m)) ||
+      (rc = hc.down(ell_out, ctx->ell.p, sizeof(double) * m))) return rc;
+  return (rc = hc.finish()) ? rc : finish_status(ctx, status, nullptr);
 }
 
 int blmm_null_loglik_grid(blmm_ctx* ctx, const blmm_opts* opts, const double* Y0, int64_t n, int64_t m, const double* Z0,
                           int64_t c, const double* lambda, const double* h2_grid, int64_t ngrid, double* Ell_out, blmm_status* status) {
   if (!ctx) return BLMM_ERR_INVALID;
   if (!opts || !Y0 || !Z0 || !lambda || !Ell_out) return fail(ctx, BLMM_ERR_INVALID, "null_loglik_grid: NULL buffer");
-  BLMM_HIP(hipSetDevice(ctx->device));
+  HostCall hc(ctx);
   double* dgrid = nullptr;
-  int rc = grid_to_device(ctx, h2_grid, ngrid, &dgrid);
-  if (rc) return rc;
   Pipe P;
-  if ((rc = upload_rotated(ctx, Y0, n, m, Z0, c, nullptr, 0, lambda, P))) return rc;
+  int rc;
+  if ((rc = hc.begin()) || (rc = grid_to_device(ctx, h2_grid, ngrid, &dgrid)) || (rc = upload_rotated(hc, Y0, n, m, Z0, c, nullptr, 0, lambda, P)))
+    return rc;
   const NullModel nm = null_model(P, opts);
-  if ((rc = ensure(ctx, ctx->EllTab, sizeof(double) * (size_t)ngrid * m))) return rc;
-  if ((rc = launch_loglik_grid(ctx, nm, P.Yt, P.ldy, m, P.Z0, P.lam, dgrid, (int)ngrid, ptr<double>(ctx->EllTab), nullptr, nullptr, P.stat))) return rc;
-  BLMM_HIP(hipMemcpyAsync(Ell_out, ctx->EllTab.p, sizeof(double) * (size_t)ngrid * m, hipMemcpyDeviceToHost, ctx->stream));
-  BLMM_HIP(hipStreamSynchronize(ctx->stream));
-  return finish_status(ctx, status, nullptr);
+  if ((rc = ensure(ctx, ctx->EllTab, sizeof(double) * (size_t)ngrid * m)) ||
+      (rc = launch_loglik_grid(ctx, nm, P.Yt, P.ldy, m, P.Z0, P.lam, dgrid, (int)ngrid, ptr<double>(ctx->EllTab), nullptr, nullptr, P.stat)) ||
+      (rc = hc.down(Ell_out, ctx->EllTab.p, sizeof(double) * (size_t)ngrid * m))) return rc;
+  return (rc = hc.finish()) ? rc : finish_status(ctx, status, nullptr);
 }
 
 int blmm_weighted_liteqtl(blmm_ctx* ctx, const double* Y0, int64_t n, int64_t m, const double* X0, int64_t c, int64_t p,
@@ -2151,10 +2032,10 @@ int blmm_weighted_liteqtl(blmm_ctx* ctx, const double* Y0, int64_t n, int64_t m,
   if (!ctx) return BLMM_ERR_INVALID;
   if (!Y0 || !X0 || !lambda || !LOD_out || p < 1) return fail(ctx, BLMM_ERR_INVALID, "weighted_liteqtl: bad arguments");
   if (std::isinf(hsq / (1.0 - hsq))) return fail(ctx, BLMM_ERR_H2_ONE, "Heritability of 1 is not allowed.");
-  BLMM_HIP(hipSetDevice(ctx->device));
+  HostCall hc(ctx);
   Pipe P;
-  int rc = upload_rotated(ctx, Y0, n, m, X0, c, X0 + (size_t)n * c, p, lambda, P);
-  if (rc) return rc;
+  int rc;
+  if ((rc = hc.begin()) || (rc = upload_rotated(hc, Y0, n, m, X0, c, X0 + (size_t)n * c, p, lambda, P))) return rc;
   blmm_opts o; blmm_default_opts(&o);
   const NullModel nm = null_model(P, &o);
   if ((rc = ensure(ctx, ctx->h2, sizeof(double) * m))) return rc;
@@ -2166,10 +2047,8 @@ int blmm_weighted_liteqtl(blmm_ctx* ctx, const double* Y0, int64_t n, int64_t m,
   if ((rc = ensure(ctx, ctx->outL, sizeof(double) * (size_t)p * m))) return rc;
   ScanArgs a = scan_args(ctx, P, ptr<double>(ctx->panels), P.ldy, ptr<double>(ctx->outL), p, m);
   a.isx = ptr<double>(ctx->isx); a.ld_isx = P.ldx;
-  if ((rc = launch_scan_table(ctx, a))) return rc;
-  BLMM_HIP(hipMemcpyAsync(LOD_out, ctx->outL.p, sizeof(double) * (size_t)p * m, hipMemcpyDeviceToHost, ctx->stream));
-  BLMM_HIP(hipStreamSynchronize(ctx->stream));
-  return finish_status(ctx, status, nullptr);
+  if ((rc = launch_scan_table(ctx, a)) || (rc = hc.down(LOD_out, ctx->outL.p, sizeof(double) * (size_t)p * m))) return rc;
+  return (rc = hc.finish()) ? rc : finish_status(ctx, status, nullptr);
 }
 
 int blmm_liteqtl_given_h2(blmm_ctx* ctx, const double* Y0, int64_t n, int64_t m, const double* X0, int64_t c, int64_t p,
@@ -2178,15 +2057,13 @@ int blmm_liteqtl_given_h2(blmm_ctx* ctx, const double* Y0, int64_t n, int64_t m,
   if (!Y0 || !X0 || !lambda || !h2 || !LOD_out || p < 1) return fail(ctx, BLMM_ERR_INVALID, "liteqtl_given_h2: bad arguments");
   for (int64_t j = 0; j < m; ++j)
     if (std::isinf(h2[j] / (1.0 - h2[j]))) return fail(ctx, BLMM_ERR_H2_ONE, "Heritability of 1 is not allowed.");
-  BLMM_HIP(hipSetDevice(ctx->device));
+  HostCall hc(ctx);
   Pipe P;
-  int rc = upload_rotated(ctx, Y0, n, m, X0, c, X0 + (size_t)n * c, p, lambda, P);
-  if (rc) return rc;
+  int rc;
+  if ((rc = hc.begin()) || (rc = upload_rotated(hc, Y0, n, m, X0, c, X0 + (size_t)n * c, p, lambda, P))) return rc;
   blmm_opts o; blmm_default_opts(&o);
   const NullModel nm = null_model(P, &o);
-  if ((rc = ensure(ctx, ctx->h2, sizeof(double) * m))) return rc;
-  BLMM_HIP(hipMemcpyAsync(ctx->h2.p, h2, sizeof(double) * m, hipMemcpyHostToDevice, ctx->stream));
-  if ((rc = ensure(ctx, ctx->outL, sizeof(double) * (size_t)p * m))) return rc;
+  if ((rc = hc.up(ctx->h2, h2, sizeof(double) * m)) || (rc = ensure(ctx, ctx->outL, sizeof(double) * (size_t)p * m))) return rc;
   // the same kernel choice as bulkscan(method = null-exact): low-rank weights form with its residual guard unless
   // BLMM_EXACT=full, c = 4 or n beyond the basis kernel
   if (!exact_full(ctx) && P.c <= 3 && n <= 6000) {
@@ -2200,9 +2077,8 @@ int blmm_liteqtl_given_h2(blmm_ctx* ctx, const double* Y0, int64_t n, int64_t m,
     if ((rc = launch_scan_exact(ctx, a, P.c))) return rc;
     if ((rc = illcond_rescan(ctx, P, nm, m, ptr<double>(ctx->h2), ptr<double>(ctx->outL), p))) return rc;
   }
-  BLMM_HIP(hipMemcpyAsync(LOD_out, ctx->outL.p, sizeof(double) * (size_t)p * m, hipMemcpyDeviceToHost, ctx->stream));
-  BLMM_HIP(hipStreamSynchronize(ctx->stream));
-  return finish_status(ctx, status, nullptr);
+  if ((rc = hc.down(LOD_out, ctx->outL.p, sizeof(double) * (size_t)p * m))) return rc;
+  return (rc = hc.finish()) ? rc : finish_status(ctx, status, nullptr);
 }
 
 }  // extern "C"

@@ -112,8 +112,9 @@ struct blmm_ctx {
   bool wb_on_side2 = false;            // start_wbasis: the weight basis went to the second side stream (lr_begin follows it there)
   // Host entry points (blmm_bulkscan, blmm_bulkscan_reduced): K, the covariates and the weights go up first, the eigen phase is
   // queued, and only then Y and G are copied -- on their own stream, beside the eigen kernels (0.23 ms at n = 79 that the caller
-  // used to wait for behind 27 MB of uploads).  up_pending: upload_bulk_inputs left them for prepare(); in_wait: the copies are
-  // in flight, whoever reads inY / inG waits for ev_in first.
+  // used to wait for behind 27 MB of uploads).  up_pending: HostCall::defer_yg left them for prepare(); in_wait: the copies are
+  // in flight, whoever reads inY / inG waits for ev_in first.  HostCall owns this state: it sets it, and its destructor clears it
+  // at the end of every host-pointer call.
   hipStream_t copy = nullptr; hipEvent_t ev_in = nullptr, ev_inY = nullptr;   // ev_inY: the traits are there (the main stream's need), ev_in: the markers too
   bool up_pending = false, in_wait = false;
   const void* up_src[2] = {nullptr, nullptr}; void* up_dst[2] = {nullptr, nullptr}; size_t up_bytes[2] = {0, 0};
@@ -179,6 +180,28 @@ struct GridKernelGuard {
 };
 // host_path.hip: device -> caller memory in stream order; returns when the bytes are in place
 int copy_to_host(blmm_ctx* ctx, void* dst, const void* dsrc, size_t bytes);
+// host_path.hip: the host-pointer leg of an entry point that takes caller memory, one on the stack per call.  begin() selects the
+// device; up() copies a caller array into device memory on ctx->stream (the DevBuf form ensures the buffer first); up_opt() does so
+// for an optional input and yields nullptr for a null pointer or an empty array; defer_yg() leaves Y and G to prepare()
+// (blmm_ctx::up_pending); down() is a small device -> host copy on ctx->stream, skipped for a null destination (copy_to_host moves
+// the large blocks); finish() is the success path's final synchronisation.  Every other exit -- an error rc, a BLMM_HIP early
+// return, a failed ensure -- leaves through the destructor, which waits for the context's four streams: nothing the call enqueued
+// still reads caller memory or the context's input buffers once it has returned.
+struct HostCall {
+  blmm_ctx* ctx;
+  bool done = false;
+  explicit HostCall(blmm_ctx* c) : ctx(c) {}
+  ~HostCall();
+  HostCall(const HostCall&) = delete;
+  HostCall& operator=(const HostCall&) = delete;
+  int begin();
+  int up(void* dst, const void* src, size_t bytes);
+  int up(DevBuf& b, const void* src, size_t bytes);
+  int up_opt(DevBuf& b, const double* src, int64_t count, const double** dev);
+  int defer_yg(const double* Y, size_t ybytes, const double* G, size_t gbytes);
+  int down(void* dst, const void* dsrc, size_t bytes);
+  int finish(bool sync = true);   // sync = false: the last copy has waited already (copy_to_host, the blmm_last_* consumers)
+};
 void destroy_host_stage(HostStage* hs);
 template <typename T>
 inline T* ptr(DevBuf& b) { return reinterpret_cast<T*>(b.p); }

@@ -267,39 +267,27 @@ int blmm_bulkscan_multi(blmm_multi* mc, const blmm_opts* opts, const blmm_multi_
   const int64_t cols_alloc = full ? blk * R : blk;
   int rc = on_all(mc, [&](int r) -> int {
     blmm_ctx* ctx = mc->ctx[r];
-    BLMM_HIP(hipSetDevice(ctx->device));
+    HostCall hc(ctx);
     int64_t lo, hi;
     blmm_multi_shard(m, r, R, &lo, &hi);
     const int64_t mr = hi - lo;
+    const double *dCov, *dW;
     int e;
-    if ((e = ensure(ctx, mc->dY[r], sizeof(double) * n * (mr > 0 ? mr : 1)))) return e;
-    if ((e = ensure(ctx, mc->dG[r], sizeof(double) * n * (p > 0 ? p : 1)))) return e;
-    if ((e = ensure(ctx, mc->dK[r], sizeof(double) * n * n))) return e;
-    if ((e = ensure(ctx, mc->dL[r], sizeof(double) * (size_t)(p > 0 ? p : 1) * (cols_alloc > 0 ? cols_alloc : 1)))) return e;
-    if ((e = ensure(ctx, mc->dH[r], sizeof(double) * (alt ? (size_t)(p > 0 ? p : 1) : 1) * (cols_alloc > 0 ? cols_alloc : 1)))) return e;
-    if (mr > 0) BLMM_HIP(hipMemcpyAsync(mc->dY[r].p, Y + (size_t)lo * n, sizeof(double) * n * mr, hipMemcpyHostToDevice, ctx->stream));
-    if (p > 0) BLMM_HIP(hipMemcpyAsync(mc->dG[r].p, G, sizeof(double) * n * p, hipMemcpyHostToDevice, ctx->stream));
-    BLMM_HIP(hipMemcpyAsync(mc->dK[r].p, K, sizeof(double) * n * n, hipMemcpyHostToDevice, ctx->stream));
-    const double* dCov = nullptr; const double* dW = nullptr;
-    if (Covar && ncov > 0) {
-      if ((e = ensure(ctx, mc->dCov[r], sizeof(double) * n * ncov))) return e;
-      BLMM_HIP(hipMemcpyAsync(mc->dCov[r].p, Covar, sizeof(double) * n * ncov, hipMemcpyHostToDevice, ctx->stream));
-      dCov = ptr<double>(mc->dCov[r]);
-    }
-    if (weights) {
-      if ((e = ensure(ctx, mc->dW[r], sizeof(double) * n))) return e;
-      BLMM_HIP(hipMemcpyAsync(mc->dW[r].p, weights, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
-      dW = ptr<double>(mc->dW[r]);
-    }
+    if ((e = hc.begin()) ||
+        (e = ensure(ctx, mc->dL[r], sizeof(double) * (size_t)(p > 0 ? p : 1) * (cols_alloc > 0 ? cols_alloc : 1))) ||
+        (e = ensure(ctx, mc->dH[r], sizeof(double) * (alt ? (size_t)(p > 0 ? p : 1) : 1) * (cols_alloc > 0 ? cols_alloc : 1))) ||
+        (e = hc.up(mc->dY[r], Y + (size_t)lo * n, sizeof(double) * n * (mr > 0 ? mr : 0))) || (e = hc.up(mc->dG[r], G, sizeof(double) * n * p)) ||
+        (e = hc.up(mc->dK[r], K, sizeof(double) * n * n)) || (e = hc.up_opt(mc->dCov[r], Covar, n * ncov, &dCov)) ||
+        (e = hc.up_opt(mc->dW[r], weights, n, &dW))) return e;
     const int64_t off = full ? lo : 0;
     double* dL = ptr<double>(mc->dL[r]) + (size_t)off * p;
     double* dH = ptr<double>(mc->dH[r]) + (alt ? (size_t)off * p : (size_t)off);
     e = blmm_bulkscan_dev(ctx, opts, ptr<double>(mc->dY[r]), n, mr, ptr<double>(mc->dG[r]), p, dCov, dCov ? ncov : 0,
                           ptr<double>(mc->dK[r]), dW, h2_grid, ngrid, dL, p > 0 ? p : 1, dH, status ? status + r : nullptr);
-    if (e) { (void)hipStreamSynchronize(ctx->stream); return e; }
     // the host inputs may be released; the blocks are complete; a device-side failure of this call made without a status
     // (grid-barrier timeout, eigensolver abort) is reported by this call
-    return blmm_synchronize(ctx);
+    if (e || (e = blmm_synchronize(ctx))) return e;
+    return hc.finish(false);
   });
   if (rc) return rc;
   mc->last_m = m; mc->last_p = p; mc->last_block = blk; mc->last_gather = gather; mc->last_method = opts->method;

@@ -142,6 +142,62 @@ int copy_to_host(blmm_ctx* ctx, void* dst, const void* dsrc, size_t bytes) {
   return BLMM_OK;
 }
 
+int HostCall::begin() {
+  BLMM_HIP(hipSetDevice(ctx->device));
+  return BLMM_OK;
+}
+
+int HostCall::up(void* dst, const void* src, size_t bytes) {
+  if (bytes) BLMM_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+  return BLMM_OK;
+}
+
+int HostCall::up(DevBuf& b, const void* src, size_t bytes) {
+  int rc = ensure(ctx, b, bytes);
+  return rc ? rc : up(b.p, src, bytes);
+}
+
+int HostCall::up_opt(DevBuf& b, const double* src, int64_t count, const double** dev) {
+  *dev = nullptr;
+  if (!src || count <= 0) return BLMM_OK;
+  int rc = up(b, src, sizeof(double) * (size_t)count);
+  if (!rc) *dev = static_cast<const double*>(b.p);
+  return rc;
+}
+
+// The traits and the markers are copied by prepare() on ctx->copy once the eigen phase is queued (see blmm_ctx::up_pending)
+int HostCall::defer_yg(const double* Y, size_t ybytes, const double* G, size_t gbytes) {
+  int rc;
+  if ((rc = ensure(ctx, ctx->inY, ybytes)) || (rc = ensure(ctx, ctx->inG, gbytes))) return rc;
+  ctx->up_src[0] = Y; ctx->up_dst[0] = ctx->inY.p; ctx->up_bytes[0] = ybytes;
+  ctx->up_src[1] = G; ctx->up_dst[1] = ctx->inG.p; ctx->up_bytes[1] = gbytes;
+  ctx->up_pending = true; ctx->in_wait = false;
+  return BLMM_OK;
+}
+
+int HostCall::down(void* dst, const void* dsrc, size_t bytes) {
+  if (dst && bytes) BLMM_HIP(hipMemcpyAsync(dst, dsrc, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  return BLMM_OK;
+}
+
+int HostCall::finish(bool sync) {
+  if (sync) BLMM_HIP(hipStreamSynchronize(ctx->stream));
+  done = true;
+  return BLMM_OK;
+}
+
+HostCall::~HostCall() {
+  if (!done) {
+    // an error exit: wait for whatever the call enqueued -- uploads from caller memory, side-stream readers of the workspace.
+    // The call's own rc and message stand; these waits only drain.
+    (void)hipStreamSynchronize(ctx->stream);
+    for (hipStream_t s : {ctx->side, ctx->side2, ctx->copy})
+      if (s) (void)hipStreamSynchronize(s);
+    (void)hipGetLastError();
+  }
+  ctx->up_pending = false; ctx->in_wait = false;
+}
+
 }  // namespace blmm
 
 extern "C" {

@@ -1,0 +1,225 @@
+"""The contract of every host-pointer entry point that has a device-pointer twin: the host form uploads its inputs, runs the
+twin and downloads the result, so it returns what the twin returns -- bit for bit, NaN positions included.  One small seeded
+shape per entry point; a dropped upload or a wrong buffer offset in the host layer (host_path.hip: HostCall) fails here.
+
+The twins run in-process on buffers of the HIP runtime (common.DevBuf), on the context's own stream: the test synchronises the
+context before it reads them back."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from common import DevBuf, make_data
+
+pytestmark = pytest.mark.gpu
+
+GRID = [i / 10.0 for i in range(10)]
+
+
+def col(a):
+    """A host matrix as the column-major bytes the C ABI reads."""
+    return np.asfortranarray(np.asarray(a, dtype=np.float64)).ravel("F")
+
+
+def same(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    assert a.shape == b.shape and a.dtype == b.dtype, (a.shape, b.shape, a.dtype, b.dtype)
+    assert np.array_equal(a, b, equal_nan=a.dtype.kind == "f")
+
+
+def opts(blmm, method, **kw):
+    return blmm.api._opts(method, kw.get("reml", False), True, "eigen", 1, kw.get("prior_variance", 1.0), 0.0)
+
+
+def inputs(Y, G, K, Cov=None, w=None):
+    return (DevBuf(col(Y)), DevBuf(col(G)), DevBuf(col(K)), DevBuf(col(Cov)) if Cov is not None else None,
+            DevBuf(np.asarray(w, dtype=np.float64)) if w is not None else None)
+
+
+def vp(b):
+    return None if b is None else C.c_void_p(b.ptr)
+
+
+@pytest.mark.parametrize("method,ncov,weighted", [("null-exact", 2, True), ("null-grid", 0, False), ("alt-grid", 1, False)])
+def test_bulkscan_host_equals_dev(blmm, method, ncov, weighted):
+    Y, G, K, Cov = make_data(p=333, m=70, seed=8100 + ncov, ncov=ncov)
+    n, m = Y.shape
+    p = G.shape[1]
+    w = np.linspace(0.5, 2.0, n) if weighted else None
+    ctx = blmm.Context(0)
+    host = blmm.bulkscan(Y, G, K, Cov, method=method, h2_grid=GRID, weights=w, ctx=ctx)
+    meth = blmm.api._METHODS[method]
+    o = opts(blmm, meth)
+    dY, dG, dK, dC, dW = inputs(Y, G, K, Cov, w)
+    alt = method == "alt-grid"
+    dL, dH = DevBuf(nbytes=8 * p * m), DevBuf(nbytes=8 * (p * m if alt else m))
+    grid = np.asarray(GRID) if meth != blmm._lib.BLMM_NULL_EXACT else None
+    ctx.check(ctx.lib.blmm_bulkscan_dev(ctx.h, C.byref(o), vp(dY), n, m, vp(dG), p, vp(dC), ncov, vp(dK), vp(dW),
+                                        None if grid is None else grid.ctypes.data_as(C.c_void_p), 0 if grid is None else len(grid),
+                                        vp(dL), p, vp(dH), None))
+    ctx.synchronize()
+    same(host["L"], dL.get((m, p)).T)
+    if alt:
+        same(host["h2_panel"], dH.get((m, p)).T)
+    else:
+        same(host["h2_null_list"], dH.get(m))
+
+
+@pytest.mark.parametrize("method", ["null-exact", "alt-grid"])
+def test_bulkscan_reduced_host_equals_dev(blmm, method):
+    Y, G, K, Cov = make_data(p=700, m=90, seed=8200, ncov=1)
+    n, m = Y.shape
+    p = G.shape[1]
+    ctx = blmm.Context(0)
+    thr = 2.5
+    host = blmm.bulkscan_reduced(Y, G, K, Cov, method=method, h2_grid=GRID, threshold=thr, cap=1 << 16, ctx=ctx)
+    route = host["route"]
+    meth = blmm.api._METHODS[method]
+    o = opts(blmm, meth)
+    dY, dG, dK, dC, _ = inputs(Y, G, K, Cov)
+    cap = 1 << 16
+    dmx, dax, dh2 = DevBuf(nbytes=8 * m), DevBuf(nbytes=8 * m), DevBuf(nbytes=8 * m)
+    dti, dtj, dtl, dtc = DevBuf(nbytes=4 * cap), DevBuf(nbytes=4 * cap), DevBuf(nbytes=8 * cap), DevBuf(np.zeros(1, dtype=np.int64))
+    r = blmm._lib.blmm_reduced(dmx.ptr, dax.ptr, 1, thr, cap, dti.ptr, dtj.ptr, dtl.ptr, dtc.ptr)
+    grid = np.asarray(GRID) if meth != blmm._lib.BLMM_NULL_EXACT else None
+    ctx.check(ctx.lib.blmm_bulkscan_reduced_dev(ctx.h, C.byref(o), vp(dY), n, m, vp(dG), p, vp(dC), 1, vp(dK), None,
+                                                None if grid is None else grid.ctypes.data_as(C.c_void_p),
+                                                0 if grid is None else len(grid), C.byref(r), vp(dh2), None))
+    ctx.synchronize()
+    assert int(ctx.lib.blmm_last_reduced_route(ctx.h)) == route
+    same(host["max_lod"], dmx.get(m))
+    same(host["argmax"], dax.get(m, np.int64))
+    if method != "alt-grid":
+        same(host["h2_null_list"], dh2.get(m))
+    k = int(dtc.get(1, np.int64)[0])
+    assert k == len(host["triplets"][0]) > 0
+    ii, jj, ll = dti.get(k, np.int32), dtj.get(k, np.int32), dtl.get(k)
+    order = np.lexsort((ii, jj))
+    for h, d in zip(host["triplets"], (ii[order], jj[order], ll[order])):
+        same(h, d)
+
+
+@pytest.mark.parametrize("f32", [False, True])
+def test_scan_perms_host_equals_dev(blmm, f32):
+    Y, G, K, Cov = make_data(p=257, m=1, seed=8300, ncov=1)
+    n, p, nperms = Y.shape[0], G.shape[1], 40
+    w = np.linspace(0.8, 1.2, n)
+    ctx = blmm.Context(0)
+    host = blmm.scan(Y[:, 0], G, K, Cov, weights=w, permutation_test=True, nperms=nperms, rndseed=11,
+                     perm_precision="f32" if f32 else "f64", ctx=ctx)
+    o = opts(blmm, blmm._lib.BLMM_NULL_EXACT, prior_variance=0.0)
+    dY, dG, dK, dC, dW = inputs(Y[:, 0], G, K, Cov, w)
+    dsc, dlod = DevBuf(nbytes=16), DevBuf(nbytes=8 * p)
+    dLp = DevBuf(nbytes=(4 if f32 else 8) * p * nperms)
+    fn = ctx.lib.blmm_scan_perms_f32_dev if f32 else ctx.lib.blmm_scan_perms_dev
+    ctx.check(fn(ctx.h, C.byref(o), vp(dY), n, vp(dG), p, vp(dC), 1, vp(dK), vp(dW), nperms, C.c_uint64(11), None,
+                 vp(dsc), vp(dlod), vp(dLp), None))
+    ctx.synchronize()
+    sc = dsc.get(2)
+    assert host["sigma2_e"] == sc[0] and host["h2_null"] == sc[1]
+    same(host["lod"], dlod.get(p))
+    same(host["L_perms"], dLp.get((nperms, p), np.float32 if f32 else np.float64).T)
+
+
+def test_scan_alt_host_equals_dev(blmm):
+    Y, G, K, Cov = make_data(p=150, m=1, seed=8400, ncov=2)
+    n, p = Y.shape[0], G.shape[1]
+    ctx = blmm.Context(0)
+    host = blmm.scan(Y[:, 0], G, K, Cov, assumption="alt", ctx=ctx)
+    o = opts(blmm, blmm._lib.BLMM_NULL_EXACT, prior_variance=0.0)
+    dY, dG, dK, dC, _ = inputs(Y[:, 0], G, K, Cov)
+    dsc, dlod, dh2 = DevBuf(nbytes=16), DevBuf(nbytes=8 * p), DevBuf(nbytes=8 * p)
+    ctx.check(ctx.lib.blmm_scan_alt_dev(ctx.h, C.byref(o), vp(dY), n, vp(dG), p, vp(dC), 2, vp(dK), None, vp(dsc), vp(dlod), vp(dh2), None))
+    ctx.synchronize()
+    sc = dsc.get(2)
+    assert host["sigma2_e"] == sc[0] and host["h2_null"] == sc[1]
+    same(host["lod"], dlod.get(p))
+    same(host["h2_each_marker"], dh2.get(p))
+
+
+def test_bulkscan_alt_exact_host_equals_dev(blmm):
+    Y, G, K, Cov = make_data(p=130, m=9, seed=8500, ncov=1)
+    n, m = Y.shape
+    p = G.shape[1]
+    w = np.linspace(0.7, 1.4, n)
+    ctx = blmm.Context(0)
+    host = blmm.bulkscan_alt_exact(Y, G, K, Cov, weights=w, ctx=ctx)
+    o = opts(blmm, blmm._lib.BLMM_NULL_EXACT, prior_variance=0.0)
+    dY, dG, dK, dC, dW = inputs(Y, G, K, Cov, w)
+    dL, dH, dh2, ds2 = DevBuf(nbytes=8 * p * m), DevBuf(nbytes=8 * p * m), DevBuf(nbytes=8 * m), DevBuf(nbytes=8 * m)
+    ctx.check(ctx.lib.blmm_bulkscan_alt_exact_dev(ctx.h, C.byref(o), vp(dY), n, m, vp(dG), p, vp(dC), 1, vp(dK), vp(dW),
+                                                  vp(dL), p, vp(dH), p, vp(dh2), vp(ds2), None))
+    ctx.synchronize()
+    same(host["L"], dL.get((m, p)).T)
+    same(host["h2_panel"], dH.get((m, p)).T)
+    same(host["h2_null_list"], dh2.get(m))
+    same(host["sigma2_e"], ds2.get(m))
+
+
+def test_kinship_host_equals_dev(blmm):
+    _, G, _, _ = make_data(n=97, p=411, m=1, seed=8600, bxd=False)
+    n, p = G.shape
+    ctx = blmm.Context(0)
+    dG, dK = DevBuf(col(G)), DevBuf(nbytes=8 * n * n)
+    ctx.check(ctx.lib.blmm_kinship_dev(ctx.h, vp(dG), n, p, vp(dK)))
+    ctx.synchronize()
+    Kd = dK.get((n, n)).T
+    same(blmm.calcKinship(G, ctx=ctx), Kd)
+    # digits: k_round_digits is rint(v * 10^d) / 10^d -- NumPy's round, on the same unrounded matrix
+    same(blmm.calcKinship(G, ctx=ctx, digits=6), np.round(Kd, 6))
+
+
+def test_lod_consumers_host_equal_dev(blmm):
+    Y, G, K, _ = make_data(p=300, m=50, seed=8700)
+    ctx = blmm.Context(0)
+    Lm = np.asfortranarray(blmm.bulkscan(Y, G, K, method="null-grid", h2_grid=GRID, ctx=ctx)["L"])
+    Lm[5, 3] = np.nan
+    Lm[:, 7] = np.nan
+    Lm[11, 9] = Lm[200, 9] = Lm[:, 9].max() + 1.0            # a tie: the lowest marker wins in both forms
+    p, m = Lm.shape
+    dL = DevBuf(col(Lm))
+
+    mx, arg = blmm.lod_colmax(Lm, ctx=ctx)
+    dmx, dax = DevBuf(nbytes=8 * m), DevBuf(nbytes=8 * m)
+    ctx.check(ctx.lib.blmm_lod_colmax_dev(ctx.h, vp(dL), p, m, p, vp(dmx), vp(dax)))
+    ctx.synchronize()
+    same(mx, dmx.get(m))
+    same(arg, dax.get(m, np.int64))
+    lmx, larg = np.empty(m), np.empty(m, dtype=np.int64)   # the host form's upload is the context's resident matrix now
+    ctx.check(ctx.lib.blmm_last_lod_colmax(ctx.h, lmx.ctypes.data_as(C.c_void_p), larg.ctypes.data_as(C.c_void_p)))
+    same(mx, lmx)
+    same(arg, larg)
+
+    P = blmm.lod2log10p(Lm, 1, ctx=ctx)
+    dP = DevBuf(nbytes=8 * p * m)
+    ctx.check(ctx.lib.blmm_lod2log10p_dev(ctx.h, vp(dL), p, m, p, 1, vp(dP), p))
+    ctx.synchronize()
+    same(P, dP.get((m, p)).T)
+
+    thr, cap = float(np.nanquantile(Lm, 0.9)), 4096
+    ti, tj, tl = blmm.lod_threshold(Lm, thr, ctx=ctx, cap=cap)
+    dti, dtj, dtl, dtc = DevBuf(nbytes=4 * cap), DevBuf(nbytes=4 * cap), DevBuf(nbytes=8 * cap), DevBuf(nbytes=8)
+    ctx.check(ctx.lib.blmm_lod_threshold_dev(ctx.h, vp(dL), p, m, p, thr, cap, vp(dti), vp(dtj), vp(dtl), vp(dtc)))
+    ctx.synchronize()
+    k = int(dtc.get(1, np.int64)[0])
+    assert 0 < k == len(ti) <= cap
+    ii, jj, ll = dti.get(k, np.int32), dtj.get(k, np.int32), dtl.get(k)
+    order = np.lexsort((ii, jj))
+    for h, d in zip((ti, tj, tl), (ii[order], jj[order], ll[order])):
+        same(h, d)
+    li, lj, ll2 = (np.empty(cap, dtype=np.int32), np.empty(cap, dtype=np.int32), np.empty(cap))
+    cnt = C.c_int64(0)
+    ctx.check(ctx.lib.blmm_last_lod_threshold(ctx.h, thr, cap, li.ctypes.data_as(C.c_void_p), lj.ctypes.data_as(C.c_void_p),
+                                              ll2.ctypes.data_as(C.c_void_p), C.byref(cnt)))
+    assert cnt.value == k
+    order = np.lexsort((li[:k], lj[:k]))
+    for h, d in zip((ti, tj, tl), (li[:k][order], lj[:k][order], ll2[:k][order])):
+        same(h, d)
+
+    Lp = np.asfortranarray(Lm[:, 10:])                      # as permutation maxima: no NaN column
+    dLp = DevBuf(col(Lp))
+    host = blmm.get_thresholds(Lp, [0.5, 0.1, 0.05], ctx=ctx)
+    got = np.empty(3)
+    ctx.check(ctx.lib.blmm_get_thresholds_dev(ctx.h, vp(dLp), p, Lp.shape[1], p, host["probs"].ctypes.data_as(C.c_void_p), 3,
+                                              got.ctypes.data_as(C.c_void_p)))
+    same(host["thrs"], got)
