@@ -806,6 +806,59 @@ def get_thresholds(L_perms, signif_level, ctx: Optional[Context] = None):
     return {"probs": thr_probs, "thrs": thrs}
 
 
+def bulkscan_perms(Y, G, K, Covar=None, *, nperms: int = 1024, rndseed: int = 0, perm_idx=None, signif_level=(0.10, 0.05),
+                   weights=None, prior_variance: float = 0.0, prior_sample_size: float = 0.0, addIntercept: bool = True,
+                   reml: bool = False, optim_interval: int = 1, decomp_scheme: str = "eigen", ctx: Optional[Context] = None) -> dict:
+    """The permutation test for every trait (blmm_bulkscan_perms): for trait j, scan(Y[:, j], G, K, Covar; permutation_test=True,
+    nperms, rndseed / perm_idx) (src/scan.jl:485-557) under ONE permutation set shared by all traits -- bit for bit that call's
+    L_perms reduced on the device; the p x m x nperms LOD tensor is never written.  Keyword defaults are scan's.  Returns
+    {"h2_null", "sigma2_e", "lod_max", "lod_argmax" (0-based): m each; "max_perms": nperms x m (genome-wide maximum LOD of each
+    permuted copy); "thresholds": len(signif_level) x m (get_thresholds(L_perms_j, signif_level)); "pvals_perm": m,
+    (1 + #{k : max_perms[k, j] >= lod_max[j]}) / (nperms + 1); "probs": 1 - signif_level}.  nperms = 0: the fit and the peaks,
+    thresholds and p-values NaN."""
+    Y = _F(Y)
+    G = _F(G)
+    K = _F(K)
+    n, m = Y.shape
+    p = G.shape[1]
+    if G.shape[0] != n or K.shape[0] != n or K.shape[1] != n:
+        raise BulkLMMError("Dimension mismatch.", -2)
+    _check_n(n)
+    if nperms < 0:
+        raise BulkLMMError("The required number of permutations must be a positive integer.", -9)
+    cov = None
+    ncov = 0
+    if Covar is not None:
+        cov = _F(Covar)
+        if cov.shape[0] != n:
+            raise BulkLMMError("Dimension mismatch.", -2)
+        ncov = cov.shape[1]
+    else:
+        addIntercept = True
+    w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).ravel())
+    if w is not None and w.shape[0] != n:
+        raise BulkLMMError("Dimension mismatch.", -2)
+    pidx = None
+    if perm_idx is not None and nperms > 0:
+        pidx = np.asfortranarray(np.asarray(perm_idx, dtype=np.int32))
+        if pidx.shape != (n, nperms):
+            raise BulkLMMError("Dimension mismatch.", -2)
+    probs = np.ascontiguousarray(1.0 - np.atleast_1d(np.asarray(signif_level, dtype=np.float64)))
+    ctx = ctx or default_context()
+    o = _opts(L.BLMM_NULL_EXACT, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
+    st = L.blmm_status()
+    h2, s2, mx, pv = np.empty(m), np.empty(m), np.empty(m), np.empty(m)
+    arg = np.empty(m, dtype=np.int64)
+    mp = np.empty((max(nperms, 1), m), order="F")
+    thr = np.empty((probs.shape[0], m), order="F")
+    ctx.check(ctx.lib.blmm_bulkscan_perms(ctx.h, C.byref(o), _p(Y), n, m, _p(G), p, _p(cov), ncov, _p(K), _p(w), int(nperms),
+                                          C.c_uint64(int(rndseed)), _p(pidx), _p(probs), probs.shape[0], _p(h2), _p(s2), _p(mx),
+                                          _p(arg), _p(mp), _p(thr), _p(pv), C.byref(st)))
+    _raise_status(st)
+    return {"h2_null": h2, "sigma2_e": s2, "lod_max": mx, "lod_argmax": arg, "max_perms": mp[:nperms], "thresholds": thr,
+            "pvals_perm": pv, "probs": probs}
+
+
 # ---- lower-level seams ------------------------------------------------------------------------------
 
 def transform_rotation(y, g, K, *, addIntercept: bool = True, decomp_scheme: str = "eigen", ctx: Optional[Context] = None):
@@ -1098,4 +1151,29 @@ def scan_perms_dev(ctx: Context, y, G, K, scalars_out, lod_out, Lperms_out, *, n
                                           None if perm_idx is None else perm_idx.data_ptr(), scalars_out.data_ptr(),
                                           lod_out.data_ptr(), None if Lperms_out is None else Lperms_out.data_ptr(),
                                           C.byref(st) if status else None))
+    return st
+
+
+def bulkscan_perms_dev(ctx: Context, Y, G, K, h2_out, sigma2_out, lod_max_out, lod_argmax_out, max_perms_out=None, thr_out=None,
+                       pval_out=None, *, nperms: int, seed: int = 0, perm_idx=None, signif_level=(0.10, 0.05), Covar=None,
+                       weights=None, addIntercept: bool = True, prior_variance: float = 0.0, prior_sample_size: float = 0.0,
+                       reml: bool = False, optim_interval: int = 1, decomp_scheme: str = "eigen", status: bool = False):
+    """blmm_bulkscan_perms_dev on torch CUDA tensors (layouts as bulkscan_dev / scan_perms_dev): Y (m, n), G (p, n), K (n, n);
+    h2_out / sigma2_out / lod_max_out / pval_out (m,) float64, lod_argmax_out (m,) int64, max_perms_out (m, nperms) [= nperms x m
+    column-major], thr_out (m, len(signif_level)), perm_idx (nperms, n) int32 or None (the library's generator with `seed`).
+    Enqueues on the context's stream (status=True synchronises it)."""
+    m, n = Y.shape
+    p = G.shape[0]
+    ncov = 0 if Covar is None else Covar.shape[0]
+    if Covar is None:
+        addIntercept = True
+    o = _opts(L.BLMM_NULL_EXACT, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
+    probs = np.ascontiguousarray(1.0 - np.atleast_1d(np.asarray(signif_level, dtype=np.float64)))
+    st = L.blmm_status() if status else None
+    dp = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+    ctx.check(ctx.lib.blmm_bulkscan_perms_dev(ctx.h, C.byref(o), Y.data_ptr(), n, m, G.data_ptr(), p, dp(Covar), ncov, K.data_ptr(),
+                                              dp(weights), int(nperms), C.c_uint64(int(seed)), dp(perm_idx), _p(probs),
+                                              probs.shape[0], h2_out.data_ptr(), sigma2_out.data_ptr(), lod_max_out.data_ptr(),
+                                              lod_argmax_out.data_ptr(), dp(max_perms_out), dp(thr_out), dp(pval_out),
+                                              C.byref(st) if status else None))
     return st

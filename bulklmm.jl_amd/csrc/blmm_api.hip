@@ -4,6 +4,7 @@
 // scan_perms_lite (src/scan.jl:485-557) of BulkLMM.jl; nothing here falls back to a CPU path.
 #include "blmm_internal.h"
 #include "fastmath.h"
+#include <algorithm>
 #include <cmath>
 #include <cstddef>
 #include <chrono>
@@ -788,7 +789,7 @@ void blmm_destroy(blmm_ctx* ctx) {
                     &ctx->iyy, &ctx->h2, &ctx->h2idx, &ctx->sig2, &ctx->ell, &ctx->isx, &ctx->stat, &ctx->gridd, &ctx->misc,
                     &ctx->EllTab, &ctx->inY, &ctx->inG, &ctx->inK, &ctx->inCov, &ctx->inW, &ctx->outL, &ctx->outH2,
                     &ctx->tmpA, &ctx->tmpB, &ctx->tmpC, &ctx->perm, &ctx->r0, &ctx->altbuf, &ctx->logtab, &ctx->lraw,
-                    &ctx->wbQ, &ctx->wbW, &ctx->wbRk, &ctx->lrT, &ctx->lrC, &ctx->lrL, &ctx->lrFlag, &ctx->lrPart, &ctx->lrPerm, &ctx->lrDen0, &ctx->eigW, &ctx->xf32, &ctx->pf32, &ctx->brSt, &ctx->brList, &ctx->illList, &ctx->qrSlab, &ctx->lodtab, &ctx->dynFac, &ctx->pvtab, &ctx->outP, &ctx->redbuf, &ctx->redtrip, &ctx->altC, &ctx->rf32, &ctx->btG, &ctx->redflag};
+                    &ctx->wbQ, &ctx->wbW, &ctx->wbRk, &ctx->lrT, &ctx->lrC, &ctx->lrL, &ctx->lrFlag, &ctx->lrPart, &ctx->lrPerm, &ctx->lrDen0, &ctx->eigW, &ctx->xf32, &ctx->pf32, &ctx->brSt, &ctx->brList, &ctx->illList, &ctx->qrSlab, &ctx->lodtab, &ctx->dynFac, &ctx->pvtab, &ctx->outP, &ctx->redbuf, &ctx->redtrip, &ctx->altC, &ctx->rf32, &ctx->btG, &ctx->redflag, &ctx->bperm};
   for (DevBuf* b : bufs) if (b->p) hipFree(b->p);
   for (auto& s : ctx->evsets) for (auto& e : s.e) (void)hipEventDestroy(e);
   if (ctx->side) { (void)hipStreamSynchronize(ctx->side); (void)hipStreamDestroy(ctx->side); }
@@ -924,6 +925,7 @@ static const struct { const char* key; int kind; size_t off; double lo, hi; } kT
   {"lr_split", 1, offsetof(blmm::Tuning, lr_split), -1, 1},
   {"eigen_solver", 1, offsetof(blmm::Tuning, eigen_solver), 0, 2},
   {"f32_rotation", 1, offsetof(blmm::Tuning, f32_rotation), 0, 1},
+  {"bulk_perm_cols", 1, offsetof(blmm::Tuning, bulk_perm_cols), 0, 2147483647.0},
 };
 int blmm_set_tuning(blmm_ctx* ctx, const char* key, double value) {
   if (!ctx) return BLMM_ERR_INVALID;
@@ -1833,6 +1835,141 @@ int blmm_scan_perms_f32(blmm_ctx* ctx, const blmm_opts* opts, const double* y, i
                         const int32_t* perm_idx, double* scalars_out, double* lod_out, float* Lperms_out, blmm_status* status) {
   return scan_perms_host(ctx, opts, y, n, G, p, Covar, ncov, K, weights, nperms, seed, perm_idx, scalars_out, lod_out,
                          Lperms_out, true, status);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The permutation test of every trait (include/bulklmm_hip.h: blmm_bulkscan_perms): the bulk null fit, then trait chunks of
+// panel columns (kernels_bperm.hip) through the table kernel's reduce-in-epilogue instantiation -- its slot partials and
+// k_red_final give every column's maximum exactly as k_colmax on the stored column would -- and the per-trait summary.
+struct BpermOut {
+  double *h2, *sigma2, *lod_max; int64_t* lod_argmax; double *max_perms, *thr, *pval;
+};
+static int bperm_check(blmm_ctx* ctx, const blmm_opts* opts, int64_t n, int64_t m, int64_t p, const double* Covar, int64_t ncov,
+                       int64_t nperms, const double* probs, int64_t nprobs, bool have_in, const BpermOut& o) {
+  int rc = check_opts(ctx, opts);
+  if (rc) return rc;
+  if (nperms < 0) return fail(ctx, BLMM_ERR_NPERMS, "The required number of permutations must be a positive integer.");
+  if (!have_in || !o.h2 || !o.sigma2 || !o.lod_max || !o.lod_argmax) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_perms: NULL buffer");
+  if (nprobs < 0 || nprobs > 64 || (nprobs > 0 && !probs)) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_perms: 0 .. 64 threshold levels");
+  if (n < 1 || m < 0 || p < 0 || ncov < 0 || m > 0x7fffffffLL || p > 0x7fffffffLL) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
+  if (nperms > BPERM_MAX_NPERMS)
+    return fail(ctx, BLMM_ERR_UNSUPPORTED, "bulkscan_perms: more than 16384 permutations (the per-trait sort runs in LDS)");
+  const int64_t c = (ncov == 0 || !Covar) ? 1 : ncov + (opts->add_intercept ? 1 : 0);
+  if (c > CTPL) return fail(ctx, BLMM_ERR_UNSUPPORTED, "bulkscan_perms: more than 8 null covariates (incl. intercept) are not supported");
+  return BLMM_OK;
+}
+
+static int bulk_perms_impl(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG, int64_t p,
+                           const double* dCovar, int64_t ncov, const double* dK, const double* dweights, int64_t nperms, uint64_t seed,
+                           const int32_t* dperm_idx, const double* probs, int64_t nprobs, const BpermOut& o, blmm_status* status) {
+  int rc = bperm_check(ctx, opts, n, m, p, dCovar, ncov, nperms, probs, nprobs, dY && dG && dK, o);
+  if (rc) return rc;
+  BLMM_HIP(hipSetDevice(ctx->device));
+  if ((rc = check_sticky(ctx))) return rc;
+  BpermProbs pr;
+  for (int t = 0; t < 64; ++t) pr.v[t] = t < nprobs ? probs[t] : 0.0;
+  Timer tm(ctx);
+  Pipe P;
+  ctx->perm_ready = false;
+  ctx->last_L = nullptr;                        // no matrix of this call (and the workspace it sat in is reused)
+  // the traits are rotated as scan rotates its one (launch_rotate picks its kernel by the column count as well as by n)
+  if ((rc = prepare(ctx, opts, dY, n, 0, dG, p, dCovar, ncov, dK, dweights, 1, P, tm))) return rc;
+  P.m = m; P.ldy = round_up(m > 0 ? m : 1, 128);
+  if ((rc = ensure(ctx, ctx->Yt, sizeof(double) * (size_t)P.npad * P.ldy))) return rc;
+  P.Yt = ptr<double>(ctx->Yt);
+  if ((rc = launch_rotate_single(ctx, ptr<double>(ctx->Rp), P.ldr, P.n, P.npad, dY, m, P.Yt, P.ldy))) return rc;
+  const NullModel nm = null_model(P, opts);
+  if (m > 0 && (rc = launch_brent(ctx, nm, P.Yt, P.ldy, m, P.Z0, P.lam, o.h2, o.sigma2, nullptr, P.stat))) return rc;
+  tm.mark();
+  const int32_t* perm = dperm_idx;
+  if (m > 0 && nperms > 0 && !perm) {
+    if ((rc = launch_perm_gen(ctx, (int)n, nperms, seed))) return rc;
+    ctx->perm_ready = false;                    // consumed here, not by a later launch_perm_panel
+    perm = ptr<int32_t>(ctx->perm);
+  }
+  // Chunks of whole traits.  Per panel column: its k-major panel (npad doubles), its reduction partials (nslot x 12 bytes), bin,
+  // maximum and marker; per trait: its row of marker norms, r0 and the panel coefficients.  Default budget 4 GiB of workspace.
+  const int64_t np1 = nperms + 1;
+  const int nslot = 2 * (int)((p + 127) / 128);
+  const double col_bytes = 8.0 * P.npad + 12.0 * nslot + 20.0 + 8.0 * (CMAX + 1);
+  const double trait_bytes = np1 * col_bytes + 8.0 * (double)P.ldx + 8.0 * n;
+  int64_t mt_max = ctx->tune.bulk_perm_cols > 0 ? ctx->tune.bulk_perm_cols / np1 : (int64_t)((double)(4ll << 30) / trait_bytes);
+  mt_max = std::max<int64_t>(1, std::min<int64_t>(mt_max, 65535));
+  for (int64_t j0 = 0; j0 < m; j0 += mt_max) {
+    const int64_t mt = std::min(mt_max, m - j0), ncols = mt * np1, ldp = round_up(ncols, 128), ldm = round_up(ncols, 64);
+    if ((rc = ensure(ctx, ctx->panels, sizeof(double) * (size_t)P.npad * ldp)) ||
+        (rc = ensure(ctx, ctx->isx, sizeof(double) * (size_t)P.ldx * mt)) ||
+        (rc = ensure(ctx, ctx->redbuf, (sizeof(double) + sizeof(int)) * (size_t)nslot * (size_t)ldm)) ||
+        (rc = ensure(ctx, ctx->bperm, (sizeof(double) + sizeof(int64_t) + sizeof(int)) * (size_t)ldp))) return rc;
+    double* mx = ptr<double>(ctx->bperm);
+    int64_t* arg = reinterpret_cast<int64_t*>(mx + ldp);
+    int* bin = reinterpret_cast<int*>(arg + ldp);
+    const double* h2c = o.h2 + j0;
+    if (p > 0 && (rc = launch_isx(ctx, nm, P.Xt, P.ldx, p, P.Z0, P.lam, h2c, (int)mt, ptr<double>(ctx->isx), P.ldx, P.stat))) return rc;
+    if ((rc = launch_bperm_panels(ctx, nm, P.Yt + j0, P.ldy, P.Z0, P.lam, h2c, mt, perm, nperms, ptr<double>(ctx->panels), ldp, bin, P.stat))) return rc;
+    if (p > 0) {
+      RedArgs r;
+      r.pmax = ptr<double>(ctx->redbuf); r.parg = reinterpret_cast<int*>(r.pmax + (size_t)nslot * ldm); r.ldm = ldm;
+      ScanArgs a = scan_args(ctx, P, ptr<double>(ctx->panels), ldp, nullptr, 0, ncols);
+      a.isx = ptr<double>(ctx->isx); a.ld_isx = P.ldx; a.bin = bin;
+      a.Pv = nullptr; a.red = r;
+      if ((rc = launch_scan_table(ctx, a)) || (rc = launch_red_final(ctx, r, nslot, ncols, mx, arg))) return rc;
+    } else {                                    // no markers: every column's maximum is -inf at marker -1 (k_colmax's empty column)
+      if ((rc = fill(ctx, mx, ncols, -INFINITY))) return rc;
+      BLMM_HIP(hipMemsetAsync(arg, 0xff, sizeof(int64_t) * (size_t)ncols, ctx->stream));
+    }
+    if ((rc = launch_bperm_summary(ctx, mx, arg, mt, nperms, pr, (int)nprobs, j0, o.lod_max, o.lod_argmax, o.max_perms, o.thr, o.pval))) return rc;
+  }
+  tm.mark();
+  return end_call(ctx, P, status, &tm);
+}
+
+int blmm_bulkscan_perms_dev(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG, int64_t p,
+                            const double* dCovar, int64_t ncov, const double* dK, const double* dweights, int64_t nperms,
+                            uint64_t seed, const int32_t* dperm_idx, const double* probs, int64_t nprobs, double* dh2_out,
+                            double* dsigma2_out, double* dlod_max_out, int64_t* dlod_argmax_out, double* dmax_perms_out,
+                            double* dthr_out, double* dpval_out, blmm_status* status) {
+  if (!ctx) return BLMM_ERR_INVALID;
+  const BpermOut o{dh2_out, dsigma2_out, dlod_max_out, dlod_argmax_out, dmax_perms_out, dthr_out, dpval_out};
+  return bulk_perms_impl(ctx, opts, dY, n, m, dG, p, dCovar, ncov, dK, dweights, nperms, seed, dperm_idx, probs, nprobs, o, status);
+}
+
+int blmm_bulkscan_perms(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, int64_t n, int64_t m, const double* G, int64_t p,
+                        const double* Covar, int64_t ncov, const double* K, const double* weights, int64_t nperms, uint64_t seed,
+                        const int32_t* perm_idx, const double* probs, int64_t nprobs, double* h2_out, double* sigma2_out,
+                        double* lod_max_out, int64_t* lod_argmax_out, double* max_perms_out, double* thr_out, double* pval_out,
+                        blmm_status* status) {
+  if (!ctx) return BLMM_ERR_INVALID;
+  const BpermOut ho{h2_out, sigma2_out, lod_max_out, lod_argmax_out, max_perms_out, thr_out, pval_out};
+  int rc = bperm_check(ctx, opts, n, m, p, Covar, ncov, nperms, probs, nprobs, Y && G && K, ho);
+  if (rc) return rc;
+  // caller-supplied permutations are indices into the trait's n entries: checked here, before a kernel reads through them
+  if (perm_idx && nperms > 0)
+    for (int64_t e = 0; e < n * nperms; ++e)
+      if (perm_idx[e] < 0 || perm_idx[e] >= n) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_perms: perm_idx entries must lie in 0 .. n - 1");
+  HostCall hc(ctx);
+  // device outputs in outL: h2, sigma2, lod_max, lod_argmax (m each), pval (m), thresholds (nprobs x m), max_perms (nperms x m)
+  const size_t mm = (size_t)m;
+  if ((rc = hc.begin()) || (rc = ensure(ctx, ctx->outL, sizeof(double) * (mm * (5 + (size_t)nprobs + (size_t)nperms) + 1)))) return rc;
+  double* d = ptr<double>(ctx->outL);
+  const BpermOut o{d, d + mm, d + 2 * mm, reinterpret_cast<int64_t*>(d + 3 * mm), max_perms_out ? d + (5 + nprobs) * mm : nullptr,
+                   thr_out ? d + 5 * mm : nullptr, pval_out ? d + 4 * mm : nullptr};
+  const double *dCov, *dW;
+  if ((rc = hc.up(ctx->inY, Y, sizeof(double) * n * m)) || (rc = hc.up(ctx->inG, G, sizeof(double) * n * p)) ||
+      (rc = hc.up(ctx->inK, K, sizeof(double) * n * n)) || (rc = hc.up_opt(ctx->inCov, Covar, n * ncov, &dCov)) ||
+      (rc = hc.up_opt(ctx->inW, weights, n, &dW))) return rc;
+  const int32_t* dperm = nullptr;
+  if (perm_idx && nperms > 0) {
+    if ((rc = hc.up(ctx->tmpC, perm_idx, sizeof(int32_t) * (size_t)n * nperms))) return rc;
+    dperm = ptr<int32_t>(ctx->tmpC);
+  }
+  if ((rc = bulk_perms_impl(ctx, opts, ptr<double>(ctx->inY), n, m, ptr<double>(ctx->inG), p, dCov, dCov ? ncov : 0, ptr<double>(ctx->inK),
+                            dW, nperms, seed, dperm, probs, nprobs, o, status))) return rc;
+  if ((rc = hc.down(h2_out, o.h2, sizeof(double) * mm)) || (rc = hc.down(sigma2_out, o.sigma2, sizeof(double) * mm)) ||
+      (rc = hc.down(lod_max_out, o.lod_max, sizeof(double) * mm)) || (rc = hc.down(lod_argmax_out, o.lod_argmax, sizeof(int64_t) * mm)) ||
+      (rc = hc.down(pval_out, o.pval, sizeof(double) * mm)) || (rc = hc.down(thr_out, o.thr, sizeof(double) * mm * nprobs))) return rc;
+  if (max_perms_out && (rc = copy_to_host(ctx, max_perms_out, o.max_perms, sizeof(double) * mm * nperms))) return rc;
+  return (rc = hc.finish()) ? rc : check_sticky(ctx);
 }
 
 // ---------------------------------------------------------------------------------------------------

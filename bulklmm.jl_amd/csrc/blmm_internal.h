@@ -54,6 +54,7 @@ struct Tuning {
   int lr_split = -1;            // -1: split the h2 search into two panel regions from 8192 traits on; 0 / 1: never / always
   int f32_rotation = 1;         // fp32 permutation path (blmm_scan_perms_f32, c <= 3): 1 = rotate G on the fp32 matrix cores straight into k_scan_f32's operand layout; 0 = fp64 rotation + conversion (round 3)
   int eigen_solver = 0;         // 0: by n (fast path + Jacobi up to 124, tridiagonalisation + divide and conquer beyond); 1: Jacobi; 2: divide and conquer
+  int bulk_perm_cols = 0;       // blmm_bulkscan_perms: largest trait chunk in panel columns (traits x (nperms + 1)); 0: from the memory budget
 };
 
 struct DevBuf {
@@ -97,7 +98,7 @@ struct blmm_ctx {
   std::string err;
   // grow-only workspace
   blmm::DevBuf Ks, V, lam, U, Zs, Z0, Rp, Yt, Xt, panels, iyy, h2, h2idx, sig2, ell, isx, stat, gridd, misc, EllTab,
-      inY, inG, inK, inCov, inW, outL, outH2, tmpA, tmpB, tmpC, perm, r0, altbuf, logtab, lraw, wbQ, wbW, wbRk, lrT, lrC, lrL, lrFlag, lrPart, lrPerm, lrDen0, eigW, xf32, pf32, brSt, brList, illList, qrSlab, lodtab, dynFac, pvtab, outP, redbuf, redtrip, altC, rf32, btG, redflag;
+      inY, inG, inK, inCov, inW, outL, outH2, tmpA, tmpB, tmpC, perm, r0, altbuf, logtab, lraw, wbQ, wbW, wbRk, lrT, lrC, lrL, lrFlag, lrPart, lrPerm, lrDen0, eigW, xf32, pf32, brSt, brList, illList, qrSlab, lodtab, dynFac, pvtab, outP, redbuf, redtrip, altC, rf32, btG, redflag, bperm;
   // event sets: one per timed call since the last blmm_read_timings (grown on demand, reused afterwards)
   struct EvSet { hipEvent_t e[8]; int n; };
   std::vector<EvSet> evsets;
@@ -235,6 +236,8 @@ int launch_post_eigen(blmm_ctx* ctx, const double* lraw, const double* V, const 
 // Out (row-major, npad x ldo) = R * In  (In column-major n x ncols); pads with zeros up to ncols_pad / npad.
 int launch_rotate(blmm_ctx* ctx, const double* Rp, int ldr, int n, int npad, const double* In, int64_t ncols,
                   double* Out, int64_t ldo, int64_t ncols_pad);
+// launch_rotate's arithmetic for ONE column (scan's trait), applied to ncols columns; Out padded with zeros up to ldo columns
+int launch_rotate_single(blmm_ctx* ctx, const double* Rp, int ldr, int n, int npad, const double* In, int64_t ncols, double* Out, int64_t ldo);
 // row-major (npad x ld) -> column-major (n x ncols)
 int launch_untranspose(blmm_ctx* ctx, const double* In, int64_t ld, int n, int64_t ncols, double* Out);
 
@@ -421,6 +424,18 @@ struct AltArgs {
 };
 int launch_scan_alt(blmm_ctx* ctx, const AltArgs& a);
 int launch_alt_ctab(blmm_ctx* ctx, const double* EllTab, int ngrid, int64_t m, int n, double* C);
+// kernels_bperm.hip: blmm_bulkscan_perms.  Panel columns of the chunk's mt traits (Yt, h2c: the chunk's first trait), column
+// jj (nperms + 1) + b = trait jj under permutation b - 1 of perm (n x nperms; b = 0: unpermuted), bin[column] = jj; c <= CTPL
+int launch_bperm_panels(blmm_ctx* ctx, const NullModel& nm, const double* Yt, int64_t ldy, const double* Z0, const double* lam,
+                        const double* h2c, int64_t mt, const int32_t* perm, int64_t nperms, double* panel, int64_t ldp, int* bin,
+                        int64_t* stat);
+// quantile levels of the thresholds, passed by value (at most 64, as blmm_get_thresholds)
+struct BpermProbs { double v[64]; };
+// per trait of the chunk: peak and marker, the permutation maxima (max_perms: nperms x m, ld = nperms), thresholds (nprobs x m,
+// ld = nprobs) and the empirical p-value (max_perms / thr / pval may be null)
+int launch_bperm_summary(blmm_ctx* ctx, const double* mx, const int64_t* arg, int64_t mt, int64_t nperms, const BpermProbs& probs,
+                         int nprobs, int64_t j0, double* lod_max, int64_t* lod_argmax, double* max_perms, double* thr, double* pval);
+constexpr int BPERM_MAX_NPERMS = 16384;   // k_bperm_summary sorts a trait's maxima in LDS (128 KB)
 
 }  // namespace blmm
 

@@ -1119,6 +1119,55 @@ int launch_rotate(blmm_ctx* ctx, const double* Rp, int ldr, int n, int npad, con
   return BLMM_OK;
 }
 
+// k_rotate_vec's arithmetic for many columns at once (column = first + blockIdx.y): blmm_bulkscan_perms rotates its traits the way
+// scan rotates its single one, so that a trait's rotated values -- and everything behind them -- are scan's bit for bit
+__global__ void __launch_bounds__(256) k_rotate_vec_cols(const double* __restrict__ Rp, int ldr, int n, int npad,
+                                                         const double* __restrict__ In, int64_t first, double* __restrict__ Out,
+                                                         int64_t ldo) {
+  __shared__ double s_acc[4][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int k = blockIdx.x * 64 + lane;
+  const int64_t col = first + blockIdx.y;
+  const double* x = In + col * (int64_t)n;
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+  const int kc = (k < npad) ? k : 0;
+  int i = wave;
+  for (; i + 28 < n; i += 32) {
+    double r[8], xv[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) { r[u] = Rp[(size_t)(i + 4 * u) * ldr + kc]; xv[u] = x[i + 4 * u]; }
+    a0 = fma(r[0], xv[0], a0); a1 = fma(r[1], xv[1], a1); a2 = fma(r[2], xv[2], a2); a3 = fma(r[3], xv[3], a3);
+    a0 = fma(r[4], xv[4], a0); a1 = fma(r[5], xv[5], a1); a2 = fma(r[6], xv[6], a2); a3 = fma(r[7], xv[7], a3);
+  }
+  for (; i < n; i += 4) a0 = fma(Rp[(size_t)i * ldr + kc], x[i], a0);
+  const double acc = (k < npad) ? (a0 + a1) + (a2 + a3) : 0.0;
+  s_acc[wave][lane] = acc;
+  __syncthreads();
+  if (wave == 0 && k < npad) Out[(int64_t)k * ldo + col] = (s_acc[0][lane] + s_acc[1][lane]) + (s_acc[2][lane] + s_acc[3][lane]);
+}
+
+// The rotation launch_rotate gives ONE column (scan's trait), for ncols columns: k_rotate_vec's form beyond n = 256, else the
+// k_rotate form (whose columns do not depend on the call's width); pads Out's columns up to ldo with zeros
+int launch_rotate_single(blmm_ctx* ctx, const double* Rp, int ldr, int n, int npad, const double* In, int64_t ncols, double* Out, int64_t ldo) {
+  if (ncols <= 0) return BLMM_OK;
+  if (n <= 256) {
+    constexpr int MBLK = 5;
+    const int nrb = (npad + 15) / 16;
+    dim3 grid((unsigned)((ldo + 63) / 64), (unsigned)((nrb + MBLK - 1) / MBLK));
+    hipLaunchKernelGGL(k_rotate<MBLK>, grid, dim3(256), 0, ctx->stream, Rp, ldr, n, npad, In, ncols, Out, ldo, ldo);
+    KCHECK();
+    return BLMM_OK;
+  }
+  BLMM_HIP(hipMemsetAsync(Out, 0, sizeof(double) * (size_t)npad * ldo, ctx->stream));
+  for (int64_t c0 = 0; c0 < ncols; c0 += 65535) {
+    const int64_t nc = std::min<int64_t>(65535, ncols - c0);
+    hipLaunchKernelGGL(k_rotate_vec_cols, dim3((unsigned)((npad + 63) / 64), (unsigned)nc), dim3(256), 0, ctx->stream, Rp, ldr, n, npad,
+                       In, c0, Out, ldo);
+  }
+  KCHECK();
+  return BLMM_OK;
+}
+
 __global__ void k_untranspose(const double* __restrict__ In, int64_t ld, int n, int64_t ncols, double* __restrict__ Out) {
   __shared__ double tile[32][33];
   const int64_t c0 = (int64_t)blockIdx.x * 32;

@@ -11,7 +11,7 @@
 # every `ccall`'s symbol, return type and argument tuple (arity and types) against the prototype in include/bulklmm_hip.h.
 module BulkLMMHIP
 
-export bulkscan_reduced, bulkscan_reduced_async!, synchronize, DeviceLOD, lod_columns, set_tuning, calcKinship, bulkscan, bulkscan_null, bulkscan_null_grid, bulkscan_alt_grid, bulkscan_alt_exact, scan, bulkscan_multi, lod2log10p, get_thresholds,
+export bulkscan_perms, bulkscan_reduced, bulkscan_reduced_async!, synchronize, DeviceLOD, lod_columns, set_tuning, calcKinship, bulkscan, bulkscan_null, bulkscan_null_grid, bulkscan_alt_grid, bulkscan_alt_exact, scan, bulkscan_multi, lod2log10p, get_thresholds,
        lod_threshold, lod_colmax, pinned_matrix, host_register, host_unregister
 
 const libblmm = get(ENV, "BULKLMM_HIP_LIB", joinpath(@__DIR__, "..", "csrc", "libbulklmm_hip.so"))
@@ -552,6 +552,37 @@ function get_thresholds(L_perms::Array{Float64, 2}, signif_level::Array{Float64,
         (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64}),
         context(), L_perms, size(L_perms, 1), size(L_perms, 2), probs, length(probs), thrs))
     return (probs = probs, thrs = thrs)
+end
+
+# The permutation test for EVERY trait (blmm_bulkscan_perms): per trait scan(Y[:, j], ...; permutation_test = true) under ONE
+# permutation set (the library's generator from rndseed), reduced on the device -- peak, genome-wide permutation maxima,
+# get_thresholds and the empirical p-value; lod_argmax is 1-based here (0 = no comparable LOD).
+function bulkscan_perms(Y::Array{Float64, 2}, G::Array{Float64, 2}, Covar::Union{Nothing, Array{Float64, 2}}, K::Array{Float64, 2};
+                        nperms::Int64 = 1024, rndseed::Int64 = 0, signif_level::Array{Float64, 1} = [0.10, 0.05],
+                        weights::Union{Missing, Array{Float64, 1}} = missing, prior_variance::Float64 = 0.0,
+                        prior_sample_size::Float64 = 0.0, addIntercept::Bool = true, reml::Bool = false,
+                        optim_interval::Int64 = 1, decomp_scheme::String = "eigen")
+    n, m = size(Y); p = size(G, 2)
+    (size(G, 1) != n || size(K, 1) != n || size(K, 2) != n || (Covar !== nothing && size(Covar, 1) != n)) && error("Dimension mismatch.")
+    check_n(n)
+    (weights !== missing && length(weights) != n) && error("Dimension mismatch.")
+    nperms < 0 && error("The required number of permutations must be a positive integer.")
+    o = BlmmOpts(NULL_EXACT, reml, addIntercept, decomp(decomp_scheme), optim_interval, 0, prior_variance, prior_sample_size)
+    probs = 1.0 .- signif_level
+    h2 = Array{Float64, 1}(undef, m); s2 = similar(h2); mx = similar(h2); pv = similar(h2)
+    arg = Array{Int64, 1}(undef, m)
+    mp = Array{Float64, 2}(undef, max(nperms, 1), m); thr = Array{Float64, 2}(undef, length(probs), m)
+    st = BlmmStatus()
+    ncov = Covar === nothing ? 0 : size(Covar, 2)
+    GC.@preserve Y G Covar K weights probs h2 s2 mx arg mp thr pv check(ccall((:blmm_bulkscan_perms, libblmm), Cint,
+        (Ptr{Cvoid}, Ref{BlmmOpts}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64},
+         Ptr{Float64}, Int64, UInt64, Ptr{Int32}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{BlmmStatus}),
+        context(), o, Y, n, m, G, p, ptr_or_null(Covar), ncov, K, ptr_or_null(weights), nperms, UInt64(rndseed), C_NULL, probs,
+        length(probs), h2, s2, mx, arg, mp, thr, pv, st))
+    raise_status(st)
+    return (h2_null = h2, sigma2_e = s2, lod_max = mx, lod_argmax = arg .+ 1, max_perms = mp[1:nperms, :],
+            thresholds = thr, pvals_perm = pv)
 end
 
 # ---- on-device consumers of L (README.md:246-255, 354-359) -------------------------------------------------------------

@@ -157,6 +157,8 @@ int blmm_synchronize(blmm_ctx* ctx);
  *   "eigen_solver"    0      0 = by n; 1 = Jacobi; 2 = tridiagonalisation + divide and conquer
  *   "f32_rotation"    1      blmm_scan_perms_f32 with an intercept-only null model: 1 = the marker rotation runs on the fp32 matrix
  *                            cores as well; 0 = fp64 rotation, converted (0.2.2)
+ *   "bulk_perm_cols"  0      blmm_bulkscan_perms: largest trait chunk in panel columns (0: sized by the workspace budget); results do
+ *                            not depend on it
  *   "defaults"               (set only) every key back to its default
  * Every setting gives results within the library's stated tolerances; they exist for tests and for A/B measurements. */
 int blmm_set_tuning(blmm_ctx* ctx, const char* key, double value);
@@ -370,6 +372,36 @@ int blmm_scan_perms_f32_dev(blmm_ctx* ctx, const blmm_opts* opts, const double* 
                             int64_t p, const double* dCovar, int64_t ncov, const double* dK, const double* dweights,
                             int64_t nperms, uint64_t seed, const int32_t* dperm_idx, double* dscalars_out,
                             double* dlod_out, float* dLperms_out, blmm_status* status);
+
+/* ---- the permutation test for EVERY trait of a bulk call: genome-wide thresholds and p-values per trait -----------------
+ * For each trait j of Y (n x m) the reference's scan_perms_lite (src/scan.jl:485-557) under the trait's own null heritability,
+ * reduced on the device -- the p x m x nperms LOD tensor is never written.  ONE permutation set serves every trait: perm_idx
+ * (n x nperms int32, 0-based, as blmm_scan_perms; entries in 0 .. n - 1) or, NULL, the library's generator seeded by `seed`.  So
+ * trait j equals blmm_scan_perms(Y[:, j], same nperms / seed / perm_idx) bit for bit, and the correlation between traits within a
+ * permutation is kept.  Null model as blmm_scan_perms (opts: reml, prior, optim_interval, add_intercept, decomp_scheme; Covar,
+ * weights); 1 .. 8 null covariates incl. the intercept (more: BLMM_ERR_UNSUPPORTED); nperms 0 .. 16384 (more: BLMM_ERR_UNSUPPORTED;
+ * < 0: BLMM_ERR_NPERMS); probs: nprobs (0 .. 64) quantile levels in HOST memory, 1 - signif_level as for blmm_get_thresholds.
+ * Outputs (m each unless stated):
+ *   h2_out, sigma2_out    the null fit (scan's h2_null, sigma2_e)
+ *   lod_max_out           peak of the unpermuted LOD column; lod_argmax_out its marker (0-based, lowest on ties, NaN never the
+ *                         maximum; -inf / -1 for a column without a comparable LOD, as blmm_lod_colmax)
+ *   max_perms_out         nperms x m (ld = nperms): genome-wide maximum LOD of every permuted copy (or NULL)
+ *   thr_out               nprobs x m (ld = nprobs): blmm_get_thresholds of the trait's permutation matrix (or NULL)
+ *   pval_out              (1 + #{k : max_perms[k, j] >= lod_max[j]}) / (nperms + 1), a -inf maximum never counted (or NULL)
+ *   nperms = 0: thresholds and p-values are NaN.
+ * Traits run in chunks of at most 65535 traits, sized by a 4 GiB workspace budget (tuning key "bulk_perm_cols": the largest chunk
+ * in panel columns, traits x (nperms + 1); 0 = the budget).  blmm_bulkscan_perms_dev: device pointers (probs still host), ordered
+ * on the context's stream; with a status it synchronises, as blmm_scan_perms_dev.  The host form synchronises. */
+int blmm_bulkscan_perms(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, int64_t n, int64_t m, const double* G, int64_t p,
+                        const double* Covar, int64_t ncov, const double* K, const double* weights, int64_t nperms, uint64_t seed,
+                        const int32_t* perm_idx, const double* probs, int64_t nprobs, double* h2_out, double* sigma2_out,
+                        double* lod_max_out, int64_t* lod_argmax_out, double* max_perms_out, double* thr_out, double* pval_out,
+                        blmm_status* status);
+int blmm_bulkscan_perms_dev(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG, int64_t p,
+                            const double* dCovar, int64_t ncov, const double* dK, const double* dweights, int64_t nperms,
+                            uint64_t seed, const int32_t* dperm_idx, const double* probs, int64_t nprobs, double* dh2_out,
+                            double* dsigma2_out, double* dlod_max_out, int64_t* dlod_argmax_out, double* dmax_perms_out,
+                            double* dthr_out, double* dpval_out, blmm_status* status);
 
 /* ---- scan(y, G, [Z], K; assumption = "alt") -> scan_alt (src/scan.jl:397-453): the variance components are re-estimated for
  * every marker (fitlmm on [Z g_i], src/lmm.jl:56-86, one Brent search per marker on the device).
