@@ -1177,3 +1177,149 @@ def bulkscan_perms_dev(ctx: Context, Y, G, K, h2_out, sigma2_out, lod_max_out, l
                                               lod_argmax_out.data_ptr(), dp(max_perms_out), dp(thr_out), dp(pval_out),
                                               C.byref(st) if status else None))
     return st
+
+
+# ---- leave-one-chromosome-out (LOCO) ---------------------------------------------------------------------------------------------
+def chromosome_runs(chrom, p: int):
+    """(labels in run order, chr_start int64 nchr + 1) of a length-p sequence of chromosome labels whose equal values form contiguous
+    runs (the order of a genetic map).  A label that comes back after another chromosome is refused with its name."""
+    labels = list(chrom.tolist() if hasattr(chrom, "tolist") else chrom)
+    if len(labels) != p:
+        raise BulkLMMError("Dimension mismatch.", -2)
+    runs, starts, seen = [], [], set()
+    for i, lab in enumerate(labels):
+        if i == 0 or lab != labels[i - 1]:
+            if lab in seen:
+                raise BulkLMMError("chromosome %r appears again after another chromosome: the markers must be ordered by "
+                                   "chromosome (contiguous runs)" % (lab,), -1)
+            seen.add(lab)
+            runs.append(lab)
+            starts.append(i)
+    starts.append(p)
+    chr_start = np.asarray(starts, dtype=np.int64)
+    _check_chr_start(chr_start, p)
+    return runs, chr_start
+
+
+def _check_chr_start(chr_start, p: int) -> np.ndarray:
+    """The library's own offset checks (blmm_api.hip: loco_check), here before any context exists."""
+    cs = np.ascontiguousarray(np.asarray(chr_start, dtype=np.int64).ravel())
+    nchr = cs.shape[0] - 1
+    if nchr < 2:
+        raise BulkLMMError("leave-one-chromosome-out needs at least 2 chromosomes", -1)
+    if nchr > 65535:
+        raise BulkLMMError("at most 65535 chromosomes", -1)
+    if cs[0] != 0 or cs[-1] != p:
+        raise BulkLMMError("chromosome offsets must run from 0 to p", -1)
+    d = np.diff(cs)
+    if (d == 0).any():
+        raise BulkLMMError("chromosome %d is empty" % int(np.flatnonzero(d == 0)[0]), -1)
+    if (d < 0).any():
+        raise BulkLMMError("chromosome offsets are not increasing", -1)
+    if (d == p).any():
+        raise BulkLMMError("a chromosome holds every marker (no kinship is left)", -1)
+    return cs
+
+
+def calcKinship_loco(G, chrom, digits: Optional[int] = None, ctx: Optional[Context] = None) -> np.ndarray:
+    """calcKinship of every leave-one-chromosome-out genotype matrix (src/kinship.jl:4-14 on G[:, not chromosome c]), all from one
+    pass over G on the device: shape (nchr, n, n), matrix c for the c-th chromosome in run order.  `digits`: rounded as calcKinship."""
+    Gf = _F(G)
+    n, p = Gf.shape
+    _, cs = chromosome_runs(chrom, p)
+    nchr = cs.shape[0] - 1
+    ctx = ctx or default_context()
+    out = np.empty((nchr, n, n), dtype=np.float64)     # block c = matrix c, column-major
+    ctx.check(ctx.lib.blmm_kinship_loco(ctx.h, _p(Gf), n, p, _p(cs), nchr, -1 if digits is None else int(digits), _p(out)))
+    return out.transpose(0, 2, 1)
+
+
+def bulkscan_loco(Y, G, chrom, Covar=None, *, method: str = "null-grid", h2_grid=None, kinship_digits: Optional[int] = None,
+                  addIntercept: bool = True, weights=None, prior_variance: float = 1.0, prior_sample_size: float = 0.0,
+                  reml: bool = False, optim_interval: int = 1, decomp_scheme: str = "eigen", output_pvals: bool = False,
+                  chisq_df: int = 1, ctx: Optional[Context] = None, keep_on_device: bool = False,
+                  return_status: bool = False) -> dict:
+    """Leave-one-chromosome-out bulkscan (blmm_bulkscan_loco): the markers of each chromosome are scanned against the kinship of
+    all the others, so that the random effect does not absorb the QTL under test (proximal contamination).  For the c-th
+    chromosome in run order, L[rows_c] is bulkscan(Y, G[:, rows_c], calcKinship_loco(G, chrom, kinship_digits)[c]; same
+    options)["L"] bit for bit.  `chrom`: a length-p sequence of labels in contiguous runs.  Returns {"L": p x m (or a DeviceLOD),
+    "h2_null_list": nchr x m (null-* methods) or "h2_panel": p x m (alt-grid), "chromosomes": labels in run order,
+    "chr_start": nchr + 1 offsets [, "log10Pvals_mat", "Chisq_df"] [, "status"]}."""
+    if h2_grid is None:
+        h2_grid = [i / 10.0 for i in range(10)]
+    if method not in _METHODS:
+        raise BulkLMMError("Unknown method `%s`; choose null-exact, null-grid or alt-grid." % method, -5)
+    meth = _METHODS[method]
+    Y = _F(Y)
+    G = _F(G)
+    n, m = Y.shape
+    p = G.shape[1]
+    if G.shape[0] != n:
+        raise BulkLMMError("Dimension mismatch.", -2)
+    runs, cs = chromosome_runs(chrom, p)
+    nchr = cs.shape[0] - 1
+    _check_n(n)
+    cov, ncov = None, 0
+    if Covar is not None:
+        cov = _F(Covar)
+        if cov.shape[0] != n:
+            raise BulkLMMError("Dimension mismatch.", -2)
+        ncov = cov.shape[1]
+    else:
+        addIntercept = True
+    w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).ravel())
+    if w is not None and w.shape[0] != n:
+        raise BulkLMMError("Dimension mismatch.", -2)
+    grid, ngrid = None, 0
+    if meth != L.BLMM_NULL_EXACT:
+        grid = np.ascontiguousarray(np.asarray(h2_grid, dtype=np.float64).ravel())
+        ngrid = grid.shape[0]
+    o = _opts(meth, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
+    ctx = ctx or default_context()  # after the argument checks: those must not need a GPU
+    Lout = None if keep_on_device else np.empty((p, m), dtype=np.float64, order="F")
+    h2 = np.empty((p, m), order="F") if meth == L.BLMM_ALT_GRID else np.empty((nchr, m))   # row c: chromosome c's h2 (C order)
+    st = L.blmm_status()
+    ctx.check(ctx.lib.blmm_bulkscan_loco(ctx.h, C.byref(o), _p(Y), n, m, _p(G), p, _p(cs), nchr,
+                                         -1 if kinship_digits is None else int(kinship_digits), _p(cov), ncov, _p(w), _p(grid), ngrid,
+                                         _p(Lout), _p(h2), C.byref(st)))
+    _raise_status(st)
+    out = {"L": DeviceLOD(ctx, p, m) if keep_on_device else Lout, "chromosomes": runs, "chr_start": cs}
+    out["h2_panel" if meth == L.BLMM_ALT_GRID else "h2_null_list"] = h2
+    if output_pvals:
+        out["log10Pvals_mat"] = _last_log10p(ctx, (p, m), chisq_df)
+        out["Chisq_df"] = chisq_df
+    if return_status:
+        out["status"] = st
+    return out
+
+
+def bulkscan_loco_dev(ctx: Context, Y, G, chr_start, L_out, h2_out, *, method: str = "null-exact", h2_grid=None, K_loco=None,
+                      kinship_digits: Optional[int] = None, Covar=None, weights=None, addIntercept: bool = True,
+                      prior_variance: float = 1.0, prior_sample_size: float = 0.0, reml: bool = False, optim_interval: int = 1,
+                      decomp_scheme: str = "eigen", status: bool = False):
+    """blmm_bulkscan_loco_dev on torch CUDA tensors (layouts as bulkscan_dev: Y (m, n), G (p, n), L_out (m, p) with rows possibly
+    padded); chr_start: nchr + 1 host offsets; h2_out: (nchr, m) for the null-* methods, (m, p) [= p x m] for alt-grid; K_loco:
+    (nchr, n, n) as calcKinship_loco, or None (computed on the device).  Enqueues on the context's stream; status=True synchronises."""
+    m, n = Y.shape
+    p = G.shape[0]
+    cs = _check_chr_start(chr_start, p)
+    nchr = cs.shape[0] - 1
+    _check_n(n)
+    if method not in _METHODS:
+        raise BulkLMMError("Unknown method `%s`; choose null-exact, null-grid or alt-grid." % method, -5)
+    grid, ngrid = None, 0
+    if method != "null-exact":
+        grid = np.ascontiguousarray(np.asarray(h2_grid if h2_grid is not None else [i / 10.0 for i in range(10)], dtype=np.float64))
+        ngrid = grid.shape[0]
+    ncov = 0 if Covar is None else Covar.shape[0]
+    if Covar is None:
+        addIntercept = True
+    o = _opts(_METHODS[method], reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
+    st = L.blmm_status() if status else None
+    ctx.check(ctx.lib.blmm_bulkscan_loco_dev(ctx.h, C.byref(o), Y.data_ptr(), n, m, G.data_ptr(), p, _p(cs), nchr,
+                                             -1 if kinship_digits is None else int(kinship_digits),
+                                             None if Covar is None else Covar.data_ptr(), ncov,
+                                             None if weights is None else weights.data_ptr(), _p(grid), ngrid,
+                                             None if K_loco is None else K_loco.data_ptr(), L_out.data_ptr(), _ld(L_out, p),
+                                             None if h2_out is None else h2_out.data_ptr(), C.byref(st) if status else None))
+    return st

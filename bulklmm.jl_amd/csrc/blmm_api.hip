@@ -174,12 +174,9 @@ int reset_stat(blmm_ctx* ctx, int64_t** stat) {
 }
 
 // Synchronises and fills *status (only when the caller asked for it).
-int finish_status(blmm_ctx* ctx, blmm_status* st, Timer* tm) {
-  if (!st) return BLMM_OK;
+// *st from one call's status block h (on the host); fails on the device-side aborts it records
+int fill_status(blmm_ctx* ctx, const int64_t* h, blmm_status* st) {
   std::memset(st, 0, sizeof(*st));
-  int64_t h[NSTAT];
-  BLMM_HIP(hipMemcpyAsync(h, ctx->stat.p, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-  BLMM_HIP(hipStreamSynchronize(ctx->stream));
   st->n_neg_eig = h[ST_NEG_EIG];
   st->n_nonpos_weight = h[ST_NONPOS_W];
   st->n_zero_norm = h[ST_ZERO_NORM];
@@ -198,6 +195,16 @@ int finish_status(blmm_ctx* ctx, blmm_status* st, Timer* tm) {
                               ": -7 grid barrier of the tridiagonalisation timed out, -8 QL iteration limit)");
   if (ctx->hflag && *ctx->hflag) return check_sticky(ctx);
   { double r2; std::memcpy(&r2, &h[9], sizeof(double)); st->lowrank_resid = std::sqrt(r2 < 0 ? 0.0 : r2); }
+  return BLMM_OK;
+}
+
+int finish_status(blmm_ctx* ctx, blmm_status* st, Timer* tm) {
+  if (!st) return BLMM_OK;
+  int64_t h[NSTAT];
+  BLMM_HIP(hipMemcpyAsync(h, ctx->stat.p, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+  BLMM_HIP(hipStreamSynchronize(ctx->stream));
+  int rc = fill_status(ctx, h, st);
+  if (rc) return rc;
   if (tm && tm->set && tm->set->n >= 2) {
     double t[6];
     phase_times(*tm->set, t);
@@ -218,10 +225,15 @@ int end_call(blmm_ctx* ctx, const Pipe& P, blmm_status* st, Timer* tm) {
   return finish_status(ctx, st, tm);
 }
 
+// The eigen phase of one matrix done ahead by a batched launch (blmm_bulkscan_loco: launch_eig_fast_batch over the weighted kinships
+// Ks, with their own vectors, eigenvalues and status words, which the design of the call has filled and zeroed): prepare_eigen then
+// runs only what follows the fast solver -- the Jacobi behind it (a no-op when its checks passed) and the post-eigen work.
+struct EigPre { double* Ks; double* V; double* lraw; int64_t* stat; };
+
 // design -> eigen (prepare_eigen) -> rotation of Y and G (prepare_rotate).  centered = 1: the rotation also removes the
 // unweighted projection on the null covariates (kernels_prep.hip:k_post_eigen).
 int prepare_eigen(blmm_ctx* ctx, const blmm_opts* o, int64_t n, const double* dCovar, int64_t ncov, const double* dK,
-                  const double* dweights, int centered, Pipe& P, Timer& tm) {
+                  const double* dweights, int centered, Pipe& P, Timer& tm, const EigPre* pre = nullptr) {
   // whatever blmm_prepare_dev left in this context (Rp, Z0, lambda, the status block) is about to be overwritten or reallocated:
   // the *_prerotated entry points must not run on it afterwards (blmm_prepare_dev sets the flag again when IT got here)
   ctx->prep_valid = false;
@@ -234,16 +246,30 @@ int prepare_eigen(blmm_ctx* ctx, const blmm_opts* o, int64_t n, const double* dC
   if (c >= n) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
   P.n = (int)n; P.c = c; P.npad = (int)round_up(n, 8); P.ldr = (int)round_up(P.npad, 16);   // K padded to 8: even K-step count
   int rc;
-  if ((rc = ensure(ctx, ctx->Ks, sizeof(double) * n * n))) return rc;
-  if ((rc = ensure(ctx, ctx->V, sizeof(double) * (n * n + 4 * n + 16)))) return rc;
-  if ((rc = ensure(ctx, ctx->lraw, sizeof(double) * n))) return rc;
   if ((rc = ensure(ctx, ctx->U, sizeof(double) * n * n))) return rc;
   if ((rc = ensure(ctx, ctx->lam, sizeof(double) * n))) return rc;
   if ((rc = ensure(ctx, ctx->Zs, sizeof(double) * n * c))) return rc;
   if ((rc = ensure(ctx, ctx->Z0, sizeof(double) * n * c))) return rc;
   if ((rc = ensure(ctx, ctx->Rp, sizeof(double) * (size_t)P.npad * P.ldr))) return rc;
-  if ((rc = reset_stat(ctx, &P.stat))) return rc;
   P.Z0 = ptr<double>(ctx->Z0); P.lam = ptr<double>(ctx->lam);
+  if (pre) {
+    P.stat = pre->stat;
+    ctx->audit_ran = false;
+    ctx->brent_cnt_used = false;
+    P.big = n > jacobi_lds_max_n();
+    bool post_done = false;
+    tm.mark();
+    if ((rc = launch_jacobi_post(ctx, pre->Ks, pre->V, (int)n, pre->lraw, P.stat, ptr<double>(ctx->Zs), dweights, c, P.npad, P.ldr,
+                                 o->decomp_scheme, centered, P.lam, ptr<double>(ctx->U), P.Z0, ptr<double>(ctx->Rp), &post_done))) return rc;
+    if (!post_done && (rc = launch_post_eigen(ctx, pre->lraw, pre->V, ptr<double>(ctx->Zs), dweights, (int)n, c, P.npad, P.ldr,
+                                              o->decomp_scheme, centered, P.lam, ptr<double>(ctx->U), P.Z0, ptr<double>(ctx->Rp), P.stat))) return rc;
+    tm.mark();
+    return BLMM_OK;
+  }
+  if ((rc = ensure(ctx, ctx->Ks, sizeof(double) * n * n))) return rc;
+  if ((rc = ensure(ctx, ctx->V, sizeof(double) * (n * n + 4 * n + 16)))) return rc;
+  if ((rc = ensure(ctx, ctx->lraw, sizeof(double) * n))) return rc;
+  if ((rc = reset_stat(ctx, &P.stat))) return rc;
   tm.mark();
   if ((rc = launch_design(ctx, dK, dCovar, (int)ncov, add_int, dweights, (int)n, ptr<double>(ctx->Ks), ptr<double>(ctx->Zs)))) return rc;
   const double* evec = ptr<double>(ctx->V);
@@ -362,13 +388,13 @@ int rotate_markers(blmm_ctx* ctx, Pipe& P, const double* dG, int64_t p) {
 
 int prepare(blmm_ctx* ctx, const blmm_opts* o, const double* dY, int64_t n, int64_t m, const double* dG, int64_t p,
             const double* dCovar, int64_t ncov, const double* dK, const double* dweights, int centered, Pipe& P, Timer& tm,
-            bool early_wbasis = false, bool grid_side = false, bool skip_markers = false) {
+            bool early_wbasis = false, bool grid_side = false, bool skip_markers = false, const EigPre* pre = nullptr) {
   if (m < 0 || p < 0) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
   // the side streams fork where the eigen phase ends: its last kernel records the fork event itself (BLMM_LAUNCH_STOP)
   const bool forks = m > 0 && p > 0 && (early_wbasis || grid_side);
   ctx->stop_event_used = false;
   ctx->stop_event_next = forks ? ctx->ev_xt : nullptr;
-  int rc = prepare_eigen(ctx, o, n, dCovar, ncov, dK, dweights, centered, P, tm);
+  int rc = prepare_eigen(ctx, o, n, dCovar, ncov, dK, dweights, centered, P, tm, pre);
   const bool xt_recorded = ctx->stop_event_used;
   ctx->stop_event_next = nullptr; ctx->stop_event_used = false;
   if (rc) return rc;
@@ -789,7 +815,8 @@ void blmm_destroy(blmm_ctx* ctx) {
                     &ctx->iyy, &ctx->h2, &ctx->h2idx, &ctx->sig2, &ctx->ell, &ctx->isx, &ctx->stat, &ctx->gridd, &ctx->misc,
                     &ctx->EllTab, &ctx->inY, &ctx->inG, &ctx->inK, &ctx->inCov, &ctx->inW, &ctx->outL, &ctx->outH2,
                     &ctx->tmpA, &ctx->tmpB, &ctx->tmpC, &ctx->perm, &ctx->r0, &ctx->altbuf, &ctx->logtab, &ctx->lraw,
-                    &ctx->wbQ, &ctx->wbW, &ctx->wbRk, &ctx->lrT, &ctx->lrC, &ctx->lrL, &ctx->lrFlag, &ctx->lrPart, &ctx->lrPerm, &ctx->lrDen0, &ctx->eigW, &ctx->xf32, &ctx->pf32, &ctx->brSt, &ctx->brList, &ctx->illList, &ctx->qrSlab, &ctx->lodtab, &ctx->dynFac, &ctx->pvtab, &ctx->outP, &ctx->redbuf, &ctx->redtrip, &ctx->altC, &ctx->rf32, &ctx->btG, &ctx->redflag, &ctx->bperm};
+                    &ctx->wbQ, &ctx->wbW, &ctx->wbRk, &ctx->lrT, &ctx->lrC, &ctx->lrL, &ctx->lrFlag, &ctx->lrPart, &ctx->lrPerm, &ctx->lrDen0, &ctx->eigW, &ctx->xf32, &ctx->pf32, &ctx->brSt, &ctx->brList, &ctx->illList, &ctx->qrSlab, &ctx->lodtab, &ctx->dynFac, &ctx->pvtab, &ctx->outP, &ctx->redbuf, &ctx->redtrip, &ctx->altC, &ctx->rf32, &ctx->btG, &ctx->redflag, &ctx->bperm,
+                    &ctx->locoK, &ctx->locoPart, &ctx->locoChr, &ctx->locoStat, &ctx->locoKs, &ctx->locoV, &ctx->locoLraw};
   for (DevBuf* b : bufs) if (b->p) hipFree(b->p);
   for (auto& s : ctx->evsets) for (auto& e : s.e) (void)hipEventDestroy(e);
   if (ctx->side) { (void)hipStreamSynchronize(ctx->side); (void)hipStreamDestroy(ctx->side); }
@@ -1116,7 +1143,7 @@ static int isx_maybe_side(blmm_ctx* ctx, const Pipe& P, const NullModel& nm, con
 
 static int scan_pipeline(blmm_ctx* ctx, const blmm_opts* opts, Pipe& P, Timer& tm, bool lowrank, bool wbasis_started, double* dgrid,
                          const double* h2_grid_host, int64_t ngrid, double* dL_out, int64_t ldL, double* dh2_out, blmm_status* status,
-                         const PvReq& pvreq) {
+                         const PvReq& pvreq, int64_t ldH = -1) {   // ldH: leading dimension of alt-grid's h2_panel (-1: p)
   int rc;
   const int64_t m = P.m, p = P.p;
   const NullModel nm = null_model(P, opts);
@@ -1212,7 +1239,7 @@ static int scan_pipeline(blmm_ctx* ctx, const blmm_opts* opts, Pipe& P, Timer& t
     AltArgs aa;
     aa.s = scan_args(ctx, P, ptr<double>(ctx->panels), ldp, dL_out, ldL, m);
     aa.s.isx = ptr<double>(ctx->isx); aa.s.ld_isx = P.ldx;
-    aa.ngrid = (int)ngrid; aa.EllTab = ptr<double>(ctx->EllTab); aa.grid_dev = dgrid; aa.H2 = dh2_out; aa.ldH = p;
+    aa.ngrid = (int)ngrid; aa.EllTab = ptr<double>(ctx->EllTab); aa.grid_dev = dgrid; aa.H2 = dh2_out; aa.ldH = ldH < 0 ? p : ldH;
     aa.Ctab = ptr<double>(ctx->altC);
     aa.counter_quirk = (opts->compat_flags & BLMM_COMPAT_ALT_COUNTER) ? 1 : 0;
     if ((rc = launch_scan_alt(ctx, aa))) return rc;
@@ -1517,6 +1544,274 @@ int blmm_bulkscan(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, int64_t
     fprintf(stderr, "blmm_bulkscan legs (ms): uploads %.2f | enqueue %.2f | device %.2f | L to host %.2f | h2 to host + sync %.2f\n", hp1 - hp0, hp2 - hp1,
             hp3 - hp2, hp4 - hp3, now() - hp4);
   return check_sticky(ctx);   // a device-side failure of THIS call (no status passed): reported now, not by the next call
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Leave-one-chromosome-out (include/bulklmm_hip.h: blmm_kinship_loco, blmm_bulkscan_loco).  The argument checks come before anything
+// touches the device.
+static int loco_check(blmm_ctx* ctx, int64_t n, int64_t p, const int64_t* chr, int64_t nchr, const char* who) {
+  const std::string w(who);
+  if (n < 1 || p < 1) return fail(ctx, BLMM_ERR_INVALID, w + ": bad arguments");
+  if (!chr) return fail(ctx, BLMM_ERR_INVALID, w + ": chr_start is NULL");
+  if (nchr < 2) return fail(ctx, BLMM_ERR_INVALID, w + ": leave-one-chromosome-out needs at least 2 chromosomes");
+  if (nchr > 65535) return fail(ctx, BLMM_ERR_INVALID, w + ": at most 65535 chromosomes");
+  if (chr[0] != 0 || chr[nchr] != p) return fail(ctx, BLMM_ERR_INVALID, w + ": chromosome offsets must run from 0 to p");
+  for (int64_t c = 0; c < nchr; ++c) {
+    if (chr[c + 1] == chr[c]) return fail(ctx, BLMM_ERR_INVALID, w + ": chromosome " + std::to_string((long long)c) + " is empty");
+    if (chr[c + 1] < chr[c]) return fail(ctx, BLMM_ERR_INVALID, w + ": chromosome offsets are not increasing");
+    if (chr[c + 1] - chr[c] == p) return fail(ctx, BLMM_ERR_INVALID, w + ": a chromosome holds every marker (no kinship is left)");
+  }
+  return BLMM_OK;
+}
+
+// the chromosome offsets on the device (locoChr), in stream order and without waiting: the caller's array is copied into a pinned
+// slot of the context (the ring of grid_to_device's asynchronous form: a slot whose copy is still queued is left alone and the ring
+// grows instead), and the device copy is enqueued from there
+static int loco_offsets(blmm_ctx* ctx, const int64_t* chr, int64_t nchr, const int64_t** dchr) {
+  const size_t bytes = sizeof(int64_t) * (size_t)(nchr + 1);
+  int rc = ensure(ctx, ctx->locoChr, bytes);
+  if (rc) return rc;
+  blmm_ctx::GridSlot* slot = nullptr;
+  for (auto& g : ctx->gstage)
+    if (g.cap >= bytes && (!g.used || hipEventQuery(g.ev) == hipSuccess)) { slot = &g; break; }
+  if (!slot) {
+    blmm_ctx::GridSlot g;
+    g.cap = bytes < 4096 ? 4096 : bytes;
+    void* h = nullptr;
+    BLMM_HIP(hipHostMalloc(&h, g.cap, hipHostMallocDefault));
+    g.h = static_cast<double*>(h);
+    if (hipEventCreateWithFlags(&g.ev, hipEventDisableTiming) != hipSuccess) { (void)hipHostFree(h); return fail(ctx, BLMM_ERR_HIP, "hipEventCreate failed"); }
+    ctx->gstage.push_back(g);
+    slot = &ctx->gstage.back();
+  }
+  std::memcpy(slot->h, chr, bytes);
+  BLMM_HIP(hipMemcpyAsync(ctx->locoChr.p, slot->h, bytes, hipMemcpyHostToDevice, ctx->stream));
+  BLMM_HIP(hipEventRecord(slot->ev, ctx->stream));
+  slot->used = true;
+  *dchr = ptr<int64_t>(ctx->locoChr);
+  return BLMM_OK;
+}
+
+static int kinship_loco_impl(blmm_ctx* ctx, const double* dG, int64_t n, const int64_t* chr, int64_t nchr, int64_t digits, double* dK) {
+  const int64_t* dchr = nullptr;
+  const int ns = loco_kinship_splits(n, nchr);
+  int rc;
+  if ((rc = loco_offsets(ctx, chr, nchr, &dchr)) || (rc = ensure(ctx, ctx->locoPart, sizeof(double) * (size_t)nchr * ns * n * n))) return rc;
+  return launch_kinship_loco(ctx, dG, n, dchr, nchr, digits, dK, ptr<double>(ctx->locoPart), ns);
+}
+
+int blmm_kinship_loco_dev(blmm_ctx* ctx, const double* dG, int64_t n, int64_t p, const int64_t* chr_start, int64_t nchr,
+                          int64_t digits, double* dK_out) {
+  if (!ctx) return BLMM_ERR_INVALID;
+  if (!dG || !dK_out || digits > 300) return fail(ctx, BLMM_ERR_INVALID, "kinship_loco: bad arguments");
+  int rc = loco_check(ctx, n, p, chr_start, nchr, "kinship_loco");
+  if (rc) return rc;
+  BLMM_HIP(hipSetDevice(ctx->device));
+  return kinship_loco_impl(ctx, dG, n, chr_start, nchr, digits, dK_out);
+}
+
+int blmm_kinship_loco(blmm_ctx* ctx, const double* G, int64_t n, int64_t p, const int64_t* chr_start, int64_t nchr,
+                      int64_t digits, double* K_out) {
+  if (!ctx) return BLMM_ERR_INVALID;
+  if (!G || !K_out || digits > 300) return fail(ctx, BLMM_ERR_INVALID, "kinship_loco: bad arguments");
+  int rc = loco_check(ctx, n, p, chr_start, nchr, "kinship_loco");
+  if (rc) return rc;
+  HostCall hc(ctx);
+  const size_t kb = sizeof(double) * (size_t)n * n * nchr;
+  if ((rc = hc.begin()) || (rc = ensure(ctx, ctx->locoK, kb)) || (rc = hc.up(ctx->inG, G, sizeof(double) * n * p)) ||
+      (rc = kinship_loco_impl(ctx, ptr<double>(ctx->inG), n, chr_start, nchr, digits, ptr<double>(ctx->locoK))) ||
+      (rc = copy_to_host(ctx, K_out, ctx->locoK.p, kb))) return rc;
+  return hc.finish(false);
+}
+
+// The pipeline: the kinships (unless given), then per chromosome the whole bulkscan front and scan on its column block, into its rows
+// of L.  The chromosomes run largest first, so that no p-sized workspace grows -- and no buffer is freed under queued work -- after
+// the first of them; each one's status block is copied aside (locoStat) and summed once at the end.
+static int bulkscan_loco_dev_impl(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG,
+                                  int64_t p, const int64_t* chr, int64_t nchr, int64_t kdigits, const double* dCovar, int64_t ncov,
+                                  const double* dweights, const double* h2_grid_host, int64_t ngrid, const double* dK_loco,
+                                  double* dL, int64_t ldL, double* dh2, blmm_status* status, const PvReq& pvreq) {
+  int rc = check_opts(ctx, opts);
+  if (rc) return rc;
+  if (!dY || !dG || !dL || (!dh2 && opts->method != BLMM_ALT_GRID)) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_loco: NULL buffer");
+  if (opts->method != BLMM_NULL_EXACT && opts->method != BLMM_NULL_GRID && opts->method != BLMM_ALT_GRID)
+    return fail(ctx, BLMM_ERR_METHOD, "Unknown method; choose null-exact, null-grid or alt-grid.");
+  if ((rc = loco_check(ctx, n, p, chr, nchr, "bulkscan_loco"))) return rc;
+  if (m < 0 || ldL < p || kdigits > 300) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_loco: bad arguments");
+  if (n > 2048) return fail(ctx, BLMM_ERR_UNSUPPORTED, "more than 2048 individuals: the device eigensolver (tridiagonalisation + divide and conquer) stops at n = 2048");
+  BLMM_HIP(hipSetDevice(ctx->device));
+  if ((rc = check_sticky(ctx))) return rc;
+  double* dgrid = nullptr;
+  if (opts->method != BLMM_NULL_EXACT && (rc = grid_to_device(ctx, h2_grid_host, ngrid, &dgrid))) return rc;
+  // one event set for the start of the call (t_total_ms spans the kinships computed inside it, which count in no phase), one for the
+  // batched eigen phase, one per chromosome: none may be reallocated or recycled under another one's Timer
+  if (ctx->ev_used + (size_t)nchr + 2 >= 4096) ctx->ev_used = 0;
+  ctx->evsets.reserve(ctx->ev_used + (size_t)nchr + 2);
+  Timer t0(ctx);
+  t0.mark();
+  const double* dK = dK_loco;
+  if (!dK) {
+    if ((rc = ensure(ctx, ctx->locoK, sizeof(double) * (size_t)n * n * nchr)) ||
+        (rc = kinship_loco_impl(ctx, dG, n, chr, nchr, kdigits, ptr<double>(ctx->locoK)))) return rc;
+    dK = ptr<double>(ctx->locoK);
+  }
+  if ((rc = ensure(ctx, ctx->locoStat, sizeof(int64_t) * NSTAT * (size_t)nchr))) return rc;
+  int64_t* dst_all = ptr<int64_t>(ctx->locoStat);
+  std::vector<int64_t> order((size_t)nchr);
+  for (int64_t c = 0; c < nchr; ++c) order[(size_t)c] = c;
+  std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return chr[a + 1] - chr[a] > chr[b + 1] - chr[b]; });
+  Timer tb(ctx);
+  // n <= eig_fast_max_n() (the fast path is what a single call runs there): the design of every chromosome's kinship, then ONE set of
+  // eigen launches for all of them (launch_eig_fast_batch: matrix c on blockIdx.y, its own workspace and status words); each
+  // chromosome's prepare_eigen runs only the Jacobi check behind it and the post-eigen work.  Beyond: per chromosome, unbatched.
+  const bool batched = n >= 3 && n <= eig_fast_max_n() && !dev_env("BLMM_EIGEN") && ctx->tune.eigen_solver == 0;
+  const int64_t sA = round_up(n * n, 32), sE = round_up(n * n + 4 * n + 16, 32), sL = round_up(n, 32);
+  if (batched) {
+    int add_int = opts->add_intercept ? 1 : 0;
+    int64_t nc = ncov;
+    const double* cov = dCovar;
+    if (nc == 0 || !cov) { add_int = 1; nc = 0; cov = nullptr; }
+    const int64_t cc = nc + add_int;
+    if (cc < 1 || cc > CMAX) return fail(ctx, BLMM_ERR_UNSUPPORTED, BLMM_C_ERR);
+    if (cc >= n) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
+    if ((rc = ensure(ctx, ctx->locoKs, sizeof(double) * (size_t)nchr * sA)) || (rc = ensure(ctx, ctx->locoV, sizeof(double) * (size_t)nchr * sE)) ||
+        (rc = ensure(ctx, ctx->locoLraw, sizeof(double) * (size_t)nchr * sL)) || (rc = ensure(ctx, ctx->Zs, sizeof(double) * n * cc))) return rc;
+    BLMM_HIP(hipMemsetAsync(dst_all, 0, sizeof(int64_t) * NSTAT * (size_t)nchr, ctx->stream));
+    tb.mark();
+    for (int64_t c = 0; c < nchr; ++c)
+      if ((rc = launch_design(ctx, dK + (size_t)c * n * n, cov, (int)nc, add_int, dweights, (int)n, ptr<double>(ctx->locoKs) + (size_t)c * sA,
+                              ptr<double>(ctx->Zs)))) return rc;
+    if ((rc = launch_eig_fast_batch(ctx, ptr<double>(ctx->locoKs), sA, (int)n, (int)nchr, ptr<double>(ctx->locoLraw), sL,
+                                    ptr<double>(ctx->locoV), sE, dst_all, NSTAT))) return rc;
+    tb.mark();
+  }
+  std::vector<Timer> tms;
+  tms.reserve((size_t)nchr);
+  const bool alt = opts->method == BLMM_ALT_GRID;
+  const bool lowrank = wants_lowrank(ctx, opts, n, dCovar, ncov);
+  bool audit = false;
+  for (int64_t c : order) {
+    const int64_t s0 = chr[c], pc = chr[c + 1] - chr[c];
+    tms.emplace_back(ctx);
+    Timer& tm = tms.back();
+    Pipe P;
+    const EigPre pre{ptr<double>(ctx->locoKs) + (size_t)c * sA, ptr<double>(ctx->locoV) + (size_t)c * sE,
+                     ptr<double>(ctx->locoLraw) + (size_t)c * sL, dst_all + (size_t)c * NSTAT};
+    if ((rc = prepare(ctx, opts, dY, n, m, dG + (size_t)n * s0, pc, dCovar, ncov, dK + (size_t)c * n * n, dweights, 1, P, tm, lowrank,
+                      opts->method != BLMM_NULL_EXACT, false, batched ? &pre : nullptr)))
+      return rc;
+    double* h2c = alt ? (dh2 ? dh2 + s0 : nullptr) : dh2 + (size_t)c * m;
+    if (alt && !h2c) {   // the h2_panel was not asked for: the context's scratch (p x m at most, this chromosome's rows only)
+      if ((rc = ensure(ctx, ctx->outH2, sizeof(double) * (size_t)pc * (m > 0 ? m : 1)))) return rc;
+      h2c = ptr<double>(ctx->outH2);
+    }
+    if ((rc = scan_pipeline(ctx, opts, P, tm, lowrank, lowrank && m > 0, dgrid, h2_grid_host, ngrid, dL + s0, ldL, h2c, nullptr, PvReq(),
+                            (alt && dh2) ? p : pc))) return rc;
+    audit = audit || ctx->audit_ran;
+    // the next chromosome reuses every buffer this one's side-stream work reads: the main stream waits for both side streams
+    BLMM_HIP(hipEventRecord(ctx->ev_fork, ctx->side));
+    BLMM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_fork, 0));
+    BLMM_HIP(hipEventRecord(ctx->ev_fork, ctx->side2));
+    BLMM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_fork, 0));
+    if (P.stat != dst_all + (size_t)c * NSTAT)
+      BLMM_HIP(hipMemcpyAsync(dst_all + (size_t)c * NSTAT, P.stat, sizeof(int64_t) * NSTAT, hipMemcpyDeviceToDevice, ctx->stream));
+  }
+  // the context's status block is what blmm_lowrank_profile / blmm_lowrank_columns read: the last chromosome's, as after a run of
+  // single calls (the batched path kept every chromosome's block in locoStat instead)
+  if (batched && !order.empty()) {
+    if ((rc = ensure(ctx, ctx->stat, sizeof(int64_t) * NSTAT))) return rc;
+    BLMM_HIP(hipMemcpyAsync(ctx->stat.p, dst_all + (size_t)order.back() * NSTAT, sizeof(int64_t) * NSTAT, hipMemcpyDeviceToDevice, ctx->stream));
+  }
+  if (pvreq.armed && m > 0) {
+    double* Pv = pvreq.out;
+    int64_t ld = pvreq.ld;
+    if (Pv && ld < p) return fail(ctx, BLMM_ERR_INVALID, "log10p output: ldP < p");
+    if (!Pv) {
+      if ((rc = ensure(ctx, ctx->outP, sizeof(double) * (size_t)p * m))) return rc;
+      Pv = ptr<double>(ctx->outP); ld = p;
+    }
+    if ((rc = launch_lod2log10p(ctx, dL, p, m, ldL, (int)pvreq.df, Pv, ld))) return rc;
+    if (!pvreq.out) { ctx->last_P = Pv; ctx->last_P_ld = ld; ctx->last_P_df = pvreq.df; }
+  }
+  if (!status) return BLMM_OK;
+  std::vector<int64_t> h((size_t)nchr * NSTAT);
+  BLMM_HIP(hipMemcpyAsync(h.data(), dst_all, sizeof(int64_t) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
+  BLMM_HIP(hipStreamSynchronize(ctx->stream));
+  blmm_status sum;
+  std::memset(&sum, 0, sizeof(sum));
+  for (int64_t c = 0; c < nchr; ++c) {
+    blmm_status one;
+    if ((rc = fill_status(ctx, h.data() + (size_t)c * NSTAT, &one))) return rc;
+    sum.n_neg_eig += one.n_neg_eig; sum.n_nonpos_weight += one.n_nonpos_weight; sum.n_zero_norm += one.n_zero_norm;
+    sum.n_nan_lod += one.n_nan_lod; sum.n_brent_maxiter += one.n_brent_maxiter; sum.jacobi_sweeps += one.jacobi_sweeps;
+    sum.jacobi_cycles += one.jacobi_cycles; sum.jacobi_ticks_100mhz += one.jacobi_ticks_100mhz;
+    sum.lowrank_rank = std::max(sum.lowrank_rank, one.lowrank_rank);
+    sum.lowrank_fallback += one.lowrank_fallback; sum.lowrank_shared += one.lowrank_shared;
+    sum.lowrank_resid = std::max(sum.lowrank_resid, one.lowrank_resid);
+    sum.n_h2_boundary += one.n_h2_boundary; sum.n_h2_multimodal += one.n_h2_multimodal; sum.n_illcond_rescan += one.n_illcond_rescan;
+  }
+  if (!audit) sum.n_h2_multimodal = -1;
+  for (const Timer& tm : tms) {
+    if (!tm.set || tm.set->n < 2) continue;
+    double t[6];
+    phase_times(*tm.set, t);
+    sum.t_eigen_ms += t[0]; sum.t_rotate_ms += t[1]; sum.t_h2_ms += t[2]; sum.t_prep_ms += t[3]; sum.t_scan_ms += t[4];
+  }
+  if (tb.set && tb.set->n >= 2) {            // the batched eigen phase (the chromosomes' own eigen phases are their post-eigen work)
+    float te = 0;
+    (void)hipEventElapsedTime(&te, tb.set->e[0], tb.set->e[1]);
+    sum.t_eigen_ms += te;
+  }
+  if (!tms.empty() && tms.front().set && tms.back().set && tms.back().set->n >= 2) {
+    float tot = 0;
+    const hipEvent_t first = t0.set ? t0.set->e[0] : tms.front().set->e[0];
+    (void)hipEventElapsedTime(&tot, first, tms.back().set->e[tms.back().set->n - 1]);
+    sum.t_total_ms = tot;
+  }
+  *status = sum;
+  return BLMM_OK;
+}
+
+int blmm_bulkscan_loco_dev(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG, int64_t p,
+                           const int64_t* chr_start, int64_t nchr, int64_t kinship_digits, const double* dCovar, int64_t ncov,
+                           const double* dweights, const double* h2_grid, int64_t ngrid, const double* dK_loco, double* dL_out,
+                           int64_t ldL, double* dh2_out, blmm_status* status) {
+  if (!ctx) return BLMM_ERR_INVALID;
+  const PvReq pvreq = pv_take(ctx);
+  ctx->red_cur = RedArgs();
+  if (ncov == 0) dCovar = nullptr;
+  return bulkscan_loco_dev_impl(ctx, opts, dY, n, m, dG, p, chr_start, nchr, kinship_digits, dCovar, dCovar ? ncov : 0, dweights, h2_grid,
+                                ngrid, dK_loco, dL_out, ldL, dh2_out, status, pvreq);
+}
+
+int blmm_bulkscan_loco(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, int64_t n, int64_t m, const double* G, int64_t p,
+                       const int64_t* chr_start, int64_t nchr, int64_t kinship_digits, const double* Covar, int64_t ncov,
+                       const double* weights, const double* h2_grid, int64_t ngrid, double* L_out, double* h2_out,
+                       blmm_status* status) {
+  if (!ctx) return BLMM_ERR_INVALID;
+  const PvReq pvreq = pv_take(ctx);
+  if (!opts) return fail(ctx, BLMM_ERR_INVALID, "opts is NULL");
+  const bool alt = opts->method == BLMM_ALT_GRID;
+  if (!Y || !G || (!h2_out && !alt)) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_loco: NULL buffer");
+  if (m < 0 || ncov < 0) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
+  int rc = loco_check(ctx, n, p, chr_start, nchr, "bulkscan_loco");
+  if (rc) return rc;
+  if (n > 2048) return fail(ctx, BLMM_ERR_UNSUPPORTED, "more than 2048 individuals: the device eigensolver (tridiagonalisation + divide and conquer) stops at n = 2048");
+  HostCall hc(ctx);
+  const size_t h2_elems = alt ? (size_t)p * m : (size_t)m * nchr;
+  const double *dCov, *dW;
+  if ((rc = hc.begin()) || (rc = ensure(ctx, ctx->outL, sizeof(double) * (size_t)p * m)) || (rc = ensure(ctx, ctx->outH2, sizeof(double) * h2_elems)) ||
+      (rc = hc.up(ctx->inY, Y, sizeof(double) * n * m)) || (rc = hc.up(ctx->inG, G, sizeof(double) * n * p)) ||
+      (rc = hc.up_opt(ctx->inCov, Covar, n * ncov, &dCov)) || (rc = hc.up_opt(ctx->inW, weights, n, &dW))) return rc;
+  ctx->red_cur = RedArgs();
+  if ((rc = bulkscan_loco_dev_impl(ctx, opts, ptr<double>(ctx->inY), n, m, ptr<double>(ctx->inG), p, chr_start, nchr, kinship_digits, dCov,
+                                   dCov ? ncov : 0, dW, h2_grid, ngrid, nullptr, ptr<double>(ctx->outL), p,
+                                   (alt && !h2_out) ? nullptr : ptr<double>(ctx->outH2), status, pvreq))) return rc;
+  ctx->last_L = ptr<double>(ctx->outL); ctx->last_p = p; ctx->last_m = m; ctx->last_f32 = false;
+  if (L_out && (size_t)p * m > 0 && (rc = copy_to_host(ctx, L_out, ctx->outL.p, sizeof(double) * (size_t)p * m))) return rc;
+  if (h2_out && h2_elems > 0 && (rc = copy_to_host(ctx, h2_out, ctx->outH2.p, sizeof(double) * h2_elems))) return rc;
+  if ((rc = hc.finish())) return rc;
+  return check_sticky(ctx);
 }
 
 // host-pointer form of the reduce-in-epilogue scan: `out` holds HOST pointers; the small results come back, nothing p x m moves

@@ -98,7 +98,8 @@ struct blmm_ctx {
   std::string err;
   // grow-only workspace
   blmm::DevBuf Ks, V, lam, U, Zs, Z0, Rp, Yt, Xt, panels, iyy, h2, h2idx, sig2, ell, isx, stat, gridd, misc, EllTab,
-      inY, inG, inK, inCov, inW, outL, outH2, tmpA, tmpB, tmpC, perm, r0, altbuf, logtab, lraw, wbQ, wbW, wbRk, lrT, lrC, lrL, lrFlag, lrPart, lrPerm, lrDen0, eigW, xf32, pf32, brSt, brList, illList, qrSlab, lodtab, dynFac, pvtab, outP, redbuf, redtrip, altC, rf32, btG, redflag, bperm;
+      inY, inG, inK, inCov, inW, outL, outH2, tmpA, tmpB, tmpC, perm, r0, altbuf, logtab, lraw, wbQ, wbW, wbRk, lrT, lrC, lrL, lrFlag, lrPart, lrPerm, lrDen0, eigW, xf32, pf32, brSt, brList, illList, qrSlab, lodtab, dynFac, pvtab, outP, redbuf, redtrip, altC, rf32, btG, redflag, bperm,
+      locoK, locoPart, locoChr, locoStat, locoKs, locoV, locoLraw;   // blmm_kinship_loco / blmm_bulkscan_loco (kernels_loco.hip)
   // event sets: one per timed call since the last blmm_read_timings (grown on demand, reused afterwards)
   struct EvSet { hipEvent_t e[8]; int n; };
   std::vector<EvSet> evsets;
@@ -227,6 +228,9 @@ int launch_jacobi_post(blmm_ctx* ctx, double* A, double* V, int n, double* lraw,
 int launch_eig_dc(blmm_ctx* ctx, const double* A, int n, double* lraw, double* evec, int64_t* stat);
 int eig_dc_max_n(const blmm_ctx* ctx);
 int launch_eig_fast(blmm_ctx* ctx, const double* A, int n, double* lraw, double* evec, int64_t* stat);
+// ... for nb matrices in one set of launches (batch on blockIdx.y): matrix b at A + b sA -> lraw + b sL, evec + b sE, stat + b sS
+int launch_eig_fast_batch(blmm_ctx* ctx, const double* A, int64_t sA, int n, int nb, double* lraw, int64_t sL, double* evec, int64_t sE,
+                          int64_t* stat, int64_t sS);
 int eig_fast_max_n();
 int jacobi_lds_max_n();
 // lambda (ascending, or |lambda| descending for svd), U sorted, Z0 = U' Zs, Rp = (centered ? Q U' Wd : U' Wd)'
@@ -277,6 +281,11 @@ int launch_panels(blmm_ctx* ctx, const NullModel& nm, const double* Yt, int64_t 
 int launch_isx(blmm_ctx* ctx, const NullModel& nm, const double* Xt, int64_t ldx, int64_t p, const double* Z0,
                const double* lam, const double* grid_dev, int ngrid, double* isx, int64_t ld_isx, int64_t* stat);
 int launch_kinship(blmm_ctx* ctx, const double* dG, int64_t n, int64_t p, double* dK, double* partial);
+// kernels_loco.hip: the nchr leave-one-chromosome-out kinships (n x n each, stacked) from one pass over G; dchr = the nchr + 1
+// chromosome offsets on the device; partial: nchr * nsplit * n * n doubles, nsplit from loco_kinship_splits
+int loco_kinship_splits(int64_t n, int64_t nchr);
+int launch_kinship_loco(blmm_ctx* ctx, const double* dG, int64_t n, const int64_t* dchr, int64_t nchr, int64_t digits, double* dK,
+                        double* partial, int nsplit);
 int launch_colmax(blmm_ctx* ctx, const double* L, int64_t p, int64_t m, int64_t ldL, double* mx, int64_t* arg);
 // kernels_post.hip
 int launch_lod2log10p(blmm_ctx* ctx, const double* dL, int64_t p, int64_t m, int64_t ldL, int df, double* dP, int64_t ldP);

@@ -969,11 +969,20 @@ __host__ __device__ inline size_t bt_lds_staged(int NR, int n) {
   return sizeof(double) * ((size_t)n * (n | 1) + 128 + (size_t)BT_RB * bt_groups(n) * 64 * NR + 16 * (size_t)bt_groups(n));
 }
 
+// matrix blockIdx.y of a batch (launch_eig_fast_batch): V, tau and Zc_chk lie in its workspace block (w doubles apart), G, Z and the
+// status words g, z and s apart.  One matrix: BtBatch{}.
+struct BtBatch { int64_t w = 0, g = 0, z = 0, s = 0; };
 template <int NR, int CPW, int NT>
 __global__ void __launch_bounds__(NT) k_backtransform(const double* __restrict__ V, const double* __restrict__ tau,
                                                        const double* __restrict__ G, int n, double* __restrict__ Z, const double* __restrict__ Zc_chk,
-                                                       int64_t* __restrict__ stat_chk, int stage_v) {
+                                                       int64_t* __restrict__ stat_chk, int stage_v, BtBatch bb) {
   extern __shared__ __attribute__((aligned(16))) double sh[];
+  {
+    const int64_t bi = blockIdx.y;
+    V += bi * bb.w; tau += bi * bb.w; G += bi * bb.g; Z += bi * bb.z;
+    if (Zc_chk) Zc_chk += bi * bb.w;
+    if (stat_chk) stat_chk += bi * bb.s;
+  }
   constexpr int RB = BT_RB, LDR = 64 * NR;
   constexpr size_t BUF = (size_t)RB * LDR + 16;     // one group: RB padded reflectors, then tau_0..3 and the six inner products
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = NT >> 6;
@@ -1474,9 +1483,11 @@ __host__ __device__ inline EigfWs eigf_ws(double* base, int n) {
   return q;
 }
 
+// (batched over matrices on blockIdx.y: matrix b's A, workspace block and status words are sA, sW, sS further on; one matrix: 0)
 __global__ void __launch_bounds__(1024) k_eigf_reduce(const double* __restrict__ A, int n, double* __restrict__ Vg, double* __restrict__ wsb,
-                                                      int64_t* stat) {
+                                                      int64_t* stat, int64_t sA, int64_t sW, int64_t sS) {
   extern __shared__ __attribute__((aligned(16))) double sh[];
+  { const int64_t bi = blockIdx.y; A += bi * sA; Vg += bi * sW; wsb += bi * sW; stat += bi * sS; }
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   __shared__ double s_sc[4];
   SmallWs w = {};
@@ -1522,7 +1533,9 @@ __global__ void __launch_bounds__(1024) k_eigf_reduce(const double* __restrict__
 
 template <int NT>
 __global__ void __launch_bounds__(NT) k_eigf_pairs(int n, const double* __restrict__ wsb, double* __restrict__ lam_out,
-                                                    int64_t* stat, const double* __restrict__ Vg, double* __restrict__ G) {
+                                                    int64_t* stat, const double* __restrict__ Vg, double* __restrict__ G,
+                                                    int64_t sW, int64_t sL, int64_t sS, int64_t sG) {
+  { const int64_t bi = blockIdx.y; wsb += bi * sW; Vg += bi * sW; lam_out += bi * sL; stat += bi * sS; G += bi * sG; }
   __shared__ double sd[128], se[128], sds[128], ses2[128], sDp[128], sDm[128];
   __shared__ double s_red[8];
   __shared__ int s_cnt[2][NT / 64];
@@ -1663,32 +1676,53 @@ int eig_dc_max_n(const blmm_ctx*) { return 2048; }
 // whether the result stands (stat[ST_EIG_FAST] = 1: it ran; stat[ST_EIG_BAD]: largest check / bound as the bits of a double, accepted
 // up to 1.0); the caller launches the Jacobi behind it, which returns at once when it does.
 int eig_fast_max_n() { return 124; }
-int launch_eig_fast(blmm_ctx* ctx, const double* A, int n, double* lraw, double* evec, int64_t* stat) {
+// nb matrices at once (launch_eig_fast_batch): matrix b is A + b sA, its eigenvalues go to lraw + b sL, its vectors to evec + b sE and
+// its checks to stat + b sS; each gets its own workspace block in eigW and btG.  Per matrix the arithmetic is the single launch's
+// (a pointer offset on blockIdx.y): the eigenpairs are bit-identical to launch_eig_fast on the same matrix.
+static int eig_fast_impl(blmm_ctx* ctx, const double* A, int64_t sA, int n, int nb, double* lraw, int64_t sL, double* evec, int64_t sE,
+                         int64_t* stat, int64_t sS) {
+  if (nb < 1 || nb > 65535) return fail(ctx, BLMM_ERR_UNSUPPORTED, "eig_fast: 1 .. 65535 matrices per batched launch");
   if (n < 3 || n > eig_fast_max_n()) return BLMM_ERR_UNSUPPORTED;
   int rc;
-  if ((rc = ensure(ctx, ctx->eigW, sizeof(double) * ((size_t)2 * n * n + (size_t)5 * n + 8) + 256))) return rc;
+  const size_t w1 = (size_t)2 * n * n + (size_t)5 * n + 8;
+  const int64_t sW = nb > 1 ? round_up((int64_t)w1 + 32, 32) : 0;            // (+ the 256 bytes of slack of the single form)
+  if ((rc = ensure(ctx, ctx->eigW, nb > 1 ? sizeof(double) * (size_t)nb * sW : sizeof(double) * w1 + 256))) return rc;
   const size_t lds = sizeof(double) * ((size_t)n * n + (size_t)9 * n + 8 * 128 + 16) + 64;
   if (lds > 158 * 1024) return BLMM_ERR_UNSUPPORTED;
   double* Vg = ptr<double>(ctx->eigW);
   double* wsb = Vg + (size_t)n * n;
   const EigfWs g = eigf_ws(wsb, n);
   BLMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_eigf_reduce), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k_eigf_reduce, dim3(1), dim3(1024), lds, ctx->stream, A, n, Vg, wsb, stat);
+  hipLaunchKernelGGL(k_eigf_reduce, dim3(1, nb), dim3(1024), lds, ctx->stream, A, n, Vg, wsb, stat, sA, sW, sS);
   KCHECK();
   // (256 threads: 512 / 1024 per workgroup -- more points per round, fewer rounds -- measured 0.265 / 0.286 ms of eigen phase against
   // 0.256: the waves sharing a SIMD slow each other's dependent chains)
-  if ((rc = ensure(ctx, ctx->btG, sizeof(double) * 8 * (size_t)bt_groups(n)))) return rc;
+  const int64_t sG = nb > 1 ? round_up((int64_t)8 * bt_groups(n), 32) : 0;
+  if ((rc = ensure(ctx, ctx->btG, nb > 1 ? sizeof(double) * (size_t)nb * sG : sizeof(double) * 8 * (size_t)bt_groups(n)))) return rc;
   double* btG = ptr<double>(ctx->btG);
-  hipLaunchKernelGGL(k_eigf_pairs<256>, dim3(n + (bt_groups(n) + 3) / 4), dim3(256), 0, ctx->stream, n, (const double*)wsb, lraw, stat, (const double*)Vg, btG);
+  hipLaunchKernelGGL(k_eigf_pairs<256>, dim3(n + (bt_groups(n) + 3) / 4, nb), dim3(256), 0, ctx->stream, n, (const double*)wsb, lraw, stat,
+                     (const double*)Vg, btG, sW, sL, sS, sG);
   KCHECK();
   static const bool bt_stage_off = dev_env("BLMM_BT_STAGE") && dev_env("BLMM_BT_STAGE")[0] == '0';
   const int stage_v = (bt_lds_staged(2, n) <= 158 * 1024 && !bt_stage_off) ? 1 : 0;
   const size_t lds_bt = stage_v ? bt_lds_staged(2, n) : bt_lds_chk(2, n);
   BLMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_backtransform<2, 1, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bt));
-  hipLaunchKernelGGL((k_backtransform<2, 1, 256>), dim3((n + 3) / 4), dim3(256), lds_bt, ctx->stream, Vg, g.tau, (const double*)btG, n, evec, (const double*)g.Zc, stat, stage_v);
+  BtBatch bb;
+  bb.w = sW; bb.g = sG; bb.z = sE; bb.s = sS;
+  hipLaunchKernelGGL((k_backtransform<2, 1, 256>), dim3((n + 3) / 4, nb), dim3(256), lds_bt, ctx->stream, Vg, g.tau, (const double*)btG, n, evec,
+                     (const double*)g.Zc, stat, stage_v, bb);
   KCHECK();
   ctx->eig_plan_n = -1;    // the workspace was reused: a cached merge tree of the multi-workgroup solver is gone
   return BLMM_OK;
+}
+
+int launch_eig_fast(blmm_ctx* ctx, const double* A, int n, double* lraw, double* evec, int64_t* stat) {
+  return eig_fast_impl(ctx, A, 0, n, 1, lraw, 0, evec, 0, stat, 0);
+}
+
+int launch_eig_fast_batch(blmm_ctx* ctx, const double* A, int64_t sA, int n, int nb, double* lraw, int64_t sL, double* evec, int64_t sE,
+                          int64_t* stat, int64_t sS) {
+  return eig_fast_impl(ctx, A, sA, n, nb, lraw, sL, evec, sE, stat, sS);
 }
 
 // Eigen-decomposition of the symmetric n x n matrix A (device, not modified): lraw ascending, evec[i*n + r].
@@ -1864,14 +1898,14 @@ int launch_eig_dc(blmm_ctx* ctx, const double* A, int n, double* lraw, double* e
       constexpr int NRW = (NR <= 16) ? NR : 16;                                                                            \
       const int cols_per_wg = 8 * CPWW;                                                                                    \
       if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_backtransform<NRW, CPWW, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-      hipLaunchKernelGGL((k_backtransform<NRW, CPWW, 512>), dim3((n + cols_per_wg - 1) / cols_per_wg), dim3(512), lds, ctx->stream, V, tau, (const double*)btG, n, Qin, (const double*)nullptr, (int64_t*)nullptr, 0); \
+      hipLaunchKernelGGL((k_backtransform<NRW, CPWW, 512>), dim3((n + cols_per_wg - 1) / cols_per_wg), dim3(512), lds, ctx->stream, V, tau, (const double*)btG, n, Qin, (const double*)nullptr, (int64_t*)nullptr, 0, BtBatch{}); \
     } else if (bt_cpw2 && NR <= 16) {      /* two columns per wave, 8 per workgroup: half the LDS reads and L2 fetches per column */ \
       constexpr int NRW = (NR <= 16) ? NR : 16;                                                                            \
       if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_backtransform<NRW, 2, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-      hipLaunchKernelGGL((k_backtransform<NRW, 2, 256>), dim3((n + 7) / 8), dim3(256), lds, ctx->stream, V, tau, (const double*)btG, n, Qin, (const double*)nullptr, (int64_t*)nullptr, 0);   \
+      hipLaunchKernelGGL((k_backtransform<NRW, 2, 256>), dim3((n + 7) / 8), dim3(256), lds, ctx->stream, V, tau, (const double*)btG, n, Qin, (const double*)nullptr, (int64_t*)nullptr, 0, BtBatch{});   \
     } else {                                                                                                               \
       if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_backtransform<NR, 1, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-      hipLaunchKernelGGL((k_backtransform<NR, 1, 256>), dim3((n + 3) / 4), dim3(256), lds, ctx->stream, V, tau, (const double*)btG, n, Qin, (const double*)nullptr, (int64_t*)nullptr, 0);   \
+      hipLaunchKernelGGL((k_backtransform<NR, 1, 256>), dim3((n + 3) / 4), dim3(256), lds, ctx->stream, V, tau, (const double*)btG, n, Qin, (const double*)nullptr, (int64_t*)nullptr, 0, BtBatch{});   \
     }                                                                                                                      \
   } while (0)
     if (nr <= 2) BT(2); else if (nr <= 4) BT(4); else if (nr <= 8) BT(8); else if (nr <= 16) BT(16); else if (nr <= 24) BT(24); else BT(32);

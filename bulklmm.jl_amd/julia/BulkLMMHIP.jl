@@ -11,7 +11,7 @@
 # every `ccall`'s symbol, return type and argument tuple (arity and types) against the prototype in include/bulklmm_hip.h.
 module BulkLMMHIP
 
-export bulkscan_perms, bulkscan_reduced, bulkscan_reduced_async!, synchronize, DeviceLOD, lod_columns, set_tuning, calcKinship, bulkscan, bulkscan_null, bulkscan_null_grid, bulkscan_alt_grid, bulkscan_alt_exact, scan, bulkscan_multi, lod2log10p, get_thresholds,
+export calcKinship_loco, bulkscan_loco, bulkscan_perms, bulkscan_reduced, bulkscan_reduced_async!, synchronize, DeviceLOD, lod_columns, set_tuning, calcKinship, bulkscan, bulkscan_null, bulkscan_null_grid, bulkscan_alt_grid, bulkscan_alt_exact, scan, bulkscan_multi, lod2log10p, get_thresholds,
        lod_threshold, lod_colmax, pinned_matrix, host_register, host_unregister
 
 const libblmm = get(ENV, "BULKLMM_HIP_LIB", joinpath(@__DIR__, "..", "csrc", "libbulklmm_hip.so"))
@@ -654,6 +654,69 @@ function calcKinship(G::Array{Float64, 2}, digits::Integer)
     check(ccall((:blmm_kinship_rounded, libblmm), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}),
                 context(), G, n, p, digits, K))
     return K
+end
+
+
+# ---- leave-one-chromosome-out: markers ordered by chromosome, `chrom` the label of each (contiguous runs) ----------------------
+function chromosome_runs(chrom::AbstractVector, p::Integer)
+    length(chrom) == p || error("Dimension mismatch.")
+    runs = Any[]; starts = Int64[]
+    for i in 1:p
+        if i == 1 || chrom[i] != chrom[i - 1]
+            chrom[i] in runs && error("chromosome $(chrom[i]) appears again after another chromosome: the markers must be ordered by chromosome (contiguous runs)")
+            push!(runs, chrom[i]); push!(starts, i - 1)
+        end
+    end
+    push!(starts, p)
+    length(runs) >= 2 || error("leave-one-chromosome-out needs at least 2 chromosomes")
+    return runs, starts
+end
+
+# calcKinship(G[:, not chromosome c]) for every chromosome c, from one pass over G: n x n x nchr
+function calcKinship_loco(G::Array{Float64, 2}, chrom::AbstractVector; digits::Integer = -1)
+    n, p = size(G)
+    _, cs = chromosome_runs(chrom, p)
+    nchr = length(cs) - 1
+    K = Array{Float64, 3}(undef, n, n, nchr)
+    GC.@preserve G cs K check(ccall((:blmm_kinship_loco, libblmm), Cint,
+                                    (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ptr{Int64}, Int64, Int64, Ptr{Float64}),
+                                    context(), G, n, p, cs, nchr, digits, K))
+    return K
+end
+
+# rows of chromosome c = bulkscan(Y, G[:, rows_c], calcKinship_loco(G, chrom)[:, :, c]; same options).L
+function bulkscan_loco(Y::Array{Float64, 2}, G::Array{Float64, 2}, chrom::AbstractVector;
+                       Covar::Union{Nothing, Array{Float64, 2}} = nothing, method::String = "null-grid",
+                       h2_grid::Array{Float64, 1} = collect(0.0:0.1:0.9), kinship_digits::Integer = -1,
+                       addIntercept::Bool = true, weights::Union{Missing, Array{Float64, 1}} = missing,
+                       prior_variance::Float64 = 1.0, prior_sample_size::Float64 = 0.0, reml::Bool = false,
+                       optim_interval::Int64 = 1, decomp_scheme::String = "eigen", keep_on_device::Bool = false)
+    (n, m) = size(Y); p = size(G, 2)
+    size(G, 1) != n && error("Dimension mismatch.")
+    runs, cs = chromosome_runs(chrom, p)
+    nchr = length(cs) - 1
+    check_n(n)
+    (Covar !== nothing && size(Covar, 1) != n) && error("Dimension mismatch.")
+    (weights !== missing && length(weights) != n) && error("Dimension mismatch.")
+    meth = method == "null-exact" ? NULL_EXACT : method == "null-grid" ? NULL_GRID : method == "alt-grid" ? ALT_GRID :
+           error("Unknown method `$method`; choose null-exact, null-grid or alt-grid.")
+    ncov = Covar === nothing ? 0 : size(Covar, 2)
+    o = BlmmOpts(meth, reml, Covar === nothing ? true : addIntercept, decomp(decomp_scheme), optim_interval, 0,
+                 prior_variance, prior_sample_size)
+    L = keep_on_device ? nothing : Array{Float64, 2}(undef, p, m)
+    h2 = meth == ALT_GRID ? Array{Float64, 2}(undef, p, m) : Array{Float64, 2}(undef, m, nchr)   # column c: chromosome c
+    st = BlmmStatus()
+    GC.@preserve Y G cs Covar weights h2_grid L h2 begin
+        check(ccall((:blmm_bulkscan_loco, libblmm), Cint,
+                    (Ptr{Cvoid}, Ref{BlmmOpts}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Int64}, Int64, Int64,
+                     Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ref{BlmmStatus}),
+                    context(), o, Y, n, m, G, p, cs, nchr, kinship_digits, ptr_or_null(Covar), ncov, ptr_or_null(weights),
+                    h2_grid, length(h2_grid), ptr_or_null(L), h2, st))
+    end
+    raise_status(st)
+    Lr = keep_on_device ? DeviceLOD(p, m) : L
+    return meth == ALT_GRID ? (L = Lr, h2_panel = h2, chromosomes = runs, chr_start = cs) :
+                              (L = Lr, h2_null_list = permutedims(h2), chromosomes = runs, chr_start = cs)
 end
 
 end # module

@@ -195,6 +195,19 @@ int blmm_kinship_dev(blmm_ctx* ctx, const double* dG, int64_t n, int64_t p, doub
 /* round.(calcKinship(G), digits = d) on the device, the convention of README.md:176-181 and test/generate_test_bxdData.jl:14
  * (Julia / NumPy: round(x * 10^d) / 10^d, ties to even); digits < 0: no rounding */
 int blmm_kinship_rounded(blmm_ctx* ctx, const double* G, int64_t n, int64_t p, int64_t digits, double* K_out);
+/* Leave-one-chromosome-out kinships: the markers of G (n x p) form nchr >= 2 contiguous chromosomes, chromosome c being columns
+ * chr_start[c] .. chr_start[c + 1] - 1 (chr_start: nchr + 1 HOST int64 entries, 0 = chr_start[0] < chr_start[1] < .. <
+ * chr_start[nchr] = p).  K_out (n x n x nchr; matrix c at K_out + c n n) gets calcKinship(G[:, not chromosome c]):
+ * 2 (sum over d != c of S_d) / (p - p_c) + 1/2, diagonal 1, with S_d = X_d X_d' (X = G - 1/2) -- all of them from ONE pass over G
+ * (one kinship's worth of FMAs), the other chromosomes' blocks summed in a fixed order (no S - S_c, no atomics).  digits >= 0:
+ * each matrix rounded as blmm_kinship_rounded; < 0: not rounded.  Bad offsets (an empty chromosome, not increasing from 0 to p,
+ * nchr < 2 or > 65535): BLMM_ERR_INVALID before anything is uploaded.  Workspace besides the output: the per-chromosome partial
+ * sums, at most the larger of 256 MiB and the output's own size (nchr n^2 doubles).  The _dev form: device G / K_out, enqueued on
+ * the context's stream without waiting for it (the offsets go through a pinned staging slot of the context). */
+int blmm_kinship_loco(blmm_ctx* ctx, const double* G, int64_t n, int64_t p, const int64_t* chr_start, int64_t nchr,
+                      int64_t digits, double* K_out);
+int blmm_kinship_loco_dev(blmm_ctx* ctx, const double* dG, int64_t n, int64_t p, const int64_t* chr_start, int64_t nchr,
+                          int64_t digits, double* dK_out);
 
 /* ---- bulkscan(Y, G, [Covar], K; ...)  (src/bulkscan.jl:81-162, 188-314, 321-397, 428-526) --
  * Y n x m, G n x p, Covar n x ncov (NULL/0 = none: the intercept is the only null covariate),
@@ -402,6 +415,38 @@ int blmm_bulkscan_perms_dev(blmm_ctx* ctx, const blmm_opts* opts, const double* 
                             uint64_t seed, const int32_t* dperm_idx, const double* probs, int64_t nprobs, double* dh2_out,
                             double* dsigma2_out, double* dlod_max_out, int64_t* dlod_argmax_out, double* dmax_perms_out,
                             double* dthr_out, double* dpval_out, blmm_status* status);
+
+/* ---- leave-one-chromosome-out (LOCO) bulkscan -----------------------------------------------------------------------------
+ * The markers of chromosome c (columns chr_start[c] .. chr_start[c + 1] - 1 of G; chr_start as for blmm_kinship_loco) are scanned
+ * against the kinship of every OTHER chromosome: for each c, rows chr_start[c] .. of L are
+ *   blmm_bulkscan(Y, G[:, chromosome c], K_{-c}; same opts / Covar / weights / grid).L
+ * bit for bit, with K_{-c} = blmm_kinship_loco(G, chr_start, kinship_digits)[c].  Y, G, Covar and the weights go up once; the
+ * kinships come from one pass over G; then every chromosome runs the bulkscan pipeline on its column block (design, eigen,
+ * rotation, h2, panels, scan) into its rows of ONE p x m L.  The chromosomes share the context's workspace and run one after the
+ * other in stream order; no host synchronisation between them.
+ *   L_out      p x m, or NULL: L stays resident in the context (blmm_last_dims = (p, m), blmm_last_lod_colmax, .._threshold,
+ *              .._columns, blmm_last_log10p see the whole genome)
+ *   h2_out     null-* methods: nchr blocks of m (block c = chromosome c's h2_null_list, at h2_out + c m); alt-grid: the p x m
+ *              h2_panel (may be NULL then, as for blmm_bulkscan)
+ *   status     summed over the chromosomes (counts and phase times; lowrank_rank and lowrank_resid: the largest).  t_eigen_ms
+ *              holds the batched eigen phase (n <= 124) and every chromosome's post-eigen work; t_total_ms spans the whole
+ *              call, including kinships computed inside it, which count in no phase.  blmm_lowrank_profile /
+ *              blmm_lowrank_columns afterwards describe the last chromosome run (the chromosomes run largest first).
+ * Refused with BLMM_ERR_INVALID before anything is uploaded: nchr < 2 or > 65535, an empty chromosome, offsets not increasing
+ * from 0 to p, a chromosome holding every marker; n > 2048 as blmm_bulkscan.  A pending blmm_set_log10p_output request is
+ * honoured by a column pass over the finished L.
+ * The _dev form: device Y / G / Covar / weights, dK_loco (n x n x nchr as blmm_kinship_loco_dev writes it) or NULL: computed with
+ * kinship_digits; dL_out p x m with leading dimension ldL >= p; dh2_out as h2_out (the alt-grid h2_panel with leading dimension p).
+ * It enqueues on the context's stream and waits for it only for a status and, as blmm_bulkscan_dev does, to copy the null-grid /
+ * alt-grid h2_grid out of host memory. */
+int blmm_bulkscan_loco(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, int64_t n, int64_t m, const double* G, int64_t p,
+                       const int64_t* chr_start, int64_t nchr, int64_t kinship_digits, const double* Covar, int64_t ncov,
+                       const double* weights, const double* h2_grid, int64_t ngrid, double* L_out, double* h2_out,
+                       blmm_status* status);
+int blmm_bulkscan_loco_dev(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG, int64_t p,
+                           const int64_t* chr_start, int64_t nchr, int64_t kinship_digits, const double* dCovar, int64_t ncov,
+                           const double* dweights, const double* h2_grid, int64_t ngrid, const double* dK_loco, double* dL_out,
+                           int64_t ldL, double* dh2_out, blmm_status* status);
 
 /* ---- scan(y, G, [Z], K; assumption = "alt") -> scan_alt (src/scan.jl:397-453): the variance components are re-estimated for
  * every marker (fitlmm on [Z g_i], src/lmm.jl:56-86, one Brent search per marker on the device).
