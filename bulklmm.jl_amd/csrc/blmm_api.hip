@@ -25,7 +25,7 @@ int fail(blmm_ctx* ctx, int code, const std::string& msg) {
 int ensure(blmm_ctx* ctx, DevBuf& b, size_t bytes) {
   // whoever asks for the output buffer is about to overwrite (or reallocate) it: the blmm_last_* consumers must not see the
   // previous call's matrix through it.  The entry points set last_L again once their own result is in place.
-  if (&b == &ctx->outL) ctx->last_L = nullptr;
+  if (&b == &ctx->outL) clear_last(ctx);
   if (&b == &ctx->outL || &b == &ctx->outP) ctx->last_P = nullptr;
   if (bytes == 0) bytes = 8;
   if (b.cap >= bytes) return BLMM_OK;
@@ -92,12 +92,12 @@ __global__ void k_to_rowmajor(const double* __restrict__ In, int n, int64_t ncol
 }
 
 // Copies the device-side "gave up" conditions of a call into the context's pinned host word (system-scope store):
-// bit 0: the multi-workgroup weight-basis kernel timed out at its grid barrier (stat[8] < 0);
-// bit 1: the eigensolver gave up (stat[11]: -7 grid barrier of the tridiagonalisation timed out, -8 QL iteration limit).
+// bit 0: the multi-workgroup weight-basis kernel timed out at its grid barrier (stat[ST_LR_RANK] < 0);
+// bit 1: the eigensolver gave up (stat[ST_EIG_ABORT]: -7 grid barrier of the tridiagonalisation timed out, -8 QL iteration limit).
 __global__ void k_sticky(const int64_t* __restrict__ stat, int64_t* hflag) {
   int64_t f = 0;
-  if (stat[8] < 0) f |= 1;
-  if (stat[11] != 0) { f |= 2; hflag[1] = stat[11]; }      // the code itself: -7 / -8, the own solver's aborts
+  if (stat[ST_LR_RANK] < 0) f |= 1;
+  if (stat[ST_EIG_ABORT] != 0) { f |= 2; hflag[1] = stat[ST_EIG_ABORT]; }      // the code itself: -7 / -8, the own solver's aborts
   if (f) __hip_atomic_fetch_or(hflag, f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
@@ -116,6 +116,21 @@ int check_sticky(blmm_ctx* ctx) {
   return fail(ctx, BLMM_ERR_HIP, "a call failed on the device: the eigensolver did not converge (code " + std::to_string(code) +
                                  ": -7 grid barrier of the tridiagonalisation timed out, -8 QL iteration limit)");
 }
+
+// The prologue of every device entry point once its arguments are checked: select the device, then report an earlier failure
+int enter_device(blmm_ctx* ctx) {
+  BLMM_HIP(hipSetDevice(ctx->device));
+  return check_sticky(ctx);
+}
+
+// The launchers enqueue on ctx->stream: an OnStream points it at another stream for its scope and restores it on every exit
+struct OnStream {
+  blmm_ctx* ctx; hipStream_t prev;
+  OnStream(blmm_ctx* c, hipStream_t s) : ctx(c), prev(c->stream) { c->stream = s; }
+  ~OnStream() { ctx->stream = prev; }
+  OnStream(const OnStream&) = delete;
+  OnStream& operator=(const OnStream&) = delete;
+};
 
 struct Timer {
   blmm_ctx* ctx; blmm_ctx::EvSet* set = nullptr;
@@ -163,6 +178,12 @@ int check_opts(blmm_ctx* ctx, const blmm_opts* o) {
   return BLMM_OK;
 }
 
+int check_method(blmm_ctx* ctx, const blmm_opts* o) {
+  if (o->method != BLMM_NULL_EXACT && o->method != BLMM_NULL_GRID && o->method != BLMM_ALT_GRID)
+    return fail(ctx, BLMM_ERR_METHOD, "Unknown method; choose null-exact, null-grid or alt-grid.");
+  return BLMM_OK;
+}
+
 int reset_stat(blmm_ctx* ctx, int64_t** stat) {
   int rc = ensure(ctx, ctx->stat, sizeof(int64_t) * NSTAT);
   if (rc) return rc;
@@ -183,19 +204,39 @@ int fill_status(blmm_ctx* ctx, const int64_t* h, blmm_status* st) {
   st->n_nan_lod = h[ST_NAN_LOD];
   st->n_brent_maxiter = h[ST_BRENT_MAXIT];
   st->jacobi_sweeps = h[ST_JACOBI_SWEEPS];
-  st->jacobi_cycles = h[6]; st->jacobi_ticks_100mhz = h[7];
-  st->lowrank_rank = h[8];
-  st->lowrank_fallback = h[10];
-  st->lowrank_shared = h[12] + h[14];
+  st->jacobi_cycles = h[ST_EIG_CYCLES]; st->jacobi_ticks_100mhz = h[ST_EIG_TICKS];
+  st->lowrank_rank = h[ST_LR_RANK];
+  st->lowrank_fallback = h[ST_LR_FIX];
+  st->lowrank_shared = h[ST_LR_SHARED0] + h[ST_LR_SHARED1];
   st->n_h2_boundary = h[ST_H2_BOUNDARY];
   st->n_h2_multimodal = ctx->audit_ran ? h[ST_H2_MULTIMODAL] : -1;
   st->n_illcond_rescan = h[ST_ILLCOND];
-  if (h[8] < 0) return fail(ctx, BLMM_ERR_HIP, "weight-basis kernel: a workgroup timed out at the grid barrier");
-  if (h[11] != 0) return fail(ctx, BLMM_ERR_HIP, "the eigensolver did not converge (code " + std::to_string((long long)h[11]) +
+  if (h[ST_LR_RANK] < 0) return fail(ctx, BLMM_ERR_HIP, "weight-basis kernel: a workgroup timed out at the grid barrier");
+  if (h[ST_EIG_ABORT] != 0) return fail(ctx, BLMM_ERR_HIP, "the eigensolver did not converge (code " + std::to_string((long long)h[ST_EIG_ABORT]) +
                               ": -7 grid barrier of the tridiagonalisation timed out, -8 QL iteration limit)");
   if (ctx->hflag && *ctx->hflag) return check_sticky(ctx);
-  { double r2; std::memcpy(&r2, &h[9], sizeof(double)); st->lowrank_resid = std::sqrt(r2 < 0 ? 0.0 : r2); }
+  { double r2; std::memcpy(&r2, &h[ST_LR_RESID2], sizeof(double)); st->lowrank_resid = std::sqrt(r2 < 0 ? 0.0 : r2); }
   return BLMM_OK;
+}
+
+// blmm_bulkscan_loco's sum over its chromosomes: the counts add up, the weight basis's rank and residual are the largest
+void add_status(blmm_status* sum, const blmm_status& one) {
+  sum->n_neg_eig += one.n_neg_eig; sum->n_nonpos_weight += one.n_nonpos_weight; sum->n_zero_norm += one.n_zero_norm;
+  sum->n_nan_lod += one.n_nan_lod; sum->n_brent_maxiter += one.n_brent_maxiter; sum->jacobi_sweeps += one.jacobi_sweeps;
+  sum->jacobi_cycles += one.jacobi_cycles; sum->jacobi_ticks_100mhz += one.jacobi_ticks_100mhz;
+  sum->lowrank_rank = std::max(sum->lowrank_rank, one.lowrank_rank);
+  sum->lowrank_fallback += one.lowrank_fallback; sum->lowrank_shared += one.lowrank_shared;
+  sum->lowrank_resid = std::max(sum->lowrank_resid, one.lowrank_resid);
+  sum->n_h2_boundary += one.n_h2_boundary; sum->n_h2_multimodal += one.n_h2_multimodal; sum->n_illcond_rescan += one.n_illcond_rescan;
+}
+
+// adds the phase times of one call's event set to *st; returns its total (phase_times: out[5])
+double add_phase_times(blmm_status* st, const Timer& tm) {
+  if (!tm.set || tm.set->n < 2) return 0.0;
+  double t[6];
+  phase_times(*tm.set, t);
+  st->t_eigen_ms += t[0]; st->t_rotate_ms += t[1]; st->t_h2_ms += t[2]; st->t_prep_ms += t[3]; st->t_scan_ms += t[4];
+  return t[5];
 }
 
 int finish_status(blmm_ctx* ctx, blmm_status* st, Timer* tm) {
@@ -205,12 +246,7 @@ int finish_status(blmm_ctx* ctx, blmm_status* st, Timer* tm) {
   BLMM_HIP(hipStreamSynchronize(ctx->stream));
   int rc = fill_status(ctx, h, st);
   if (rc) return rc;
-  if (tm && tm->set && tm->set->n >= 2) {
-    double t[6];
-    phase_times(*tm->set, t);
-    st->t_eigen_ms = t[0]; st->t_rotate_ms = t[1]; st->t_h2_ms = t[2]; st->t_prep_ms = t[3]; st->t_scan_ms = t[4];
-    st->t_total_ms = t[5];
-  }
+  if (tm) st->t_total_ms = add_phase_times(st, *tm);
   return BLMM_OK;
 }
 
@@ -230,6 +266,15 @@ int end_call(blmm_ctx* ctx, const Pipe& P, blmm_status* st, Timer* tm) {
 // runs only what follows the fast solver -- the Jacobi behind it (a no-op when its checks passed) and the post-eigen work.
 struct EigPre { double* Ks; double* V; double* lraw; int64_t* stat; };
 
+// The null model's covariates: none given (ncov == 0 or no matrix) is bulkscan(Y, G, K)'s intercept-only model.  c: the columns
+// incl. the intercept
+struct NullCov { const double* d; int64_t ncov; int add_int; int64_t c; };
+NullCov null_cov(const blmm_opts* o, const double* dCovar, int64_t ncov) {
+  if (ncov == 0 || !dCovar) return {nullptr, 0, 1, 1};
+  const int add_int = o->add_intercept ? 1 : 0;
+  return {dCovar, ncov, add_int, ncov + add_int};
+}
+
 // design -> eigen (prepare_eigen) -> rotation of Y and G (prepare_rotate).  centered = 1: the rotation also removes the
 // unweighted projection on the null covariates (kernels_prep.hip:k_post_eigen).
 int prepare_eigen(blmm_ctx* ctx, const blmm_opts* o, int64_t n, const double* dCovar, int64_t ncov, const double* dK,
@@ -239,9 +284,8 @@ int prepare_eigen(blmm_ctx* ctx, const blmm_opts* o, int64_t n, const double* dC
   ctx->prep_valid = false;
   if (n < 1 || ncov < 0) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
   if (n > 2048) return fail(ctx, BLMM_ERR_UNSUPPORTED, "more than 2048 individuals: the device eigensolver (tridiagonalisation + divide and conquer) stops at n = 2048");
-  int add_int = o->add_intercept ? 1 : 0;
-  if (ncov == 0 || !dCovar) { add_int = 1; ncov = 0; dCovar = nullptr; }  // bulkscan(Y,G,K): intercept-only null model
-  const int c = (int)ncov + add_int;
+  const NullCov nc = null_cov(o, dCovar, ncov);
+  const int c = (int)nc.c;
   if (c < 1 || c > CMAX) return fail(ctx, BLMM_ERR_UNSUPPORTED, BLMM_C_ERR);
   if (c >= n) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
   P.n = (int)n; P.c = c; P.npad = (int)round_up(n, 8); P.ldr = (int)round_up(P.npad, 16);   // K padded to 8: even K-step count
@@ -271,7 +315,7 @@ int prepare_eigen(blmm_ctx* ctx, const blmm_opts* o, int64_t n, const double* dC
   if ((rc = ensure(ctx, ctx->lraw, sizeof(double) * n))) return rc;
   if ((rc = reset_stat(ctx, &P.stat))) return rc;
   tm.mark();
-  if ((rc = launch_design(ctx, dK, dCovar, (int)ncov, add_int, dweights, (int)n, ptr<double>(ctx->Ks), ptr<double>(ctx->Zs)))) return rc;
+  if ((rc = launch_design(ctx, dK, nc.d, (int)nc.ncov, nc.add_int, dweights, (int)n, ptr<double>(ctx->Ks), ptr<double>(ctx->Zs)))) return rc;
   const double* evec = ptr<double>(ctx->V);
   // n <= 124: LDS Jacobi.  Beyond: the own tridiagonalisation + divide-and-conquer solver (kernels_eig.hip) up to n = 2048 (its
   // reduction keeps the matrix in LDS up to ~1450 and in L2-resident global memory beyond).  No vendor library: rocSOLVER's first
@@ -337,11 +381,14 @@ int start_wbasis(blmm_ctx* ctx, Pipe& P, const double* dG = nullptr, int64_t p =
   if ((rc = ensure(ctx, ctx->wbQ, sizeof(double) * (size_t)seg.S * P.npad * n))) return rc;
   if ((rc = ensure(ctx, ctx->wbW, sizeof(double) * (size_t)n * (256 + 16)))) return rc;
   if ((rc = ensure(ctx, ctx->wbRk, sizeof(int) * 4 * LR_SEG_MAX))) return rc;
-  hipStream_t main_stream = ctx->stream;
-  if (!xt_recorded) BLMM_HIP(hipEventRecord(ctx->ev_xt, main_stream));     // (else: recorded by the eigen phase's last kernel itself)
+  if (!xt_recorded) BLMM_HIP(hipEventRecord(ctx->ev_xt, ctx->stream));     // (else: recorded by the eigen phase's last kernel itself)
   BLMM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_xt, 0));
   ctx->wb_on_side2 = false;
-  if (dG) {
+  if (!dG) {
+    OnStream on(ctx, ctx->side);
+    return launch_wbasis(ctx, P.lam, (int)n, P.npad, seg, ptr<double>(ctx->wbW), ptr<double>(ctx->wbQ), ptr<int>(ctx->wbRk), P.stat);
+  }
+  {
     // The basis (a handful of 1024-thread workgroups, 70 us of dependent steps) goes to the SECOND side stream, beside the marker
     // rotation instead of behind it: queued behind the rotation it became dispatchable at the same moment as the h2 search,
     // whose 2,200 waves then held every CU until the first of them retired -- 126 us instead of 70, and with the marker-side
@@ -350,19 +397,15 @@ int start_wbasis(blmm_ctx* ctx, Pipe& P, const double* dG = nullptr, int64_t p =
     // on ITS stream (lr_begin: no cross-queue wait between the two, each of which costs 14-20 us here) and wait there for
     // the rotation (ev_wb), which is done long before.
     BLMM_HIP(hipStreamWaitEvent(ctx->side2, ctx->ev_xt, 0));
-    ctx->stream = ctx->side2;
-    rc = launch_wbasis(ctx, P.lam, (int)n, P.npad, seg, ptr<double>(ctx->wbW), ptr<double>(ctx->wbQ), ptr<int>(ctx->wbRk), P.stat);
-    ctx->stream = ctx->side;                                         // the launchers enqueue on ctx->stream
-    if (!rc && ctx->in_wait && hipStreamWaitEvent(ctx->side, ctx->ev_in, 0) != hipSuccess) rc = fail(ctx, BLMM_ERR_HIP, "hipStreamWaitEvent failed");
-    if (!rc) rc = rotate_markers(ctx, P, dG, p);
-    if (!rc && hipEventRecord(ctx->ev_wb, ctx->side) != hipSuccess) rc = fail(ctx, BLMM_ERR_HIP, "hipEventRecord failed");   // ev_wb: the rotated markers
     ctx->wb_on_side2 = true;
-  } else {
-    ctx->stream = ctx->side;
-    rc = launch_wbasis(ctx, P.lam, (int)n, P.npad, seg, ptr<double>(ctx->wbW), ptr<double>(ctx->wbQ), ptr<int>(ctx->wbRk), P.stat);
+    OnStream on(ctx, ctx->side2);
+    if ((rc = launch_wbasis(ctx, P.lam, (int)n, P.npad, seg, ptr<double>(ctx->wbW), ptr<double>(ctx->wbQ), ptr<int>(ctx->wbRk), P.stat))) return rc;
   }
-  ctx->stream = main_stream;
-  return rc;
+  OnStream on(ctx, ctx->side);
+  if (ctx->in_wait) BLMM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_in, 0));
+  if ((rc = rotate_markers(ctx, P, dG, p))) return rc;
+  BLMM_HIP(hipEventRecord(ctx->ev_wb, ctx->side));                  // ev_wb: the rotated markers
+  return BLMM_OK;
 }
 
 // The own rotation kernels sum every output element in a fixed order, so a trait's (or marker's) rotated column does not depend on
@@ -414,14 +457,11 @@ int prepare(blmm_ctx* ctx, const blmm_opts* o, const double* dY, int64_t n, int6
   // the grid methods (grid_side): the marker rotation and, later, the marker norms of every grid point (launch_isx) on the side stream,
   // beside the traits' rotation, the grid log-likelihoods and the trait panels on the main stream; joined in front of the scan
   if (grid_side && !early_wbasis && m > 0 && p > 0 && rot_side && n <= 160) {
-    hipStream_t main_stream = ctx->stream;
-    if (!xt_recorded) BLMM_HIP(hipEventRecord(ctx->ev_xt, main_stream));
+    if (!xt_recorded) BLMM_HIP(hipEventRecord(ctx->ev_xt, ctx->stream));
     BLMM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_xt, 0));
     if (ctx->in_wait) BLMM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_in, 0));
-    ctx->stream = ctx->side;
-    rc = rotate_markers(ctx, P, dG, p);
-    ctx->stream = main_stream;
-    if (rc) return rc;
+    OnStream on(ctx, ctx->side);
+    if ((rc = rotate_markers(ctx, P, dG, p))) return rc;
     P.xt_side = true;
   }
   if ((rc = rotate_traits(ctx, P, dY, m))) return rc;
@@ -443,41 +483,49 @@ NullModel null_model(const Pipe& P, const blmm_opts* o) {
   return nm;
 }
 
-int grid_to_device(blmm_ctx* ctx, const double* h2_grid_host, int64_t ngrid, double** out) {
+// Caller memory -> dst on ctx->stream without waiting: through a pinned slot of the context.  A slot whose copy has not run yet
+// (its event is pending: back-to-back calls) is left alone and the ring grows instead -- to the depth of the caller's queue at most.
+int stage_to_device(blmm_ctx* ctx, DevBuf& dst, const void* src, size_t bytes) {
+  blmm_ctx::GridSlot* slot = nullptr;
+  for (auto& g : ctx->gstage)
+    if (g.cap >= bytes && (!g.used || hipEventQuery(g.ev) == hipSuccess)) { slot = &g; break; }
+  if (!slot) {
+    blmm_ctx::GridSlot g;
+    g.cap = bytes < 4096 ? 4096 : bytes;
+    void* h = nullptr;
+    BLMM_HIP(hipHostMalloc(&h, g.cap, hipHostMallocDefault));
+    g.h = h;
+    if (hipEventCreateWithFlags(&g.ev, hipEventDisableTiming) != hipSuccess) { (void)hipHostFree(h); return fail(ctx, BLMM_ERR_HIP, "hipEventCreate failed"); }
+    ctx->gstage.push_back(g);
+    slot = &ctx->gstage.back();
+  }
+  std::memcpy(slot->h, src, bytes);
+  BLMM_HIP(hipMemcpyAsync(dst.p, slot->h, bytes, hipMemcpyHostToDevice, ctx->stream));
+  BLMM_HIP(hipEventRecord(slot->ev, ctx->stream));
+  slot->used = true;
+  return BLMM_OK;
+}
+
+int check_grid(blmm_ctx* ctx, const double* h2_grid_host, int64_t ngrid) {
   if (!h2_grid_host || ngrid < 1) return fail(ctx, BLMM_ERR_INVALID, "h2 grid is empty");
   for (int64_t g = 0; g < ngrid; ++g) {
     const double h = h2_grid_host[g];
     if (std::isinf(h / (1.0 - h))) return fail(ctx, BLMM_ERR_H2_ONE, "Heritability of 1 is not allowed.");
   }
-  int rc = ensure(ctx, ctx->gridd, sizeof(double) * ngrid);
-  if (rc) return rc;
+  return BLMM_OK;
+}
+
+int grid_to_device(blmm_ctx* ctx, const double* h2_grid_host, int64_t ngrid, double** out) {
+  int rc;
+  if ((rc = check_grid(ctx, h2_grid_host, ngrid)) || (rc = ensure(ctx, ctx->gridd, sizeof(double) * ngrid))) return rc;
   const size_t bytes = sizeof(double) * (size_t)ngrid;
-  if (ctx->grid_async) {
-    // blmm_bulkscan_reduced_async: through a pinned slot of the context, no wait.  A slot whose copy has not run yet (its event
-    // is pending: back-to-back calls) is left alone and the ring grows instead -- to the depth of the caller's queue at most.
-    blmm_ctx::GridSlot* slot = nullptr;
-    for (auto& g : ctx->gstage)
-      if (g.cap >= bytes && (!g.used || hipEventQuery(g.ev) == hipSuccess)) { slot = &g; break; }
-    if (!slot) {
-      blmm_ctx::GridSlot g;
-      g.cap = bytes < 4096 ? 4096 : bytes;
-      void* h = nullptr;
-      BLMM_HIP(hipHostMalloc(&h, g.cap, hipHostMallocDefault));
-      g.h = static_cast<double*>(h);
-      if (hipEventCreateWithFlags(&g.ev, hipEventDisableTiming) != hipSuccess) { (void)hipHostFree(h); return fail(ctx, BLMM_ERR_HIP, "hipEventCreate failed"); }
-      ctx->gstage.push_back(g);
-      slot = &ctx->gstage.back();
-    }
-    std::memcpy(slot->h, h2_grid_host, bytes);
-    BLMM_HIP(hipMemcpyAsync(ctx->gridd.p, slot->h, bytes, hipMemcpyHostToDevice, ctx->stream));
-    BLMM_HIP(hipEventRecord(slot->ev, ctx->stream));
-    slot->used = true;
-    *out = ptr<double>(ctx->gridd);
-    return BLMM_OK;
+  if (ctx->grid_async) {                     // blmm_bulkscan_reduced_async: no wait
+    if ((rc = stage_to_device(ctx, ctx->gridd, h2_grid_host, bytes))) return rc;
+  } else {
+    BLMM_HIP(hipMemcpyAsync(ctx->gridd.p, h2_grid_host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    // the source is caller memory: make sure the copy has left it before we return
+    BLMM_HIP(hipStreamSynchronize(ctx->stream));
   }
-  BLMM_HIP(hipMemcpyAsync(ctx->gridd.p, h2_grid_host, bytes, hipMemcpyHostToDevice, ctx->stream));
-  // the source is caller memory: make sure the copy has left it before we return
-  BLMM_HIP(hipStreamSynchronize(ctx->stream));
   *out = ptr<double>(ctx->gridd);
   return BLMM_OK;
 }
@@ -512,7 +560,7 @@ int64_t lr_ldq(const Pipe& P) { return P.ldy + 128 + LR_TILE * LR_SEG_MAX; }   /
 // the per-region device counters of the class / segment layout (blmm_internal.h: NSTAT)
 static LrRegion lr_region(const Pipe& P, int r) {
   LrRegion rg;
-  rg.col0 = r * lr_ldq(P); rg.ncol = lr_ldq(P); rg.counts = P.stat + 12 + 2 * r; rg.segcnt = P.stat + 24 + 20 * r;
+  rg.col0 = r * lr_ldq(P); rg.ncol = lr_ldq(P); rg.counts = P.stat + ST_LR_SHARED0 + 2 * r; rg.segcnt = P.stat + 24 + 20 * r;
   return rg;
 }
 
@@ -533,23 +581,19 @@ int lr_begin(blmm_ctx* ctx, const Pipe& P, bool wbasis_started) {
   if ((rc = ensure(ctx, ctx->wbW, sizeof(double) * (size_t)P.n * (256 + 16)))) return rc;
   if ((rc = ensure(ctx, ctx->wbRk, sizeof(int) * 4 * LR_SEG_MAX))) return rc;
   int* rk = ptr<int>(ctx->wbRk);
-  hipStream_t main_stream = ctx->stream;
   if (!(wbasis_started && P.xt_side)) {                            // (the side stream rotated the markers itself: nothing of the main stream to wait for)
-    BLMM_HIP(hipEventRecord(ctx->ev_fork, main_stream));          // rotated operands are ready
+    BLMM_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));          // rotated operands are ready
     BLMM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
   }
   // (start_wbasis put the basis on the second side stream: the marker-side products follow it THERE, behind the rotation's event)
   const bool on2 = wbasis_started && P.xt_side && ctx->wb_on_side2;
   hipStream_t lr_side = on2 ? ctx->side2 : ctx->side;
-  ctx->stream = lr_side;                                           // the launchers enqueue on ctx->stream
-  rc = BLMM_OK;
-  if (!wbasis_started) rc = launch_wbasis(ctx, P.lam, P.n, P.npad, seg, ptr<double>(ctx->wbW), ptr<double>(ctx->wbQ), rk, P.stat);
-  if (!rc && hipEventRecord(ctx->ev_q, lr_side) != hipSuccess) rc = fail(ctx, BLMM_ERR_HIP, "hipEventRecord failed");   // what the panels need
-  if (!rc && on2 && hipStreamWaitEvent(lr_side, ctx->ev_wb, 0) != hipSuccess) rc = fail(ctx, BLMM_ERR_HIP, "hipStreamWaitEvent failed");
-  if (!rc) rc = launch_lr_tpanels(ctx, P.Xt, P.ldx, P.p, P.n, P.c, P.npad, P.Z0, ptr<double>(ctx->wbQ), rk, seg, ptr<double>(ctx->lrT), tstride,
-                                  ptr<double>(ctx->lrDen0));
-  ctx->stream = main_stream;
-  if (rc) return rc;
+  OnStream on(ctx, lr_side);
+  if (!wbasis_started && (rc = launch_wbasis(ctx, P.lam, P.n, P.npad, seg, ptr<double>(ctx->wbW), ptr<double>(ctx->wbQ), rk, P.stat))) return rc;
+  BLMM_HIP(hipEventRecord(ctx->ev_q, lr_side));                     // what the panels need
+  if (on2) BLMM_HIP(hipStreamWaitEvent(lr_side, ctx->ev_wb, 0));
+  if ((rc = launch_lr_tpanels(ctx, P.Xt, P.ldx, P.p, P.n, P.c, P.npad, P.Z0, ptr<double>(ctx->wbQ), rk, seg, ptr<double>(ctx->lrT), tstride,
+                              ptr<double>(ctx->lrDen0)))) return rc;
   BLMM_HIP(hipEventRecord(ctx->ev_join, lr_side));                  // ... and what the scan needs on top
   // (the column order's preset, -1 = padding, is written by the count pass of k_lr_classify)
   return BLMM_OK;
@@ -597,7 +641,9 @@ int lr_region_panels(blmm_ctx* ctx, const Pipe& P, const NullModel& nm, const do
   return launch_lr_panels(ctx, nm, P.Yt, P.ldy, P.m, P.Z0, P.lam, dh2, ptr<double>(ctx->wbQ), ptr<int>(ctx->wbRk), lr_segments(ctx, P.n), ptr<int>(ctx->lrPerm),
                           rg, ptr<double>(ctx->panels), ptr<double>(ctx->lrC), ptr<double>(ctx->lrL), 2 * lr_ldq(P), P.stat);
 }
+// residual guard of one region on the side stream (beside the region's scan)
 int lr_region_resid(blmm_ctx* ctx, const Pipe& P, const NullModel& nm, const double* dh2, const LrRegion& rg) {
+  OnStream on(ctx, ctx->side);
   return launch_lr_resid(ctx, nm, P.m, lr_tolerance(ctx), P.lam, dh2, ptr<double>(ctx->wbQ), ptr<int>(ctx->wbRk), lr_segments(ctx, P.n), ptr<int>(ctx->lrPerm), rg,
                          ptr<double>(ctx->lrC), 2 * lr_ldq(P), ptr<int>(ctx->lrFlag), ptr<double>(ctx->lrPart), P.stat, ctx->red_cur.flags);
 }
@@ -641,11 +687,11 @@ int lr_finish(blmm_ctx* ctx, const Pipe& P, const NullModel& nm, const double* d
   if (ahead && P.c >= 2 && (rc = ensure(ctx, ctx->illList, sizeof(int) * (size_t)P.m))) return rc;
   BLMM_HIP(hipEventRecord(ctx->ev_fork, main_stream));
   BLMM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
-  ctx->stream = ctx->side;
-  rc = lr_region_resid(ctx, P, nm, dh2, rg);
-  if (!rc && ahead && P.c >= 2) rc = launch_illcond_flag(ctx, nm, P.m, P.Z0, P.lam, dh2, ptr<int>(ctx->illList), P.stat, ctx->red_cur.flags);
-  ctx->stream = main_stream;
-  if (rc) return rc;
+  if ((rc = lr_region_resid(ctx, P, nm, dh2, rg))) return rc;
+  if (ahead && P.c >= 2) {
+    OnStream on(ctx, ctx->side);
+    if ((rc = launch_illcond_flag(ctx, nm, P.m, P.Z0, P.lam, dh2, ptr<int>(ctx->illList), P.stat, ctx->red_cur.flags))) return rc;
+  }
   BLMM_HIP(hipEventRecord(ctx->ev_join, ctx->side));
   if (ahead && ctx->red_cur.want_trip) BLMM_HIP(hipStreamWaitEvent(main_stream, ctx->ev_join, 0));
   if ((rc = lr_region_scan(ctx, P, rg, dL, ldL))) return rc;
@@ -682,21 +728,18 @@ int lr_finish_split(blmm_ctx* ctx, const Pipe& P, const NullModel& nm, double* d
   //      critical path (45 us beside it, 28 alone); its chain has ~0.5 ms of slack before region 1's scan needs it
   if (!b1_recorded) BLMM_HIP(hipEventRecord(ctx->ev_b1, main_stream));
   BLMM_HIP(hipStreamWaitEvent(ctx->side2, ctx->ev_b1, 0));
-  ctx->stream = ctx->side2;
-  BrentSplit sp2 = sp;
-  rc = launch_brent(ctx, nm, P.Yt, P.ldy, P.m, P.Z0, P.lam, dh2, nullptr, nullptr, P.stat, 2, &sp2);
-  if (!rc && hipStreamWaitEvent(ctx->side2, ctx->ev_q, 0) != hipSuccess) rc = fail(ctx, BLMM_ERR_HIP, "hipStreamWaitEvent failed");
-  if (!rc) rc = launch_lr_classify(ctx, P.n, P.m, lr_shared_tol(ctx), P.lam, dh2, nullptr, sp.list, sp.cnt, ptr<int>(ctx->lrPerm), r1, seg);
-  if (!rc) rc = lr_region_panels(ctx, P, nm, dh2, r1);
-  ctx->stream = main_stream;
-  if (rc) return rc;
+  {
+    OnStream on(ctx, ctx->side2);
+    BrentSplit sp2 = sp;
+    if ((rc = launch_brent(ctx, nm, P.Yt, P.ldy, P.m, P.Z0, P.lam, dh2, nullptr, nullptr, P.stat, 2, &sp2))) return rc;
+    BLMM_HIP(hipStreamWaitEvent(ctx->side2, ctx->ev_q, 0));
+    if ((rc = launch_lr_classify(ctx, P.n, P.m, lr_shared_tol(ctx), P.lam, dh2, nullptr, sp.list, sp.cnt, ptr<int>(ctx->lrPerm), r1, seg)) ||
+        (rc = lr_region_panels(ctx, P, nm, dh2, r1))) return rc;
+  }
   BLMM_HIP(hipEventRecord(ctx->ev_b2, ctx->side2));
   tm.mark();
   BLMM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_b1, 0));            // region 0's panels are done (the same point the second side stream forks at)
-  ctx->stream = ctx->side;
-  rc = lr_region_resid(ctx, P, nm, dh2, r0);
-  ctx->stream = main_stream;
-  if (rc) return rc;
+  if ((rc = lr_region_resid(ctx, P, nm, dh2, r0))) return rc;
   // (reduced_async_impl with triplets: each region's scan waits for its guard -- see lr_finish; it splits only at c = 1)
   const bool ahead = ctx->red_cur.flags != nullptr && ctx->red_cur.want_trip;
   if (ahead) {
@@ -706,10 +749,7 @@ int lr_finish_split(blmm_ctx* ctx, const Pipe& P, const NullModel& nm, double* d
   if ((rc = lr_region_scan(ctx, P, r0, dL, ldL))) return rc;
   // ---- region 1: its guard on the first side stream (behind region 0's), its scan on the main stream
   BLMM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_b2, 0));
-  ctx->stream = ctx->side;
-  rc = lr_region_resid(ctx, P, nm, dh2, r1);
-  ctx->stream = main_stream;
-  if (rc) return rc;
+  if ((rc = lr_region_resid(ctx, P, nm, dh2, r1))) return rc;
   BLMM_HIP(hipEventRecord(ctx->ev_join, ctx->side));
   BLMM_HIP(hipStreamWaitEvent(main_stream, ctx->ev_b2, 0));
   if (ahead) BLMM_HIP(hipStreamWaitEvent(main_stream, ctx->ev_join, 0));
@@ -894,7 +934,7 @@ int blmm_lowrank_profile(blmm_ctx* ctx, int64_t* out) {
     const int64_t cnt = h[24 + s] + h[44 + s];
     if (cnt > 0) { S = s + 1; out[2 + 2 * s] = cnt; out[3 + 2 * s] = rk[4 * s]; }
   }
-  out[0] = S; out[1] = h[12] + h[14];
+  out[0] = S; out[1] = h[ST_LR_SHARED0] + h[ST_LR_SHARED1];
   return BLMM_OK;
 }
 
@@ -916,7 +956,7 @@ int blmm_lowrank_columns(blmm_ctx* ctx, int64_t m, int32_t* col_out, int64_t* re
   BLMM_HIP(hipMemcpyAsync(h, ctx->stat.p, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
   BLMM_HIP(hipStreamSynchronize(ctx->stream));
   for (int r = 0; r < 2; ++r) {
-    const int64_t nsh = h[12 + 2 * r], noth = h[13 + 2 * r];
+    const int64_t nsh = h[ST_LR_SHARED0 + 2 * r], noth = h[ST_LR_OTHER0 + 2 * r];
     if (counts_out) { counts_out[2 * r] = nsh; counts_out[2 * r + 1] = noth; }
     for (int64_t cidx = 0; cidx < ldq; ++cidx) {
       if (!(cidx < nsh || cidx >= ldq - noth)) continue;
@@ -1028,7 +1068,7 @@ int blmm_lod_colmax(blmm_ctx* ctx, const double* L, int64_t p, int64_t m, double
   int rc;
   if ((rc = hc.begin()) || (rc = hc.up(ctx->outL, L, sizeof(double) * (size_t)p * m)) || (rc = ensure(ctx, ctx->tmpA, sizeof(double) * mm)) ||
       (rc = ensure(ctx, ctx->tmpB, sizeof(int64_t) * mm))) return rc;
-  if (m > 0) { ctx->last_L = ptr<double>(ctx->outL); ctx->last_p = p; ctx->last_m = m; ctx->last_f32 = false; }
+  if (m > 0) set_last(ctx, ptr<double>(ctx->outL), p, m);
   if ((rc = launch_colmax(ctx, ptr<double>(ctx->outL), p, m, p, ptr<double>(ctx->tmpA), ptr<int64_t>(ctx->tmpB))) ||
       (rc = hc.down(max_out, ctx->tmpA.p, sizeof(double) * (size_t)m)) || (rc = hc.down(argmax_out, ctx->tmpB.p, sizeof(int64_t) * (size_t)m)))
     return rc;
@@ -1057,7 +1097,7 @@ int blmm_lod_threshold(blmm_ctx* ctx, const double* L, int64_t p, int64_t m, dou
   HostCall hc(ctx);
   int rc;
   if ((rc = hc.begin()) || (rc = hc.up(ctx->outL, L, sizeof(double) * (size_t)p * m))) return rc;
-  ctx->last_L = ptr<double>(ctx->outL); ctx->last_p = p; ctx->last_m = m; ctx->last_f32 = false;
+  set_last(ctx, ptr<double>(ctx->outL), p, m);
   if ((rc = blmm_last_lod_threshold(ctx, thr, cap, i_out, j_out, lod_out, count_out))) return rc;
   return hc.finish(false);
 }
@@ -1095,29 +1135,36 @@ void pv_hand_over(blmm_ctx* ctx, const PvReq& r) {   // host-pointer entry point
   ctx->pv_armed = r.armed; ctx->pv_out = r.out; ctx->pv_ld = r.ld; ctx->pv_df = r.df;
 }
 struct PvCall {
-  blmm_ctx* ctx; PvReq req; double* P = nullptr; int64_t ld = 0, df = 1; bool fused = false, owned = false;
+  blmm_ctx* ctx; PvReq req; double* P = nullptr; int64_t ld = 0; bool fused = false, owned = false;
   PvCall(blmm_ctx* c, const PvReq& r) : ctx(c), req(r) {}
   ~PvCall() { ctx->pv_cur = nullptr; ctx->pv_cur_ld = 0; }
-  int begin(const Pipe& Pp, const blmm_opts* o) {
+  // where the request's p x m matrix goes: the caller's buffer (refused when ldP < p) or the context's outP
+  int resolve(int64_t p, int64_t m) {
     if (!req.armed) return BLMM_OK;
-    if (Pp.p <= 0 || Pp.m <= 0) return BLMM_OK;
-    df = req.df; P = req.out; ld = req.ld;
-    if (P && ld < Pp.p) { P = nullptr; return fail(ctx, BLMM_ERR_INVALID, "log10p output: ldP < p"); }
+    if (p <= 0 || m <= 0) return BLMM_OK;
+    P = req.out; ld = req.ld;
+    if (P && ld < p) { P = nullptr; return fail(ctx, BLMM_ERR_INVALID, "log10p output: ldP < p"); }
     if (!P) {
-      int rc = ensure(ctx, ctx->outP, sizeof(double) * (size_t)Pp.p * (size_t)Pp.m);
+      int rc = ensure(ctx, ctx->outP, sizeof(double) * (size_t)p * (size_t)m);
       if (rc) return rc;
-      P = ptr<double>(ctx->outP); ld = Pp.p; owned = true;
+      P = ptr<double>(ctx->outP); ld = p; owned = true;
     }
+    return BLMM_OK;
+  }
+  int begin(const Pipe& Pp, const blmm_opts* o) {
+    int rc = resolve(Pp.p, Pp.m);
+    if (rc || !P) return rc;
     const char* pf = dev_env("BLMM_PVAL_FUSED");             // tuning key "pval_fused"
-    fused = df == 1 && o->method != BLMM_ALT_GRID && (pf ? pf[0] != '0' : ctx->tune.pval_fused != 0);
+    fused = req.df == 1 && o->method != BLMM_ALT_GRID && (pf ? pf[0] != '0' : ctx->tune.pval_fused != 0);
     if (fused) { ctx->pv_cur = P; ctx->pv_cur_ld = ld; }
     return BLMM_OK;
   }
-  int finish(const Pipe& Pp, const double* dL, int64_t ldL) {
+  // the column pass over the finished L unless the scan epilogues wrote P; a matrix in outP is what blmm_last_log10p serves
+  int finish(int64_t p, int64_t m, const double* dL, int64_t ldL) {
     ctx->pv_cur = nullptr; ctx->pv_cur_ld = 0;
     if (!P) return BLMM_OK;
-    if (!fused) { int rc = launch_lod2log10p(ctx, dL, Pp.p, Pp.m, ldL, (int)df, P, ld); if (rc) return rc; }
-    if (owned) { ctx->last_P = P; ctx->last_P_ld = ld; ctx->last_P_df = df; }
+    if (!fused) { int rc = launch_lod2log10p(ctx, dL, p, m, ldL, (int)req.df, P, ld); if (rc) return rc; }
+    if (owned) { ctx->last_P = P; ctx->last_P_ld = ld; ctx->last_P_df = req.df; }
     return BLMM_OK;
   }
 };
@@ -1129,14 +1176,13 @@ struct PvCall {
 static int isx_maybe_side(blmm_ctx* ctx, const Pipe& P, const NullModel& nm, const double* dgrid, int ngrid) {
   int rc;
   if ((rc = ensure(ctx, ctx->isx, sizeof(double) * (size_t)ngrid * P.ldx))) return rc;
-  hipStream_t main_stream = ctx->stream;
-  if (P.xt_side) ctx->stream = ctx->side;
-  rc = launch_isx(ctx, nm, P.Xt, P.ldx, P.p, P.Z0, P.lam, dgrid, ngrid, ptr<double>(ctx->isx), P.ldx, P.stat);
-  ctx->stream = main_stream;
-  if (rc) return rc;
+  {
+    OnStream on(ctx, P.xt_side ? ctx->side : ctx->stream);
+    if ((rc = launch_isx(ctx, nm, P.Xt, P.ldx, P.p, P.Z0, P.lam, dgrid, ngrid, ptr<double>(ctx->isx), P.ldx, P.stat))) return rc;
+  }
   if (P.xt_side) {
     BLMM_HIP(hipEventRecord(ctx->ev_join, ctx->side));
-    BLMM_HIP(hipStreamWaitEvent(main_stream, ctx->ev_join, 0));
+    BLMM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
   }
   return BLMM_OK;
 }
@@ -1245,7 +1291,7 @@ static int scan_pipeline(blmm_ctx* ctx, const blmm_opts* opts, Pipe& P, Timer& t
     if ((rc = launch_scan_alt(ctx, aa))) return rc;
     tm.mark();
   }
-  if ((rc = pvc.finish(P, dL_out, ldL))) return rc;
+  if ((rc = pvc.finish(p, m, dL_out, ldL))) return rc;
   return end_call(ctx, P, status, &tm);
 }
 
@@ -1263,9 +1309,9 @@ static bool exact_full(const blmm_ctx* ctx) {   // tuning key "exact_full_rank"
   const char* e = dev_env("BLMM_EXACT");
   return e ? std::strcmp(e, "full") == 0 : ctx->tune.exact_full_rank != 0;
 }
+static bool lowrank_form(const blmm_ctx* ctx, int c, int64_t n) { return !exact_full(ctx) && c <= 3 && n <= 6000; }
 static bool wants_lowrank(const blmm_ctx* ctx, const blmm_opts* opts, int64_t n, const double* dCovar, int64_t ncov) {
-  const int c_eff = (int)((ncov == 0 || !dCovar) ? 1 : ncov + (opts->add_intercept ? 1 : 0));
-  return opts->method == BLMM_NULL_EXACT && !exact_full(ctx) && c_eff <= 3 && n <= 6000;
+  return opts->method == BLMM_NULL_EXACT && lowrank_form(ctx, (int)null_cov(opts, dCovar, ncov).c, n);
 }
 
 // dL_out == nullptr: only with ctx->red_cur set (blmm_bulkscan_reduced: the scan kernels reduce in their epilogues)
@@ -1277,10 +1323,7 @@ static int bulkscan_dev_impl(blmm_ctx* ctx, const blmm_opts* opts, const double*
   if (rc) return rc;
   if (!dY || !dG || !dK || (!dL_out && !ctx->red_cur.pmax) || !dh2_out) return fail(ctx, BLMM_ERR_INVALID, "bulkscan: NULL buffer");
   if (ldL < p) return fail(ctx, BLMM_ERR_INVALID, "bulkscan: ldL < p");
-  if (opts->method != BLMM_NULL_EXACT && opts->method != BLMM_NULL_GRID && opts->method != BLMM_ALT_GRID)
-    return fail(ctx, BLMM_ERR_METHOD, "Unknown method; choose null-exact, null-grid or alt-grid.");
-  BLMM_HIP(hipSetDevice(ctx->device));
-  if ((rc = check_sticky(ctx))) return rc;
+  if ((rc = check_method(ctx, opts)) || (rc = enter_device(ctx))) return rc;
   Timer tm(ctx);
   Pipe P;
   double* dgrid = nullptr;
@@ -1311,8 +1354,7 @@ static int reduced_check(blmm_ctx* ctx, const blmm_opts* opts, const double* dY,
   if (!out || !dY || !dG || !dK || (!dh2_out && opts->method != BLMM_ALT_GRID)) return fail(ctx, BLMM_ERR_INVALID, std::string(who) + ": NULL buffer");
   if (out->cap < 0 || (out->cap > 0 && (!out->ti || !out->tj || !out->tlod)) || (out->want_triplets && !out->count))
     return fail(ctx, BLMM_ERR_INVALID, std::string(who) + ": triplet buffers");
-  if (opts->method != BLMM_NULL_EXACT && opts->method != BLMM_NULL_GRID && opts->method != BLMM_ALT_GRID)
-    return fail(ctx, BLMM_ERR_METHOD, "Unknown method; choose null-exact, null-grid or alt-grid.");
+  if ((rc = check_method(ctx, opts))) return rc;
   if (n < 1 || m < 0 || p < 0 || p > 0x7fffffffLL || m > 0x7fffffffLL) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
   return BLMM_OK;
 }
@@ -1346,7 +1388,7 @@ static int reduced_resident(blmm_ctx* ctx, const blmm_opts* opts, const double* 
     dH = ptr<double>(ctx->altbuf);
   }
   if ((rc = bulkscan_dev_impl(ctx, opts, dY, n, m, dG, p, dCovar, ncov, dK, dweights, h2_grid_host, ngrid, dL, ldL, dH, status, PvReq()))) return rc;
-  if (m > 0) { ctx->last_L = dL; ctx->last_p = p; ctx->last_m = m; ctx->last_f32 = false; }
+  if (m > 0) set_last(ctx, dL, p, m);
   if (out->colmax && m > 0 && (rc = launch_colmax(ctx, dL, p, m, ldL, out->colmax, out->argmax))) return rc;
   if (out->want_triplets && (rc = launch_threshold(ctx, dL, p, m, ldL, out->thr, out->cap, out->ti, out->tj, out->tlod, out->count))) return rc;
   return BLMM_OK;
@@ -1381,7 +1423,7 @@ static int reduced_impl(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, 
     BLMM_HIP(hipMemcpyAsync(h, ctx->stat.p, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
     BLMM_HIP(hipStreamSynchronize(ctx->stream));
     if ((rc = check_sticky(ctx))) return rc;
-    if (h[10] == 0 && h[ST_ILLCOND] == 0) { if (route_out) *route_out = 1; return BLMM_OK; }
+    if (h[ST_LR_FIX] == 0 && h[ST_ILLCOND] == 0) { if (route_out) *route_out = 1; return BLMM_OK; }
   }
   if ((rc = reduced_resident(ctx, opts, dY, n, m, dG, p, dCovar, ncov, dK, dweights, h2_grid_host, ngrid, out, dh2_out, status))) {
     (void)hipStreamSynchronize(ctx->stream);
@@ -1418,8 +1460,7 @@ int blmm_prepare_dev(blmm_ctx* ctx, const blmm_opts* opts, int64_t n, const doub
   int rc = check_opts(ctx, opts);
   if (rc) return rc;
   if (!dK) return fail(ctx, BLMM_ERR_INVALID, "prepare: NULL buffer");
-  BLMM_HIP(hipSetDevice(ctx->device));
-  if ((rc = check_sticky(ctx))) return rc;
+  if ((rc = enter_device(ctx))) return rc;
   ctx->prep_valid = false;
   Timer tm(ctx);
   Pipe P;
@@ -1465,6 +1506,17 @@ static int assemble_prerotated(blmm_ctx* ctx, Pipe& P, int64_t p, const double* 
   return BLMM_OK;
 }
 
+// A scan on the state blmm_prepare_dev left: its counters start from zero except what the eigen-decomposition left (negative
+// eigenvalues, its sweeps and clocks); the eigen and rotation phases have nothing to time
+static int reset_prepared(blmm_ctx* ctx, const Pipe& P, Timer& tm) {
+  BLMM_HIP(hipMemsetAsync(P.stat + ST_NONPOS_W, 0, sizeof(int64_t) * (ST_JACOBI_SWEEPS - ST_NONPOS_W), ctx->stream));
+  BLMM_HIP(hipMemsetAsync(P.stat + ST_LR_RANK, 0, sizeof(int64_t) * (NSTAT - ST_LR_RANK), ctx->stream));
+  ctx->audit_ran = false;
+  ctx->brent_cnt_used = false;
+  tm.mark(); tm.mark();
+  return BLMM_OK;
+}
+
 int blmm_bulkscan_prerotated_dev(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t m, int64_t p,
                                  const double* dXt_blocks, int64_t nblocks, int64_t block_cols, int64_t block_ld,
                                  const double* h2_grid_host, int64_t ngrid, double* dL_out, int64_t ldL, double* dh2_out,
@@ -1478,23 +1530,15 @@ int blmm_bulkscan_prerotated_dev(blmm_ctx* ctx, const blmm_opts* opts, const dou
   if (m < 0 || p < 0 || nblocks < 1 || block_cols < 1 || block_ld < block_cols || nblocks * block_cols < p)
     return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
   if (ldL < p) return fail(ctx, BLMM_ERR_INVALID, "bulkscan: ldL < p");
-  if (opts->method != BLMM_NULL_EXACT && opts->method != BLMM_NULL_GRID && opts->method != BLMM_ALT_GRID)
-    return fail(ctx, BLMM_ERR_METHOD, "Unknown method; choose null-exact, null-grid or alt-grid.");
-  BLMM_HIP(hipSetDevice(ctx->device));
-  if ((rc = check_sticky(ctx))) return rc;
+  if ((rc = check_method(ctx, opts)) || (rc = enter_device(ctx))) return rc;
   Timer tm(ctx);
   Pipe P = prepared_pipe(ctx);
   double* dgrid = nullptr;
   if (opts->method != BLMM_NULL_EXACT) {
     if ((rc = grid_to_device(ctx, h2_grid_host, ngrid, &dgrid))) return rc;
   }
-  // the counters of this scan start from zero except what the eigen-decomposition left (negative eigenvalues, its clocks)
-  BLMM_HIP(hipMemsetAsync(P.stat + 1, 0, sizeof(int64_t) * 4, ctx->stream));
-  BLMM_HIP(hipMemsetAsync(P.stat + 8, 0, sizeof(int64_t) * (NSTAT - 8), ctx->stream));
-  ctx->audit_ran = false;
-  ctx->brent_cnt_used = false;
-  tm.mark(); tm.mark();
-  const bool lowrank = opts->method == BLMM_NULL_EXACT && !exact_full(ctx) && P.c <= 3;
+  if ((rc = reset_prepared(ctx, P, tm))) return rc;
+  const bool lowrank = opts->method == BLMM_NULL_EXACT && lowrank_form(ctx, P.c, P.n);
   if (lowrank && m > 0 && p > 0 && (rc = start_wbasis(ctx, P))) return rc;
   if ((rc = rotate_traits(ctx, P, dY, m))) return rc;
   if ((rc = assemble_prerotated(ctx, P, p, dXt_blocks, nblocks, block_cols, block_ld))) return rc;
@@ -1524,18 +1568,17 @@ int blmm_bulkscan(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, int64_t
   static const bool hprof = getenv("BLMM_HOST_PROF") && getenv("BLMM_HOST_PROF")[0] == '1';
   auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double hp0 = hprof ? now() : 0.0;
-  const double *dCov, *dW;
-  if ((rc = hc.up(ctx->inK, K, sizeof(double) * n * n)) || (rc = hc.defer_yg(Y, sizeof(double) * n * m, G, sizeof(double) * n * p)) ||
-      (rc = hc.up_opt(ctx->inCov, Covar, n * ncov, &dCov)) || (rc = hc.up_opt(ctx->inW, weights, n, &dW))) return rc;
+  HostCall::In d;
+  if ((rc = hc.inputs(Y, n, m, G, p, K, Covar, ncov, weights, /*defer*/ true, &d))) return rc;
   if (hprof) (void)hipStreamSynchronize(ctx->stream);
   const double hp1 = hprof ? now() : 0.0;
   pv_hand_over(ctx, pvreq);
-  if ((rc = blmm_bulkscan_dev(ctx, opts, ptr<double>(ctx->inY), n, m, ptr<double>(ctx->inG), p, dCov, dCov ? ncov : 0,
-                              ptr<double>(ctx->inK), dW, h2_grid, ngrid, ptr<double>(ctx->outL), p, ptr<double>(ctx->outH2), status))) return rc;
+  if ((rc = blmm_bulkscan_dev(ctx, opts, d.Y, n, m, d.G, p, d.Cov, d.ncov, d.K, d.W, h2_grid, ngrid, ptr<double>(ctx->outL), p,
+                              ptr<double>(ctx->outH2), status))) return rc;
   const double hp2 = hprof ? now() : 0.0;
   if (hprof) (void)hipStreamSynchronize(ctx->stream);
   const double hp3 = hprof ? now() : 0.0;
-  ctx->last_L = ptr<double>(ctx->outL); ctx->last_p = p; ctx->last_m = m; ctx->last_f32 = false;
+  set_last(ctx, ptr<double>(ctx->outL), p, m);
   if (L_out && (size_t)p * m > 0 && (rc = copy_to_host(ctx, L_out, ctx->outL.p, sizeof(double) * (size_t)p * m))) return rc;
   const double hp4 = hprof ? now() : 0.0;
   if (h2_out && h2_elems > 0 && (rc = copy_to_host(ctx, h2_out, ctx->outH2.p, sizeof(double) * h2_elems))) return rc;
@@ -1564,30 +1607,11 @@ static int loco_check(blmm_ctx* ctx, int64_t n, int64_t p, const int64_t* chr, i
   return BLMM_OK;
 }
 
-// the chromosome offsets on the device (locoChr), in stream order and without waiting: the caller's array is copied into a pinned
-// slot of the context (the ring of grid_to_device's asynchronous form: a slot whose copy is still queued is left alone and the ring
-// grows instead), and the device copy is enqueued from there
+// the chromosome offsets on the device (locoChr), in stream order and without waiting (stage_to_device)
 static int loco_offsets(blmm_ctx* ctx, const int64_t* chr, int64_t nchr, const int64_t** dchr) {
   const size_t bytes = sizeof(int64_t) * (size_t)(nchr + 1);
-  int rc = ensure(ctx, ctx->locoChr, bytes);
-  if (rc) return rc;
-  blmm_ctx::GridSlot* slot = nullptr;
-  for (auto& g : ctx->gstage)
-    if (g.cap >= bytes && (!g.used || hipEventQuery(g.ev) == hipSuccess)) { slot = &g; break; }
-  if (!slot) {
-    blmm_ctx::GridSlot g;
-    g.cap = bytes < 4096 ? 4096 : bytes;
-    void* h = nullptr;
-    BLMM_HIP(hipHostMalloc(&h, g.cap, hipHostMallocDefault));
-    g.h = static_cast<double*>(h);
-    if (hipEventCreateWithFlags(&g.ev, hipEventDisableTiming) != hipSuccess) { (void)hipHostFree(h); return fail(ctx, BLMM_ERR_HIP, "hipEventCreate failed"); }
-    ctx->gstage.push_back(g);
-    slot = &ctx->gstage.back();
-  }
-  std::memcpy(slot->h, chr, bytes);
-  BLMM_HIP(hipMemcpyAsync(ctx->locoChr.p, slot->h, bytes, hipMemcpyHostToDevice, ctx->stream));
-  BLMM_HIP(hipEventRecord(slot->ev, ctx->stream));
-  slot->used = true;
+  int rc;
+  if ((rc = ensure(ctx, ctx->locoChr, bytes)) || (rc = stage_to_device(ctx, ctx->locoChr, chr, bytes))) return rc;
   *dchr = ptr<int64_t>(ctx->locoChr);
   return BLMM_OK;
 }
@@ -1634,13 +1658,10 @@ static int bulkscan_loco_dev_impl(blmm_ctx* ctx, const blmm_opts* opts, const do
   int rc = check_opts(ctx, opts);
   if (rc) return rc;
   if (!dY || !dG || !dL || (!dh2 && opts->method != BLMM_ALT_GRID)) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_loco: NULL buffer");
-  if (opts->method != BLMM_NULL_EXACT && opts->method != BLMM_NULL_GRID && opts->method != BLMM_ALT_GRID)
-    return fail(ctx, BLMM_ERR_METHOD, "Unknown method; choose null-exact, null-grid or alt-grid.");
-  if ((rc = loco_check(ctx, n, p, chr, nchr, "bulkscan_loco"))) return rc;
+  if ((rc = check_method(ctx, opts)) || (rc = loco_check(ctx, n, p, chr, nchr, "bulkscan_loco"))) return rc;
   if (m < 0 || ldL < p || kdigits > 300) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_loco: bad arguments");
   if (n > 2048) return fail(ctx, BLMM_ERR_UNSUPPORTED, "more than 2048 individuals: the device eigensolver (tridiagonalisation + divide and conquer) stops at n = 2048");
-  BLMM_HIP(hipSetDevice(ctx->device));
-  if ((rc = check_sticky(ctx))) return rc;
+  if ((rc = enter_device(ctx))) return rc;
   double* dgrid = nullptr;
   if (opts->method != BLMM_NULL_EXACT && (rc = grid_to_device(ctx, h2_grid_host, ngrid, &dgrid))) return rc;
   // one event set for the start of the call (t_total_ms spans the kinships computed inside it, which count in no phase), one for the
@@ -1667,19 +1688,15 @@ static int bulkscan_loco_dev_impl(blmm_ctx* ctx, const blmm_opts* opts, const do
   const bool batched = n >= 3 && n <= eig_fast_max_n() && !dev_env("BLMM_EIGEN") && ctx->tune.eigen_solver == 0;
   const int64_t sA = round_up(n * n, 32), sE = round_up(n * n + 4 * n + 16, 32), sL = round_up(n, 32);
   if (batched) {
-    int add_int = opts->add_intercept ? 1 : 0;
-    int64_t nc = ncov;
-    const double* cov = dCovar;
-    if (nc == 0 || !cov) { add_int = 1; nc = 0; cov = nullptr; }
-    const int64_t cc = nc + add_int;
-    if (cc < 1 || cc > CMAX) return fail(ctx, BLMM_ERR_UNSUPPORTED, BLMM_C_ERR);
-    if (cc >= n) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
+    const NullCov nc = null_cov(opts, dCovar, ncov);
+    if (nc.c < 1 || nc.c > CMAX) return fail(ctx, BLMM_ERR_UNSUPPORTED, BLMM_C_ERR);
+    if (nc.c >= n) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
     if ((rc = ensure(ctx, ctx->locoKs, sizeof(double) * (size_t)nchr * sA)) || (rc = ensure(ctx, ctx->locoV, sizeof(double) * (size_t)nchr * sE)) ||
-        (rc = ensure(ctx, ctx->locoLraw, sizeof(double) * (size_t)nchr * sL)) || (rc = ensure(ctx, ctx->Zs, sizeof(double) * n * cc))) return rc;
+        (rc = ensure(ctx, ctx->locoLraw, sizeof(double) * (size_t)nchr * sL)) || (rc = ensure(ctx, ctx->Zs, sizeof(double) * n * nc.c))) return rc;
     BLMM_HIP(hipMemsetAsync(dst_all, 0, sizeof(int64_t) * NSTAT * (size_t)nchr, ctx->stream));
     tb.mark();
     for (int64_t c = 0; c < nchr; ++c)
-      if ((rc = launch_design(ctx, dK + (size_t)c * n * n, cov, (int)nc, add_int, dweights, (int)n, ptr<double>(ctx->locoKs) + (size_t)c * sA,
+      if ((rc = launch_design(ctx, dK + (size_t)c * n * n, nc.d, (int)nc.ncov, nc.add_int, dweights, (int)n, ptr<double>(ctx->locoKs) + (size_t)c * sA,
                               ptr<double>(ctx->Zs)))) return rc;
     if ((rc = launch_eig_fast_batch(ctx, ptr<double>(ctx->locoKs), sA, (int)n, (int)nchr, ptr<double>(ctx->locoLraw), sL,
                                     ptr<double>(ctx->locoV), sE, dst_all, NSTAT))) return rc;
@@ -1722,17 +1739,8 @@ static int bulkscan_loco_dev_impl(blmm_ctx* ctx, const blmm_opts* opts, const do
     if ((rc = ensure(ctx, ctx->stat, sizeof(int64_t) * NSTAT))) return rc;
     BLMM_HIP(hipMemcpyAsync(ctx->stat.p, dst_all + (size_t)order.back() * NSTAT, sizeof(int64_t) * NSTAT, hipMemcpyDeviceToDevice, ctx->stream));
   }
-  if (pvreq.armed && m > 0) {
-    double* Pv = pvreq.out;
-    int64_t ld = pvreq.ld;
-    if (Pv && ld < p) return fail(ctx, BLMM_ERR_INVALID, "log10p output: ldP < p");
-    if (!Pv) {
-      if ((rc = ensure(ctx, ctx->outP, sizeof(double) * (size_t)p * m))) return rc;
-      Pv = ptr<double>(ctx->outP); ld = p;
-    }
-    if ((rc = launch_lod2log10p(ctx, dL, p, m, ldL, (int)pvreq.df, Pv, ld))) return rc;
-    if (!pvreq.out) { ctx->last_P = Pv; ctx->last_P_ld = ld; ctx->last_P_df = pvreq.df; }
-  }
+  PvCall pvc(ctx, pvreq);                    // (never fused: a column pass over the finished L)
+  if ((rc = pvc.resolve(p, m)) || (rc = pvc.finish(p, m, dL, ldL))) return rc;
   if (!status) return BLMM_OK;
   std::vector<int64_t> h((size_t)nchr * NSTAT);
   BLMM_HIP(hipMemcpyAsync(h.data(), dst_all, sizeof(int64_t) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
@@ -1742,21 +1750,10 @@ static int bulkscan_loco_dev_impl(blmm_ctx* ctx, const blmm_opts* opts, const do
   for (int64_t c = 0; c < nchr; ++c) {
     blmm_status one;
     if ((rc = fill_status(ctx, h.data() + (size_t)c * NSTAT, &one))) return rc;
-    sum.n_neg_eig += one.n_neg_eig; sum.n_nonpos_weight += one.n_nonpos_weight; sum.n_zero_norm += one.n_zero_norm;
-    sum.n_nan_lod += one.n_nan_lod; sum.n_brent_maxiter += one.n_brent_maxiter; sum.jacobi_sweeps += one.jacobi_sweeps;
-    sum.jacobi_cycles += one.jacobi_cycles; sum.jacobi_ticks_100mhz += one.jacobi_ticks_100mhz;
-    sum.lowrank_rank = std::max(sum.lowrank_rank, one.lowrank_rank);
-    sum.lowrank_fallback += one.lowrank_fallback; sum.lowrank_shared += one.lowrank_shared;
-    sum.lowrank_resid = std::max(sum.lowrank_resid, one.lowrank_resid);
-    sum.n_h2_boundary += one.n_h2_boundary; sum.n_h2_multimodal += one.n_h2_multimodal; sum.n_illcond_rescan += one.n_illcond_rescan;
+    add_status(&sum, one);
   }
   if (!audit) sum.n_h2_multimodal = -1;
-  for (const Timer& tm : tms) {
-    if (!tm.set || tm.set->n < 2) continue;
-    double t[6];
-    phase_times(*tm.set, t);
-    sum.t_eigen_ms += t[0]; sum.t_rotate_ms += t[1]; sum.t_h2_ms += t[2]; sum.t_prep_ms += t[3]; sum.t_scan_ms += t[4];
-  }
+  for (const Timer& tm : tms) add_phase_times(&sum, tm);
   if (tb.set && tb.set->n >= 2) {            // the batched eigen phase (the chromosomes' own eigen phases are their post-eigen work)
     float te = 0;
     (void)hipEventElapsedTime(&te, tb.set->e[0], tb.set->e[1]);
@@ -1799,15 +1796,13 @@ int blmm_bulkscan_loco(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, in
   if (n > 2048) return fail(ctx, BLMM_ERR_UNSUPPORTED, "more than 2048 individuals: the device eigensolver (tridiagonalisation + divide and conquer) stops at n = 2048");
   HostCall hc(ctx);
   const size_t h2_elems = alt ? (size_t)p * m : (size_t)m * nchr;
-  const double *dCov, *dW;
+  HostCall::In d;
   if ((rc = hc.begin()) || (rc = ensure(ctx, ctx->outL, sizeof(double) * (size_t)p * m)) || (rc = ensure(ctx, ctx->outH2, sizeof(double) * h2_elems)) ||
-      (rc = hc.up(ctx->inY, Y, sizeof(double) * n * m)) || (rc = hc.up(ctx->inG, G, sizeof(double) * n * p)) ||
-      (rc = hc.up_opt(ctx->inCov, Covar, n * ncov, &dCov)) || (rc = hc.up_opt(ctx->inW, weights, n, &dW))) return rc;
+      (rc = hc.inputs(Y, n, m, G, p, nullptr, Covar, ncov, weights, false, &d))) return rc;
   ctx->red_cur = RedArgs();
-  if ((rc = bulkscan_loco_dev_impl(ctx, opts, ptr<double>(ctx->inY), n, m, ptr<double>(ctx->inG), p, chr_start, nchr, kinship_digits, dCov,
-                                   dCov ? ncov : 0, dW, h2_grid, ngrid, nullptr, ptr<double>(ctx->outL), p,
-                                   (alt && !h2_out) ? nullptr : ptr<double>(ctx->outH2), status, pvreq))) return rc;
-  ctx->last_L = ptr<double>(ctx->outL); ctx->last_p = p; ctx->last_m = m; ctx->last_f32 = false;
+  if ((rc = bulkscan_loco_dev_impl(ctx, opts, d.Y, n, m, d.G, p, chr_start, nchr, kinship_digits, d.Cov, d.ncov, d.W, h2_grid, ngrid, nullptr,
+                                   ptr<double>(ctx->outL), p, (alt && !h2_out) ? nullptr : ptr<double>(ctx->outH2), status, pvreq))) return rc;
+  set_last(ctx, ptr<double>(ctx->outL), p, m);
   if (L_out && (size_t)p * m > 0 && (rc = copy_to_host(ctx, L_out, ctx->outL.p, sizeof(double) * (size_t)p * m))) return rc;
   if (h2_out && h2_elems > 0 && (rc = copy_to_host(ctx, h2_out, ctx->outH2.p, sizeof(double) * h2_elems))) return rc;
   if ((rc = hc.finish())) return rc;
@@ -1840,11 +1835,10 @@ int blmm_bulkscan_reduced(blmm_ctx* ctx, const blmm_opts* opts, const double* Y,
   d.tlod = reinterpret_cast<double*>(d.count + 8);
   d.ti = reinterpret_cast<int32_t*>(d.tlod + cap);
   d.tj = d.ti + cap;
-  const double *dCov, *dW;
-  if ((rc = hc.up(ctx->inK, K, sizeof(double) * n * n)) || (rc = hc.defer_yg(Y, sizeof(double) * n * m, G, sizeof(double) * n * p)) ||
-      (rc = hc.up_opt(ctx->inCov, Covar, n * ncov, &dCov)) || (rc = hc.up_opt(ctx->inW, weights, n, &dW)) ||
-      (rc = reduced_impl(ctx, opts, ptr<double>(ctx->inY), n, m, ptr<double>(ctx->inG), p, dCov, dCov ? ncov : 0, ptr<double>(ctx->inK), dW,
-                         h2_grid, ngrid, &d, ptr<double>(ctx->outH2), status, &ctx->last_reduced_route))) return rc;
+  HostCall::In in;
+  if ((rc = hc.inputs(Y, n, m, G, p, K, Covar, ncov, weights, /*defer*/ true, &in)) ||
+      (rc = reduced_impl(ctx, opts, in.Y, n, m, in.G, p, in.Cov, in.ncov, in.K, in.W, h2_grid, ngrid, &d, ptr<double>(ctx->outH2), status,
+                         &ctx->last_reduced_route))) return rc;
   if (m > 0 && ((rc = hc.down(out->colmax, d.colmax, sizeof(double) * m)) || (rc = hc.down(out->argmax, d.argmax, sizeof(int64_t) * m)) ||
                 (rc = hc.down(alt ? nullptr : h2_out, ctx->outH2.p, sizeof(double) * m)))) return rc;
   if (out->want_triplets) {
@@ -1871,13 +1865,9 @@ static int reduced_async_impl(blmm_ctx* ctx, const blmm_opts* opts, const double
                               int64_t ngrid, const blmm_reduced* out, double* dh2_out, int64_t* dinfo) {
   int rc = reduced_check(ctx, opts, dY, n, m, dG, p, dK, out, dh2_out, "bulkscan_reduced_async");
   if (rc) return rc;
-  if (opts->method != BLMM_NULL_EXACT) {       // (grid_to_device checks it again; here: before anything is enqueued)
-    if (!h2_grid_host || ngrid < 1) return fail(ctx, BLMM_ERR_INVALID, "h2 grid is empty");
-    for (int64_t g = 0; g < ngrid; ++g)
-      if (std::isinf(h2_grid_host[g] / (1.0 - h2_grid_host[g]))) return fail(ctx, BLMM_ERR_H2_ONE, "Heritability of 1 is not allowed.");
-  }
-  BLMM_HIP(hipSetDevice(ctx->device));
-  if ((rc = check_sticky(ctx))) return rc;
+  // (grid_to_device checks the grid again; here: before anything is enqueued)
+  if (opts->method != BLMM_NULL_EXACT && (rc = check_grid(ctx, h2_grid_host, ngrid))) return rc;
+  if ((rc = enter_device(ctx))) return rc;
   // the side streams start behind everything already on the stream (a previous call's readers of the shared workspace)
   BLMM_HIP(hipEventRecord(ctx->ev_call, ctx->stream));
   BLMM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_call, 0));
@@ -1897,7 +1887,7 @@ static int reduced_async_impl(blmm_ctx* ctx, const blmm_opts* opts, const double
     ctx->grid_async = false;
     if (rc) return rc;
     if ((rc = launch_red_final(ctx, r, nslot, m, out->colmax, out->argmax))) return rc;
-    ctx->last_L = nullptr;                    // no matrix of this call: an earlier one is not served as its result
+    clear_last(ctx);                          // no matrix of this call: an earlier one is not served as its result
     return dinfo ? launch_red_info(ctx, ptr<int64_t>(ctx->stat), 0, out->want_triplets ? out->count : nullptr, dinfo) : BLMM_OK;
   }
   ctx->grid_async = true;
@@ -1927,8 +1917,7 @@ static int perms_pipeline(blmm_ctx* ctx, const blmm_opts* opts, Pipe& P, Timer& 
 // fp32 permutation path with its own fp32 rotation (kernels_scan_f32.hip: k_rotate_f32): intercept-only null model (the
 // conditioning guard of more covariates re-scans from the fp64 rotated markers), tuning key "f32_rotation"
 static bool f32_rotation_route(const blmm_ctx* ctx, const blmm_opts* o, const double* dCovar, int64_t ncov, int64_t nperms, int64_t p, bool f32) {
-  const int c_eff = (int)((ncov == 0 || !dCovar) ? 1 : ncov + (o->add_intercept ? 1 : 0));
-  return f32 && nperms > 0 && p > 0 && c_eff == 1 && ctx->tune.f32_rotation != 0;
+  return f32 && nperms > 0 && p > 0 && (int)null_cov(o, dCovar, ncov).c == 1 && ctx->tune.f32_rotation != 0;
 }
 
 static int scan_perms_impl(blmm_ctx* ctx, const blmm_opts* opts, const double* dy, int64_t n, const double* dG, int64_t p,
@@ -1941,8 +1930,7 @@ static int scan_perms_impl(blmm_ctx* ctx, const blmm_opts* opts, const double* d
   if (nperms < 0) return fail(ctx, BLMM_ERR_NPERMS, "The required number of permutations must be a positive integer.");
   if (!dy || !dG || !dK || !dscalars_out || !dlod_out || (nperms > 0 && !dLperms_out && !dLperms32_out))
     return fail(ctx, BLMM_ERR_INVALID, "scan_perms: NULL buffer");
-  BLMM_HIP(hipSetDevice(ctx->device));
-  if ((rc = check_sticky(ctx))) return rc;
+  if ((rc = enter_device(ctx))) return rc;
   Timer tm(ctx);
   Pipe P;
   // the library's own permutation indices depend on nothing in the call: generated on the side stream, beside the eigen-decomposition
@@ -1950,13 +1938,12 @@ static int scan_perms_impl(blmm_ctx* ctx, const blmm_opts* opts, const double* d
   ctx->perm_ready = false;
   bool perm_side = false;
   if (!dperm_idx && nperms > 0 && n > 256 && n <= 65535) {
-    hipStream_t main_stream = ctx->stream;
-    BLMM_HIP(hipEventRecord(ctx->ev_xt, main_stream));
+    BLMM_HIP(hipEventRecord(ctx->ev_xt, ctx->stream));
     BLMM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_xt, 0));
-    ctx->stream = ctx->side;
-    rc = launch_perm_gen(ctx, (int)n, nperms, seed);
-    ctx->stream = main_stream;
-    if (rc) return rc;
+    {
+      OnStream on(ctx, ctx->side);
+      if ((rc = launch_perm_gen(ctx, (int)n, nperms, seed))) return rc;
+    }
     BLMM_HIP(hipEventRecord(ctx->ev_m, ctx->side));
     perm_side = true;
   }
@@ -2068,20 +2055,24 @@ int blmm_scan_perms_prerotated_dev(blmm_ctx* ctx, const blmm_opts* opts, const d
   if (!dy || !dXt_blocks || !dscalars_out || !dlod_out || (nperms > 0 && !dLperms_out == !dLperms32_out))
     return fail(ctx, BLMM_ERR_INVALID, "scan_perms_prerotated: NULL buffer (exactly one of the fp64 / fp32 permutation matrices)");
   if (p < 0 || nblocks < 1 || block_cols < 1 || block_ld < block_cols || nblocks * block_cols < p) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
-  BLMM_HIP(hipSetDevice(ctx->device));
-  if ((rc = check_sticky(ctx))) return rc;
+  if ((rc = enter_device(ctx))) return rc;
   Timer tm(ctx);
   Pipe P = prepared_pipe(ctx);
-  BLMM_HIP(hipMemsetAsync(P.stat + 1, 0, sizeof(int64_t) * 4, ctx->stream));
-  BLMM_HIP(hipMemsetAsync(P.stat + 8, 0, sizeof(int64_t) * (NSTAT - 8), ctx->stream));
-  ctx->audit_ran = false;
-  ctx->brent_cnt_used = false;
+  if ((rc = reset_prepared(ctx, P, tm))) return rc;
   ctx->perm_ready = false;
-  tm.mark(); tm.mark();
   if ((rc = rotate_traits(ctx, P, dy, 1))) return rc;
   if ((rc = assemble_prerotated(ctx, P, p, dXt_blocks, nblocks, block_cols, block_ld))) return rc;
   tm.mark();
   return perms_pipeline(ctx, opts, P, tm, nperms, seed, dperm_idx, dscalars_out, dlod_out, dLperms_out, dLperms32_out, status);
+}
+
+// caller-supplied permutation indices (n x nperms) -> tmpC; nullptr: the library draws its own
+static int up_perm_idx(HostCall& hc, const int32_t* perm_idx, int64_t n, int64_t nperms, const int32_t** dperm) {
+  *dperm = nullptr;
+  if (!perm_idx || nperms <= 0) return BLMM_OK;
+  int rc = hc.up(hc.ctx->tmpC, perm_idx, sizeof(int32_t) * (size_t)n * nperms);
+  if (!rc) *dperm = ptr<int32_t>(hc.ctx->tmpC);
+  return rc;
 }
 
 static int scan_perms_host(blmm_ctx* ctx, const blmm_opts* opts, const double* y, int64_t n, const double* G, int64_t p,
@@ -2098,21 +2089,14 @@ static int scan_perms_host(blmm_ctx* ctx, const blmm_opts* opts, const double* y
   int rc;
   if ((rc = hc.begin()) || (rc = ensure(ctx, ctx->outL, sizeof(double) * (size_t)p + esz * (size_t)p * nperms)) ||
       (rc = ensure(ctx, ctx->outH2, sizeof(double) * 2))) return rc;
-  const double *dCov, *dW;
-  if ((rc = hc.up(ctx->inY, y, sizeof(double) * n)) || (rc = hc.up(ctx->inG, G, sizeof(double) * n * p)) ||
-      (rc = hc.up(ctx->inK, K, sizeof(double) * n * n)) || (rc = hc.up_opt(ctx->inCov, Covar, n * ncov, &dCov)) ||
-      (rc = hc.up_opt(ctx->inW, weights, n, &dW))) return rc;
-  const int32_t* dperm = nullptr;
-  if (perm_idx && nperms > 0) {
-    if ((rc = hc.up(ctx->tmpC, perm_idx, sizeof(int32_t) * (size_t)n * nperms))) return rc;
-    dperm = ptr<int32_t>(ctx->tmpC);
-  }
+  HostCall::In d;
+  const int32_t* dperm;
+  if ((rc = hc.inputs(y, n, 1, G, p, K, Covar, ncov, weights, false, &d)) || (rc = up_perm_idx(hc, perm_idx, n, nperms, &dperm))) return rc;
   double* dL = ptr<double>(ctx->outL);
   void* dLp = dL + p;                       // 8-byte aligned; the fp32 kernel needs 4
-  if ((rc = scan_perms_impl(ctx, opts, ptr<double>(ctx->inY), n, ptr<double>(ctx->inG), p, dCov, dCov ? ncov : 0, ptr<double>(ctx->inK), dW,
-                            nperms, seed, dperm, ptr<double>(ctx->outH2), dL,
+  if ((rc = scan_perms_impl(ctx, opts, d.Y, n, d.G, p, d.Cov, d.ncov, d.K, d.W, nperms, seed, dperm, ptr<double>(ctx->outH2), dL,
                             f32 ? nullptr : reinterpret_cast<double*>(dLp), f32 ? reinterpret_cast<float*>(dLp) : nullptr, status))) return rc;
-  ctx->last_L = reinterpret_cast<const double*>(dLp); ctx->last_p = p; ctx->last_m = nperms; ctx->last_f32 = f32;
+  set_last(ctx, reinterpret_cast<const double*>(dLp), p, nperms, f32);
   if ((rc = hc.down(scalars_out, ctx->outH2.p, sizeof(double) * 2)) || (rc = hc.down(lod_out, dL, sizeof(double) * p))) return rc;
   if (p > 0 && nperms > 0 && (rc = copy_to_host(ctx, Lperms_out, dLp, esz * (size_t)p * nperms))) return rc;
   return (rc = hc.finish()) ? rc : check_sticky(ctx);
@@ -2149,8 +2133,8 @@ static int bperm_check(blmm_ctx* ctx, const blmm_opts* opts, int64_t n, int64_t 
   if (n < 1 || m < 0 || p < 0 || ncov < 0 || m > 0x7fffffffLL || p > 0x7fffffffLL) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
   if (nperms > BPERM_MAX_NPERMS)
     return fail(ctx, BLMM_ERR_UNSUPPORTED, "bulkscan_perms: more than 16384 permutations (the per-trait sort runs in LDS)");
-  const int64_t c = (ncov == 0 || !Covar) ? 1 : ncov + (opts->add_intercept ? 1 : 0);
-  if (c > CTPL) return fail(ctx, BLMM_ERR_UNSUPPORTED, "bulkscan_perms: more than 8 null covariates (incl. intercept) are not supported");
+  if (null_cov(opts, Covar, ncov).c > CTPL)
+    return fail(ctx, BLMM_ERR_UNSUPPORTED, "bulkscan_perms: more than 8 null covariates (incl. intercept) are not supported");
   return BLMM_OK;
 }
 
@@ -2158,15 +2142,13 @@ static int bulk_perms_impl(blmm_ctx* ctx, const blmm_opts* opts, const double* d
                            const double* dCovar, int64_t ncov, const double* dK, const double* dweights, int64_t nperms, uint64_t seed,
                            const int32_t* dperm_idx, const double* probs, int64_t nprobs, const BpermOut& o, blmm_status* status) {
   int rc = bperm_check(ctx, opts, n, m, p, dCovar, ncov, nperms, probs, nprobs, dY && dG && dK, o);
-  if (rc) return rc;
-  BLMM_HIP(hipSetDevice(ctx->device));
-  if ((rc = check_sticky(ctx))) return rc;
+  if (rc || (rc = enter_device(ctx))) return rc;
   BpermProbs pr;
   for (int t = 0; t < 64; ++t) pr.v[t] = t < nprobs ? probs[t] : 0.0;
   Timer tm(ctx);
   Pipe P;
   ctx->perm_ready = false;
-  ctx->last_L = nullptr;                        // no matrix of this call (and the workspace it sat in is reused)
+  clear_last(ctx);                              // no matrix of this call (and the workspace it sat in is reused)
   // the traits are rotated as scan rotates its one (launch_rotate picks its kernel by the column count as well as by n)
   if ((rc = prepare(ctx, opts, dY, n, 0, dG, p, dCovar, ncov, dK, dweights, 1, P, tm))) return rc;
   P.m = m; P.ldy = round_up(m > 0 ? m : 1, 128);
@@ -2249,17 +2231,10 @@ int blmm_bulkscan_perms(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, i
   double* d = ptr<double>(ctx->outL);
   const BpermOut o{d, d + mm, d + 2 * mm, reinterpret_cast<int64_t*>(d + 3 * mm), max_perms_out ? d + (5 + nprobs) * mm : nullptr,
                    thr_out ? d + 5 * mm : nullptr, pval_out ? d + 4 * mm : nullptr};
-  const double *dCov, *dW;
-  if ((rc = hc.up(ctx->inY, Y, sizeof(double) * n * m)) || (rc = hc.up(ctx->inG, G, sizeof(double) * n * p)) ||
-      (rc = hc.up(ctx->inK, K, sizeof(double) * n * n)) || (rc = hc.up_opt(ctx->inCov, Covar, n * ncov, &dCov)) ||
-      (rc = hc.up_opt(ctx->inW, weights, n, &dW))) return rc;
-  const int32_t* dperm = nullptr;
-  if (perm_idx && nperms > 0) {
-    if ((rc = hc.up(ctx->tmpC, perm_idx, sizeof(int32_t) * (size_t)n * nperms))) return rc;
-    dperm = ptr<int32_t>(ctx->tmpC);
-  }
-  if ((rc = bulk_perms_impl(ctx, opts, ptr<double>(ctx->inY), n, m, ptr<double>(ctx->inG), p, dCov, dCov ? ncov : 0, ptr<double>(ctx->inK),
-                            dW, nperms, seed, dperm, probs, nprobs, o, status))) return rc;
+  HostCall::In in;
+  const int32_t* dperm;
+  if ((rc = hc.inputs(Y, n, m, G, p, K, Covar, ncov, weights, false, &in)) || (rc = up_perm_idx(hc, perm_idx, n, nperms, &dperm)) ||
+      (rc = bulk_perms_impl(ctx, opts, in.Y, n, m, in.G, p, in.Cov, in.ncov, in.K, in.W, nperms, seed, dperm, probs, nprobs, o, status))) return rc;
   if ((rc = hc.down(h2_out, o.h2, sizeof(double) * mm)) || (rc = hc.down(sigma2_out, o.sigma2, sizeof(double) * mm)) ||
       (rc = hc.down(lod_max_out, o.lod_max, sizeof(double) * mm)) || (rc = hc.down(lod_argmax_out, o.lod_argmax, sizeof(int64_t) * mm)) ||
       (rc = hc.down(pval_out, o.pval, sizeof(double) * mm)) || (rc = hc.down(thr_out, o.thr, sizeof(double) * mm * nprobs))) return rc;
@@ -2276,8 +2251,7 @@ int blmm_scan_alt_dev(blmm_ctx* ctx, const blmm_opts* opts, const double* dy, in
   int rc = check_opts(ctx, opts);
   if (rc) return rc;
   if (!dy || !dG || !dK || !dscalars_out || !dlod_out || !dh2_each_out) return fail(ctx, BLMM_ERR_INVALID, "scan_alt: NULL buffer");
-  BLMM_HIP(hipSetDevice(ctx->device));
-  if ((rc = check_sticky(ctx))) return rc;
+  if ((rc = enter_device(ctx))) return rc;
   Timer tm(ctx);
   Pipe P;
   if ((rc = prepare(ctx, opts, dy, n, 1, dG, p, dCovar, ncov, dK, dweights, 1, P, tm))) return rc;
@@ -2306,8 +2280,7 @@ int blmm_bulkscan_alt_exact_dev(blmm_ctx* ctx, const blmm_opts* opts, const doub
   if (rc) return rc;
   if (!dY || !dG || !dK || !dL_out || !dh2_panel_out || !dh2_null_out) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_alt_exact: NULL buffer");
   if (ldL < p || ldH < p) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_alt_exact: leading dimension < p");
-  BLMM_HIP(hipSetDevice(ctx->device));
-  if ((rc = check_sticky(ctx))) return rc;
+  if ((rc = enter_device(ctx))) return rc;
   Timer tm(ctx);
   Pipe P;
   if ((rc = prepare(ctx, opts, dY, n, m, dG, p, dCovar, ncov, dK, dweights, 1, P, tm))) return rc;
@@ -2336,16 +2309,13 @@ int blmm_bulkscan_alt_exact(blmm_ctx* ctx, const blmm_opts* opts, const double* 
   int rc;
   if ((rc = hc.begin()) || (rc = ensure(ctx, ctx->outL, sizeof(double) * 2 * (size_t)p * m)) || (rc = ensure(ctx, ctx->outH2, sizeof(double) * 2 * (size_t)m)))
     return rc;
-  const double *dCov, *dW;
-  if ((rc = hc.up(ctx->inY, Y, sizeof(double) * n * m)) || (rc = hc.up(ctx->inG, G, sizeof(double) * n * p)) ||
-      (rc = hc.up(ctx->inK, K, sizeof(double) * n * n)) || (rc = hc.up_opt(ctx->inCov, Covar, n * ncov, &dCov)) ||
-      (rc = hc.up_opt(ctx->inW, weights, n, &dW))) return rc;
+  HostCall::In d;
+  if ((rc = hc.inputs(Y, n, m, G, p, K, Covar, ncov, weights, false, &d))) return rc;
   double* dL = ptr<double>(ctx->outL);
   double* dH = dL + (size_t)p * m;
   double* dh2 = ptr<double>(ctx->outH2);
-  if ((rc = blmm_bulkscan_alt_exact_dev(ctx, opts, ptr<double>(ctx->inY), n, m, ptr<double>(ctx->inG), p, dCov, dCov ? ncov : 0,
-                                        ptr<double>(ctx->inK), dW, dL, p, dH, p, dh2, dh2 + m, status))) return rc;
-  ctx->last_L = dL; ctx->last_p = p; ctx->last_m = m; ctx->last_f32 = false;
+  if ((rc = blmm_bulkscan_alt_exact_dev(ctx, opts, d.Y, n, m, d.G, p, d.Cov, d.ncov, d.K, d.W, dL, p, dH, p, dh2, dh2 + m, status))) return rc;
+  set_last(ctx, dL, p, m);
   if ((rc = copy_to_host(ctx, L_out, dL, sizeof(double) * (size_t)p * m)) || (rc = copy_to_host(ctx, h2_panel_out, dH, sizeof(double) * (size_t)p * m)) ||
       (rc = hc.down(h2_null_out, dh2, sizeof(double) * (size_t)m)) || (rc = hc.down(sigma2_out, dh2 + m, sizeof(double) * (size_t)m))) return rc;
   return (rc = hc.finish()) ? rc : check_sticky(ctx);
@@ -2361,14 +2331,11 @@ int blmm_scan_alt(blmm_ctx* ctx, const blmm_opts* opts, const double* y, int64_t
   HostCall hc(ctx);
   int rc;
   if ((rc = hc.begin()) || (rc = ensure(ctx, ctx->outL, sizeof(double) * 2 * (size_t)p)) || (rc = ensure(ctx, ctx->outH2, sizeof(double) * 2))) return rc;
-  const double *dCov, *dW;
-  if ((rc = hc.up(ctx->inY, y, sizeof(double) * n)) || (rc = hc.up(ctx->inG, G, sizeof(double) * n * p)) ||
-      (rc = hc.up(ctx->inK, K, sizeof(double) * n * n)) || (rc = hc.up_opt(ctx->inCov, Covar, n * ncov, &dCov)) ||
-      (rc = hc.up_opt(ctx->inW, weights, n, &dW))) return rc;
+  HostCall::In d;
+  if ((rc = hc.inputs(y, n, 1, G, p, K, Covar, ncov, weights, false, &d))) return rc;
   double* dL = ptr<double>(ctx->outL);
-  if ((rc = blmm_scan_alt_dev(ctx, opts, ptr<double>(ctx->inY), n, ptr<double>(ctx->inG), p, dCov, dCov ? ncov : 0,
-                              ptr<double>(ctx->inK), dW, ptr<double>(ctx->outH2), dL, dL + p, status))) return rc;
-  ctx->last_L = dL; ctx->last_p = p; ctx->last_m = 1; ctx->last_f32 = false;
+  if ((rc = blmm_scan_alt_dev(ctx, opts, d.Y, n, d.G, p, d.Cov, d.ncov, d.K, d.W, ptr<double>(ctx->outH2), dL, dL + p, status))) return rc;
+  set_last(ctx, dL, p, 1);
   if ((rc = hc.down(scalars_out, ctx->outH2.p, sizeof(double) * 2)) || (rc = hc.down(lod_out, dL, sizeof(double) * p)) ||
       (rc = hc.down(h2_each_out, dL + p, sizeof(double) * p))) return rc;
   return (rc = hc.finish()) ? rc : check_sticky(ctx);
@@ -2386,13 +2353,11 @@ int blmm_rotate(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, int64_t n
   if (!Y || !G || !K || !Y0_out || !X0_out || !lambda_out) return fail(ctx, BLMM_ERR_INVALID, "rotate: NULL buffer");
   if (n < 1 || m < 1 || p < 1) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
   HostCall hc(ctx);
-  const double* dCov;
-  if ((rc = hc.begin()) || (rc = hc.up(ctx->inY, Y, sizeof(double) * n * m)) || (rc = hc.up(ctx->inG, G, sizeof(double) * n * p)) ||
-      (rc = hc.up(ctx->inK, K, sizeof(double) * n * n)) || (rc = hc.up_opt(ctx->inCov, Covar, n * ncov, &dCov))) return rc;
+  HostCall::In d;
+  if ((rc = hc.begin()) || (rc = hc.inputs(Y, n, m, G, p, K, Covar, ncov, nullptr, false, &d))) return rc;
   Timer tm(ctx);
   Pipe P;
-  if ((rc = prepare(ctx, opts, ptr<double>(ctx->inY), n, m, ptr<double>(ctx->inG), p, dCov, dCov ? ncov : 0,
-                    ptr<double>(ctx->inK), nullptr, 0, P, tm))) return rc;
+  if ((rc = prepare(ctx, opts, d.Y, n, m, d.G, p, d.Cov, d.ncov, d.K, nullptr, 0, P, tm))) return rc;
   if ((rc = ensure(ctx, ctx->outL, sizeof(double) * n * (size_t)(m > p ? m : p)))) return rc;
   double* tmp = ptr<double>(ctx->outL);
   if ((rc = launch_untranspose(ctx, P.Yt, P.ldy, (int)n, m, tmp)) || (rc = hc.down(Y0_out, tmp, sizeof(double) * n * m))) return rc;
@@ -2498,7 +2463,7 @@ int blmm_liteqtl_given_h2(blmm_ctx* ctx, const double* Y0, int64_t n, int64_t m,
   if ((rc = hc.up(ctx->h2, h2, sizeof(double) * m)) || (rc = ensure(ctx, ctx->outL, sizeof(double) * (size_t)p * m))) return rc;
   // the same kernel choice as bulkscan(method = null-exact): low-rank weights form with its residual guard unless
   // BLMM_EXACT=full, c = 4 or n beyond the basis kernel
-  if (!exact_full(ctx) && P.c <= 3 && n <= 6000) {
+  if (lowrank_form(ctx, P.c, n)) {
     Timer tm(ctx);
     if ((rc = lr_begin(ctx, P, /*wbasis_started*/ false))) return rc;
     if ((rc = lr_finish(ctx, P, nm, ptr<double>(ctx->h2), ptr<double>(ctx->outL), p, tm))) return rc;

@@ -24,9 +24,15 @@ constexpr int CFAST = 4;         // ... with the tuned forms (LDS-resident evalu
   case 5: M(5); break; case 6: M(6); break; case 7: M(7); break; case 8: M(8); break;
 constexpr int TILE_T = 64;       // traits per workgroup tile of the scan kernels
 constexpr int TILE_I = 128;      // markers per workgroup tile of the scan kernels
-constexpr int NSTAT = 64;        // device status counters ([24 + 20 r ..]: per panel region r, 8 counts of traits per weight-basis segment and the 9 placement cursors of k_lr_classify; [6],[7]: eigensolver clocks, [8]: weight-basis rank, [9]: its residual, [10]: traits re-scanned full rank, [11]: eigensolver abort code, [12..15]: shared-weights traits / the others of the two panel regions (k_lr_classify), [16..18]: StatIdx below)
+constexpr int NSTAT = 64;        // device status counters ([24 + 20 r ..]: per panel region r, 8 counts of traits per weight-basis segment and the 9 placement cursors of k_lr_classify)
 
 enum StatIdx { ST_NEG_EIG = 0, ST_NONPOS_W = 1, ST_ZERO_NORM = 2, ST_NAN_LOD = 3, ST_BRENT_MAXIT = 4, ST_JACOBI_SWEEPS = 5,
+               ST_EIG_CYCLES = 6, ST_EIG_TICKS = 7 /* the eigensolver's shader cycles / 100 MHz ticks */,
+               ST_LR_RANK = 8 /* weight-basis rank (< 0: the multi-workgroup basis kernel timed out) */,
+               ST_LR_RESID2 = 9 /* its largest squared residual, bits of a double */, ST_LR_FIX = 10 /* traits re-scanned full rank */,
+               ST_EIG_ABORT = 11 /* eigensolver abort code */,
+               ST_LR_SHARED0 = 12, ST_LR_OTHER0 = 13, ST_LR_SHARED1 = 14, ST_LR_OTHER1 = 15
+               /* per panel region (k_lr_classify): its shared-weights traits, the columns of the other class */,
                ST_H2_BOUNDARY = 16, ST_H2_MULTIMODAL = 17, ST_ILLCOND = 18,
                ST_EIG_FAST = 19 /* 1: the fast eigen path ran */, ST_EIG_BAD = 20 /* its largest check / bound, bits of a double: accepted up to 1.0 */,
                ST_BRENT_CNT = 21 /* [21..22]: hand-over counter of the split h2 search (kernels_prep.hip: launch_brent_t) */,
@@ -136,10 +142,11 @@ struct blmm_ctx {
   // reduce-in-epilogue kernels stood, 2 = through a resident L (no fused instantiation, or a trait needed a re-scan)
   blmm::RedArgs red_cur; int last_reduced_route = 0;
   // blmm_bulkscan_reduced_async: no host-blocking call in steady state.  grid_async: grid_to_device stages the caller's grid in
-  // a pinned slot (gstage: a slot is reused once its event says its copy has run; a new slot is added otherwise) instead of
-  // waiting for a pageable upload.  ev_call: recorded on the stream where a call starts; the side streams wait for it.
+  // a pinned slot (blmm_api.hip: stage_to_device; gstage: a slot is reused once its event says its copy has run; a new slot is
+  // added otherwise) instead of waiting for a pageable upload.  ev_call: recorded on the stream where a call starts; the side
+  // streams wait for it.
   bool grid_async = false;
-  struct GridSlot { double* h = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool used = false; };
+  struct GridSlot { void* h = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool used = false; };
   std::vector<GridSlot> gstage;
   hipEvent_t ev_call = nullptr;
   blmm::Tuning tune;                   // blmm_set_tuning
@@ -153,6 +160,12 @@ struct blmm_ctx {
 };
 
 namespace blmm {
+
+// The only writer of the matrix the blmm_last_* consumers serve (kernels_post.hip); clear_last: none
+inline void set_last(blmm_ctx* ctx, const double* L, int64_t p, int64_t m, bool f32 = false) {
+  ctx->last_L = L; ctx->last_p = p; ctx->last_m = m; ctx->last_f32 = f32;
+}
+inline void clear_last(blmm_ctx* ctx) { set_last(ctx, nullptr, 0, 0); }
 
 // ---- error helpers -------------------------------------------------------------------------------
 int fail(blmm_ctx* ctx, int code, const std::string& msg);
@@ -185,10 +198,11 @@ int copy_to_host(blmm_ctx* ctx, void* dst, const void* dsrc, size_t bytes);
 // host_path.hip: the host-pointer leg of an entry point that takes caller memory, one on the stack per call.  begin() selects the
 // device; up() copies a caller array into device memory on ctx->stream (the DevBuf form ensures the buffer first); up_opt() does so
 // for an optional input and yields nullptr for a null pointer or an empty array; defer_yg() leaves Y and G to prepare()
-// (blmm_ctx::up_pending); down() is a small device -> host copy on ctx->stream, skipped for a null destination (copy_to_host moves
-// the large blocks); finish() is the success path's final synchronisation.  Every other exit -- an error rc, a BLMM_HIP early
-// return, a failed ensure -- leaves through the destructor, which waits for the context's four streams: nothing the call enqueued
-// still reads caller memory or the context's input buffers once it has returned.
+// (blmm_ctx::up_pending); inputs() does all of it for the standard input set (In); down() is a small device -> host copy on
+// ctx->stream, skipped for a null destination (copy_to_host moves the large blocks); finish() is the success path's final
+// synchronisation.  Every other exit -- an error rc, a BLMM_HIP early return, a failed ensure -- leaves through the destructor,
+// which waits for the context's four streams: nothing the call enqueued still reads caller memory or the context's input buffers
+// once it has returned.
 struct HostCall {
   blmm_ctx* ctx;
   bool done = false;
@@ -201,6 +215,11 @@ struct HostCall {
   int up(DevBuf& b, const void* src, size_t bytes);
   int up_opt(DevBuf& b, const double* src, int64_t count, const double** dev);
   int defer_yg(const double* Y, size_t ybytes, const double* G, size_t gbytes);
+  // Y (n x m) -> inY and G (n x p) -> inG, deferred when `defer`; then K (n x n, unless NULL) -> inK, the optional covariates
+  // (n x ncov) -> inCov and weights (n) -> inW.  The device pointers come back with ncov = 0 when there are no covariates.
+  struct In { const double *Y, *G, *K, *Cov, *W; int64_t ncov; };
+  int inputs(const double* Y, int64_t n, int64_t m, const double* G, int64_t p, const double* K, const double* Covar, int64_t ncov,
+             const double* weights, bool defer, In* in);
   int down(void* dst, const void* dsrc, size_t bytes);
   int finish(bool sync = true);   // sync = false: the last copy has waited already (copy_to_host, the blmm_last_* consumers)
 };

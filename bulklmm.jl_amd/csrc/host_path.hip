@@ -175,6 +175,18 @@ int HostCall::defer_yg(const double* Y, size_t ybytes, const double* G, size_t g
   return BLMM_OK;
 }
 
+int HostCall::inputs(const double* Y, int64_t n, int64_t m, const double* G, int64_t p, const double* K, const double* Covar,
+                     int64_t ncov, const double* weights, bool defer, In* in) {
+  int rc;
+  if (defer) rc = defer_yg(Y, sizeof(double) * n * m, G, sizeof(double) * n * p);
+  else if (!(rc = up(ctx->inY, Y, sizeof(double) * n * m))) rc = up(ctx->inG, G, sizeof(double) * n * p);
+  if (rc || (K && (rc = up(ctx->inK, K, sizeof(double) * n * n))) || (rc = up_opt(ctx->inCov, Covar, n * ncov, &in->Cov)) ||
+      (rc = up_opt(ctx->inW, weights, n, &in->W))) return rc;
+  in->Y = ptr<double>(ctx->inY); in->G = ptr<double>(ctx->inG); in->K = K ? ptr<double>(ctx->inK) : nullptr;
+  in->ncov = in->Cov ? ncov : 0;
+  return BLMM_OK;
+}
+
 int HostCall::down(void* dst, const void* dsrc, size_t bytes) {
   if (dst && bytes) BLMM_HIP(hipMemcpyAsync(dst, dsrc, bytes, hipMemcpyDeviceToHost, ctx->stream));
   return BLMM_OK;

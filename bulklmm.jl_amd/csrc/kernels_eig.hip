@@ -370,7 +370,7 @@ __global__ void __launch_bounds__(512) k_sytrd(const double* __restrict__ A, int
            pf[0] / (n - 2), pf[1] / (n - 2), pf[2] / (n - 2), pf[3] / (n - 2), pf[4] / (n - 2));
 #endif
   if (aborted) {
-    if (g == 0 && t == 0) stat[11] = -7;   // reported as an eigensolver failure (blmm_api.hip: finish_status / k_sticky)
+    if (g == 0 && t == 0) stat[ST_EIG_ABORT] = -7;   // reported as an eigensolver failure (blmm_api.hip: finish_status / k_sticky)
     return;
   }
   if (g == 0 && t == 0) { d[n - 2] = akk; e[n - 2] = sx[n - 1]; }
@@ -493,7 +493,7 @@ __global__ void __launch_bounds__(64) k_tql_leaves(const double* __restrict__ d,
     }
   }
   __syncthreads();
-  if (failed && r == 0) stat[11] = -8;
+  if (failed && r == 0) stat[ST_EIG_ABORT] = -8;
 #ifdef TQL_DIAG
   if (failed && r == 0) {
     printf("tql leaf %d [%d,%d) failed; tnorm %g\n", (int)blockIdx.x, lo, hi, tnorm);

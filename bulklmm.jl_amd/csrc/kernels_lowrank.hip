@@ -66,7 +66,7 @@ __global__ void __launch_bounds__(WB_NS * TPS) k_wbasis(const double* __restrict
   __syncthreads();
   if (s_neg) {
     for (int e = t; e < n * n; e += NT) Q[e] = ((e / n) == (e % n)) ? 1.0 : 0.0;
-    if (t == 0) { rk[0] = n; rk[1] = (n + 3) / 4; stat[8] = n; }
+    if (t == 0) { rk[0] = n; rk[1] = (n + 3) / 4; stat[ST_LR_RANK] = n; }
     return;
   }
   // leading dimension of the sample columns: NS + 16 doubles.  In LDS the TPS row groups of a half-wave then fall into
@@ -172,7 +172,7 @@ __global__ void __launch_bounds__(WB_NS * TPS) k_wbasis(const double* __restrict
   }
 #undef WK
 #undef TPS_SUM
-  if (t == 0) { rk[0] = R; rk[1] = (R + 3) / 4; stat[8] = R; }
+  if (t == 0) { rk[0] = R; rk[1] = (R + 3) / 4; stat[ST_LR_RANK] = R; }
 }
 
 // Register-resident variant for n <= 4 * NKR: the 256 sample columns live in the registers of their 4 lanes (NKR values
@@ -201,7 +201,7 @@ __global__ void __launch_bounds__(1024) k_wbasis_reg(const double* __restrict__ 
   __syncthreads();
   if (s_neg) {
     for (int e = t; e < n * n; e += NT) Q[e] = ((e / n) == (e % n)) ? 1.0 : 0.0;
-    if (t == 0) { rk[0] = n; rk[1] = (n + 3) / 4; stat[8] = n; }
+    if (t == 0) { rk[0] = n; rk[1] = (n + 3) / 4; stat[ST_LR_RANK] = n; }
     return;
   }
   // one segment: delta_0 = 0 (w = 1), then log-spaced over [1e-6, 1e9] (h2 from 1e-6 to 1 - 1e-9).  Several: sample 0 is the
@@ -305,7 +305,7 @@ __global__ void __launch_bounds__(1024) k_wbasis_reg(const double* __restrict__ 
     res2 = r2;
     __syncthreads();
   }
-  if (t == 0) { rk[0] = R; rk[1] = (R + 3) / 4; atomicMax((unsigned long long*)&stat[8], (unsigned long long)R); }   // stat[8]: the largest rank over the segments
+  if (t == 0) { rk[0] = R; rk[1] = (R + 3) / 4; atomicMax((unsigned long long*)&stat[ST_LR_RANK], (unsigned long long)R); }   // the largest rank over the segments
 }
 
 // Multi-workgroup variant for n beyond the single-workgroup LDS budget.  The 256 sample columns are dealt S per
@@ -341,7 +341,7 @@ __global__ void __launch_bounds__(1024) k_wbasis_mw(const double* __restrict__ l
   __syncthreads();
   if (s_i0) {
     for (size_t e = (size_t)g * NT + t; e < (size_t)n * n; e += (size_t)G * NT) Q[e] = ((e / n) == (e % n)) ? 1.0 : 0.0;
-    if (g == 0 && t == 0) { rk[0] = n; rk[1] = (n + 3) / 4; stat[8] = n; }
+    if (g == 0 && t == 0) { rk[0] = n; rk[1] = (n + 3) / 4; stat[ST_LR_RANK] = n; }
     return;
   }
   // sample columns of this workgroup: global sample index s = g * S + ss (the log-spaced deltas of k_wbasis)
@@ -449,8 +449,8 @@ __global__ void __launch_bounds__(1024) k_wbasis_mw(const double* __restrict__ l
     }
   }
   if (g == 0 && t == 0) {
-    if (aborted) { rk[0] = -1; rk[1] = 0; stat[8] = -1; }
-    else { rk[0] = R; rk[1] = (R + 3) / 4; stat[8] = R; }
+    if (aborted) { rk[0] = -1; rk[1] = 0; stat[ST_LR_RANK] = -1; }
+    else { rk[0] = R; rk[1] = (R + 3) / 4; stat[ST_LR_RANK] = R; }
   }
 }
 
@@ -1076,8 +1076,8 @@ __global__ void __launch_bounds__(256) k_lr_panels_w(NullModel nm, const double*
 }
 
 // Guard of the low-rank form: relative residual |w_j - Q c_j| / |w_j| of the weight-basis expansion of EVERY trait,
-// evaluated directly (one thread per trait).  The largest squared value goes to stat[9]; a trait whose squared residual
-// exceeds tol2 is appended to flag_list (count in stat[10]) and its LOD column is recomputed by k_scan_fix from the full
+// evaluated directly (one thread per trait).  The largest squared value goes to stat[ST_LR_RESID2]; a trait whose squared residual
+// exceeds tol2 is appended to flag_list (count in stat[ST_LR_FIX]) and its LOD column is recomputed by k_scan_fix from the full
 // length-n sums, so no LOD leaves the library that rests on an unchecked expansion.
 // Stage 1: block (x: 256 traits, y: a 64-row slice of the n individuals) -> partial sums of |w - Qc|^2 and |w|^2 of the
 // slice, one thread per trait (coalesced reads of its coefficients Cp[r][j]; the slice of the basis rows in LDS).
@@ -1098,7 +1098,7 @@ __global__ void __launch_bounds__(256) k_lr_resid(int n, int64_t m, const double
     Q += (int64_t)sgi * qstride; rk += 4 * sgi;
   }
   const int R = rk[0];
-  if (R < 0) return;                       // the basis kernel gave up: the call fails as a whole (stat[8] < 0)
+  if (R < 0) return;                       // the basis kernel gave up: the call fails as a whole (stat[ST_LR_RANK] < 0)
   const int k0 = blockIdx.y * LRR_KS, kc = (n - k0 < LRR_KS) ? (n - k0) : LRR_KS;
   double* sLam = sh;                       // LRR_KS
   double* sQ = sh + LRR_KS;                // R x LRR_KS
@@ -1157,15 +1157,15 @@ __global__ void __launch_bounds__(256) k_lr_resid2(int nslice, int64_t m, double
     rel2 = rr / ww;
     if (!(rel2 >= 0.0)) rel2 = INFINITY;   // NaN counts as a failure of the expansion
     if (!(rel2 <= tol2)) {
-      const unsigned long long slot = atomicAdd((unsigned long long*)&stat[10], 1ull);
+      const unsigned long long slot = atomicAdd((unsigned long long*)&stat[ST_LR_FIX], 1ull);
       flag_list[slot] = (int)j;            // panel column; order of the list is immaterial: k_scan_fix recomputes whole columns
       if (flags) atomicOr(&flags[perm[j]], 1);   // (blmm_bulkscan_reduced_async) per trait
     }
   }
-  // largest squared residual of the block -> stat[9] (bit pattern of a non-negative double orders like an integer)
+  // largest squared residual of the block -> stat[ST_LR_RESID2] (bit pattern of a non-negative double orders like an integer)
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) rel2 = fmax(rel2, __shfl_xor(rel2, o, 64));
-  if ((threadIdx.x & 63) == 0 && rel2 > 0.0) atomicMax((unsigned long long*)&stat[9], (unsigned long long)__double_as_longlong(rel2));
+  if ((threadIdx.x & 63) == 0 && rel2 > 0.0) atomicMax((unsigned long long*)&stat[ST_LR_RESID2], (unsigned long long)__double_as_longlong(rel2));
 }
 
 // Full-rank recomputation of the LOD columns of the flagged traits (univar_liteqtl, src/bulkscan_helpers.jl:138-146):
@@ -1186,7 +1186,7 @@ __global__ void __launch_bounds__(256) k_scan_fix(NullModel nm, const double* __
                                                    const double* __restrict__ pvtab, RedArgs red) {
   constexpr int KC = 256, NL = C * (C + 1) / 2;
   __shared__ double s_a0[KC], s_w[KC], s_wz[C][KC];
-  const int64_t cnt = stat[10];
+  const int64_t cnt = stat[ST_LR_FIX];
   if (cnt <= 0) return;
   const int n = nm.n;
   const int64_t ntile = (p + 255) / 256;

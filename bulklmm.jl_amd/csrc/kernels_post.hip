@@ -152,11 +152,11 @@ __global__ void __launch_bounds__(256) k_red_final(const double* __restrict__ pm
 }
 
 // The info block of blmm_bulkscan_reduced_async (include/bulklmm_hip.h: BLMM_RINFO_*), written in stream order behind the call's
-// work.  A device-side failure (stat[8] < 0: the weight-basis kernel timed out at its grid barrier; stat[11]: the eigensolver's abort
-// code) also raises the context's sticky word, as k_sticky does, so that blmm_synchronize reports it.
+// work.  A device-side failure (stat[ST_LR_RANK] < 0: the weight-basis kernel timed out at its grid barrier; stat[ST_EIG_ABORT]:
+// the eigensolver's abort code) also raises the context's sticky word, as k_sticky does, so that blmm_synchronize reports it.
 __global__ void k_red_info(const int64_t* __restrict__ stat, int route, const int64_t* __restrict__ count, int64_t* __restrict__ info,
                            int64_t* hflag) {
-  const int64_t nfix = stat[10], nqr = stat[ST_ILLCOND];
+  const int64_t nfix = stat[ST_LR_FIX], nqr = stat[ST_ILLCOND];
   info[BLMM_RINFO_ROUTE] = route ? route : ((nfix > 0 || nqr > 0) ? 3 : 1);
   info[BLMM_RINFO_LOWRANK_RESCAN] = nfix;
   info[BLMM_RINFO_ILLCOND_RESCAN] = nqr;
@@ -166,8 +166,8 @@ __global__ void k_red_info(const int64_t* __restrict__ stat, int route, const in
   info[BLMM_RINFO_NONPOS_WEIGHT] = stat[ST_NONPOS_W];
   info[BLMM_RINFO_TRIPLETS] = count ? *count : 0;
   int64_t f = 0, code = 0;
-  if (stat[8] < 0) f |= 1;
-  if (stat[11] != 0) { f |= 2; code = stat[11]; }
+  if (stat[ST_LR_RANK] < 0) f |= 1;
+  if (stat[ST_EIG_ABORT] != 0) { f |= 2; code = stat[ST_EIG_ABORT]; }
   info[BLMM_RINFO_DEVICE_ERROR] = f ? ((f & 2) ? code : -1) : 0;
   if (f && hflag) {
     if (f & 2) hflag[1] = code;

@@ -520,8 +520,8 @@ __global__ void __launch_bounds__(1024) k_jacobi_lds(const double* __restrict__ 
     }
     if (tid == 0) {
       stat[ST_JACOBI_SWEEPS] = sweep + 1;
-      stat[6] = (int64_t)(__builtin_amdgcn_s_memtime() - dbg_t0);      // shader cycles spent in the eigensolver
-      stat[7] = (int64_t)(__builtin_amdgcn_s_memrealtime() - dbg_r0);  // 100 MHz ticks
+      stat[ST_EIG_CYCLES] = (int64_t)(__builtin_amdgcn_s_memtime() - dbg_t0);
+      stat[ST_EIG_TICKS] = (int64_t)(__builtin_amdgcn_s_memrealtime() - dbg_r0);
     }
   }
   for (int e = tid; e < nr * N; e += nt) {

@@ -88,7 +88,7 @@ int blmm_bulkscan(blmm_ctx* ctx, const blmm_opts* o, const double* Y, int64_t n,
   if ((rc = ensure(ctx, ctx->outH2, sizeof(double) * (size_t)((alt ? p * m : m) + 1)))) return rc;
   rc = blmm_bulkscan_dev(ctx, o, Y, n, m, G, p, C, nc, K, w, grid, ng, ptr<double>(ctx->outL), p, ptr<double>(ctx->outH2), st);
   if (rc) return rc;
-  ctx->last_L = ptr<double>(ctx->outL); ctx->last_p = p; ctx->last_m = m; ctx->last_f32 = false;
+  set_last(ctx, ptr<double>(ctx->outL), p, m);
   // through the real device -> host leg (staging ring + CopyPool when the block is large); L_out == NULL: the block stays "in HBM"
   if (L_out && p * m > 0 && (rc = copy_to_host(ctx, L_out, ctx->outL.p, sizeof(double) * (size_t)(p * m)))) return rc;
   if (h2_out && (rc = copy_to_host(ctx, h2_out, ctx->outH2.p, sizeof(double) * (size_t)(alt ? p * m : m)))) return rc;

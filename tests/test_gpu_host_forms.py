@@ -223,3 +223,207 @@ def test_lod_consumers_host_equal_dev(blmm):
     ctx.check(ctx.lib.blmm_get_thresholds_dev(ctx.h, vp(dLp), p, Lp.shape[1], p, host["probs"].ctypes.data_as(C.c_void_p), 3,
                                               got.ctypes.data_as(C.c_void_p)))
     same(host["thrs"], got)
+
+
+# ---- refusals: one bad argument per call, the exact (code, message) of blmm_last_error ------------------------------------------
+# The device forms refuse before they touch the device; the host forms marked after-uploads refuse in their device twin, behind
+# the HostCall uploads of their inputs.  Every output buffer is large enough for the call to run, should a check ever go missing.
+RN, RM, RP = 8, 3, 6
+OUT = 1 << 16
+INVALID, DIM, DECOMP, METHOD, NPERMS = -1, -2, -4, -5, -9
+UNKNOWN = "Unknown method; choose null-exact, null-grid or alt-grid."
+BAD_DECOMP = "Please choose either `eigen` or `svd` for decomposition of the kinship matrix."
+
+
+class RefusalEnv:
+    def __init__(self, blmm, ctx):
+        rng = np.random.Generator(np.random.PCG64(9100))
+        A = rng.standard_normal((RN, RN))
+        self.blmm, self.lib, self.h = blmm, ctx.lib, ctx.h
+        self.Y, self.G = rng.standard_normal(RN * RM), rng.standard_normal(RN * RP)
+        self.K, self.Cov = col(A @ A.T / RN + np.eye(RN)), rng.standard_normal(RN * RN)
+        self.w, self.grid = np.linspace(0.5, 2.0, RN), np.array([0.0, 0.3, 0.6])
+        self.perm = np.tile(np.arange(RN, dtype=np.int32), 4)
+        self.dY, self.dG, self.dK = DevBuf(self.Y), DevBuf(self.G), DevBuf(self.K)
+        self.dout = [DevBuf(nbytes=OUT) for _ in range(8)]
+        self.hout = [np.zeros(OUT // 8) for _ in range(8)]
+
+    def o(self, method=1, decomp="eigen"):
+        return C.byref(self.blmm.api._opts(method, decomp_scheme=decomp))
+
+    def d(self, i):
+        return self.dout[i].ptr
+
+    def hp(self, a):
+        return a.ctypes.data
+
+    def reduced(self, host, cap=0):
+        pick = self.hp if host else (lambda a: a.ptr)
+        out = self.hout if host else self.dout
+        return C.byref(self.blmm._lib.blmm_reduced(pick(out[0]), pick(out[1]), 0, 0.0, cap, None, None, None, pick(out[2])))
+
+    def prepare(self):
+        assert self.lib.blmm_prepare_dev(self.h, self.o(), RN, None, 0, self.dK.ptr, None, None) == 0
+
+
+def _bulkscan_dev(e, method=1, decomp="eigen", dY=True, ldL=RP):
+    return e.lib.blmm_bulkscan_dev(e.h, e.o(method, decomp), e.dY.ptr if dY else None, RN, RM, e.dG.ptr, RP, None, 0, e.dK.ptr, None,
+                                   e.hp(e.grid), 3, e.d(0), ldL, e.d(1), None)
+
+
+def _bulkscan(e, method=1, decomp="eigen", Y=True, ncov=0):
+    return e.lib.blmm_bulkscan(e.h, e.o(method, decomp), e.hp(e.Y) if Y else None, RN, RM, e.hp(e.G), RP, e.hp(e.Cov) if ncov else None,
+                               ncov, e.hp(e.K), e.hp(e.w), e.hp(e.grid), 3, e.hp(e.hout[0]), e.hp(e.hout[1]), None)
+
+
+def _reduced_async(e, method=1, armed=False, ngrid=3):
+    if armed:
+        assert e.lib.blmm_set_log10p_output(e.h, None, 0, 1) == 0
+    return e.lib.blmm_bulkscan_reduced_async(e.h, e.o(method), e.dY.ptr, RN, RM, e.dG.ptr, RP, None, 0, e.dK.ptr, None, e.hp(e.grid),
+                                             ngrid, e.reduced(False), e.d(3), e.d(4))
+
+
+def _prerotated(e, prepare=True, method=1, ldL=RP):
+    if prepare:
+        e.prepare()
+    return e.lib.blmm_bulkscan_prerotated_dev(e.h, e.o(method), e.dY.ptr, RM, RP, e.d(5), 1, RP, RP, e.hp(e.grid), 3, e.d(0), ldL,
+                                              e.d(1), None)
+
+
+def _perms_prerotated(e, prepare=True, both=False):
+    if prepare:
+        e.prepare()
+    return e.lib.blmm_scan_perms_prerotated_dev(e.h, e.o(), e.dY.ptr, RP, e.d(5), 1, RP, RP, 4, 7, None, e.d(0), e.d(1), e.d(2),
+                                                e.d(3) if both else None, None)
+
+
+def _loco_dev(e, chr_start=(0, 3, 6), method=1):
+    cs = np.asarray(chr_start, dtype=np.int64)
+    return e.lib.blmm_bulkscan_loco_dev(e.h, e.o(method), e.dY.ptr, RN, RM, e.dG.ptr, RP, e.hp(cs), len(cs) - 1, -1, None, 0, None,
+                                        e.hp(e.grid), 3, None, e.d(0), RP, e.d(1), None)
+
+
+def _loco(e, chr_start=(0, 3, 6), method=1):
+    cs = np.asarray(chr_start, dtype=np.int64)
+    return e.lib.blmm_bulkscan_loco(e.h, e.o(method), e.hp(e.Y), RN, RM, e.hp(e.G), RP, e.hp(cs), len(cs) - 1, -1, e.hp(e.Cov), 1,
+                                    e.hp(e.w), e.hp(e.grid), 3, e.hp(e.hout[0]), e.hp(e.hout[1]), None)
+
+
+def _kinship_loco(e, dev, chr_start):
+    cs = np.asarray(chr_start, dtype=np.int64)
+    f = e.lib.blmm_kinship_loco_dev if dev else e.lib.blmm_kinship_loco
+    return f(e.h, e.dG.ptr if dev else e.hp(e.G), RN, RP, e.hp(cs), len(cs) - 1, -1, e.d(0) if dev else e.hp(e.hout[0]))
+
+
+def _scan_perms(e, f32=False, decomp="eigen", nperms=4):
+    f = e.lib.blmm_scan_perms_f32 if f32 else e.lib.blmm_scan_perms
+    return f(e.h, e.o(0, decomp), e.hp(e.Y), RN, e.hp(e.G), RP, e.hp(e.Cov), 1, e.hp(e.K), e.hp(e.w), nperms, 7, e.hp(e.perm),
+             e.hp(e.hout[0]), e.hp(e.hout[1]), e.hp(e.hout[2]), None)
+
+
+def _scan_perms_dev(e, f32=False, nperms=4, scalars=True):
+    f = e.lib.blmm_scan_perms_f32_dev if f32 else e.lib.blmm_scan_perms_dev
+    return f(e.h, e.o(0), e.dY.ptr, RN, e.dG.ptr, RP, None, 0, e.dK.ptr, None, nperms, 7, None, e.d(0) if scalars else None, e.d(1),
+             e.d(2), None)
+
+
+def _bulk_perms(e, dev, decomp="eigen", nprobs=1, bad_perm=False):
+    probs = np.full(65, 0.05)
+    perm = e.perm.copy()
+    if bad_perm:
+        perm[5] = RN
+    if dev:
+        return e.lib.blmm_bulkscan_perms_dev(e.h, e.o(0, decomp), e.dY.ptr, RN, RM, e.dG.ptr, RP, None, 0, e.dK.ptr, None, 4, 7, None,
+                                             e.hp(probs), nprobs, *[e.d(i) for i in range(7)], None)
+    return e.lib.blmm_bulkscan_perms(e.h, e.o(0, decomp), e.hp(e.Y), RN, RM, e.hp(e.G), RP, e.hp(e.Cov), 1, e.hp(e.K), e.hp(e.w), 4, 7,
+                                     e.hp(perm), e.hp(probs), nprobs, *[e.hp(e.hout[i]) for i in range(7)], None)
+
+
+def _scan_alt(e, dev, decomp="eigen"):
+    if dev:
+        return e.lib.blmm_scan_alt_dev(e.h, e.o(0, decomp), e.dY.ptr, RN, e.dG.ptr, RP, None, 0, e.dK.ptr, None, e.d(0), e.d(1), None, None)
+    return e.lib.blmm_scan_alt(e.h, e.o(0, decomp), e.hp(e.Y), RN, e.hp(e.G), RP, e.hp(e.Cov), 1, e.hp(e.K), e.hp(e.w), e.hp(e.hout[0]),
+                               e.hp(e.hout[1]), e.hp(e.hout[2]), None)
+
+
+def _alt_exact(e, dev, decomp="eigen", ldH=RP):
+    if dev:
+        return e.lib.blmm_bulkscan_alt_exact_dev(e.h, e.o(0, decomp), e.dY.ptr, RN, RM, e.dG.ptr, RP, None, 0, e.dK.ptr, None, e.d(0), RP,
+                                                 e.d(1), ldH, e.d(2), e.d(3), None)
+    return e.lib.blmm_bulkscan_alt_exact(e.h, e.o(0, decomp), e.hp(e.Y), RN, RM, e.hp(e.G), RP, e.hp(e.Cov), 1, e.hp(e.K), e.hp(e.w),
+                                         *[e.hp(e.hout[i]) for i in range(4)], None)
+
+
+def _rotate(e, decomp="eigen", ncov=1):
+    return e.lib.blmm_rotate(e.h, e.o(0, decomp), e.hp(e.Y), RN, RM, e.hp(e.G), RP, e.hp(e.Cov), ncov, e.hp(e.K), *[e.hp(e.hout[i]) for i in range(3)],
+                             None)
+
+
+REFUSALS = {
+    "bulkscan_dev-null-Y": (lambda e: _bulkscan_dev(e, dY=False), INVALID, "bulkscan: NULL buffer"),
+    "bulkscan_dev-method": (lambda e: _bulkscan_dev(e, method=7), METHOD, UNKNOWN),
+    "bulkscan_dev-ldL": (lambda e: _bulkscan_dev(e, ldL=RP - 1), INVALID, "bulkscan: ldL < p"),
+    "bulkscan_dev-decomp": (lambda e: _bulkscan_dev(e, decomp="bad"), DECOMP, BAD_DECOMP),
+    "bulkscan-null-Y": (lambda e: _bulkscan(e, Y=False), INVALID, "bulkscan: NULL buffer"),
+    "bulkscan-method-after-uploads": (lambda e: _bulkscan(e, method=7), METHOD, UNKNOWN),
+    "bulkscan-decomp-after-uploads": (lambda e: _bulkscan(e, decomp="bad"), DECOMP, BAD_DECOMP),
+    "bulkscan-covariates-after-uploads": (lambda e: _bulkscan(e, ncov=RN), DIM, "Dimension mismatch."),
+    "bulkscan_reduced-method-after-uploads": (
+        lambda e: e.lib.blmm_bulkscan_reduced(e.h, e.o(7), e.hp(e.Y), RN, RM, e.hp(e.G), RP, e.hp(e.Cov), 1, e.hp(e.K), e.hp(e.w),
+                                              e.hp(e.grid), 3, e.reduced(True), e.hp(e.hout[3]), None), METHOD, UNKNOWN),
+    "bulkscan_reduced_dev-null-out": (
+        lambda e: e.lib.blmm_bulkscan_reduced_dev(e.h, e.o(), e.dY.ptr, RN, RM, e.dG.ptr, RP, None, 0, e.dK.ptr, None, e.hp(e.grid), 3,
+                                                  None, e.d(3), None), INVALID, "bulkscan_reduced: NULL buffer"),
+    "bulkscan_reduced_dev-triplets": (
+        lambda e: e.lib.blmm_bulkscan_reduced_dev(e.h, e.o(), e.dY.ptr, RN, RM, e.dG.ptr, RP, None, 0, e.dK.ptr, None, e.hp(e.grid), 3,
+                                                  e.reduced(False, cap=8), e.d(3), None), INVALID, "bulkscan_reduced: triplet buffers"),
+    "bulkscan_reduced_async-log10p": (lambda e: _reduced_async(e, armed=True), INVALID,
+                                      "bulkscan_reduced_async: a blmm_set_log10p_output request is pending (the reduced call writes no matrix)"),
+    "bulkscan_reduced_async-method": (lambda e: _reduced_async(e, method=7), METHOD, UNKNOWN),
+    "bulkscan_reduced_async-grid": (lambda e: _reduced_async(e, ngrid=0), INVALID, "h2 grid is empty"),
+    "prepare_dev-null-K": (lambda e: e.lib.blmm_prepare_dev(e.h, e.o(), RN, None, 0, None, None, None), INVALID, "prepare: NULL buffer"),
+    "prerotated_dev-unprepared": (lambda e: _prerotated(e, prepare=False), INVALID,
+                                  "bulkscan_prerotated: blmm_prepare_dev has not run on this context"),
+    "prerotated_dev-method": (lambda e: _prerotated(e, method=7), METHOD, UNKNOWN),
+    "prerotated_dev-ldL": (lambda e: _prerotated(e, ldL=RP - 1), INVALID, "bulkscan: ldL < p"),
+    "scan_perms_prerotated_dev-unprepared": (lambda e: _perms_prerotated(e, prepare=False), INVALID,
+                                             "scan_perms_prerotated: blmm_prepare_dev has not run on this context"),
+    "scan_perms_prerotated_dev-both": (lambda e: _perms_prerotated(e, both=True), INVALID,
+                                       "scan_perms_prerotated: NULL buffer (exactly one of the fp64 / fp32 permutation matrices)"),
+    "bulkscan_loco_dev-empty": (lambda e: _loco_dev(e, (0, 3, 3, 6)), INVALID, "bulkscan_loco: chromosome 1 is empty"),
+    "bulkscan_loco_dev-start": (lambda e: _loco_dev(e, (1, 3, 6)), INVALID, "bulkscan_loco: chromosome offsets must run from 0 to p"),
+    "bulkscan_loco_dev-one": (lambda e: _loco_dev(e, (0, 6)), INVALID,
+                              "bulkscan_loco: leave-one-chromosome-out needs at least 2 chromosomes"),
+    "bulkscan_loco_dev-method": (lambda e: _loco_dev(e, method=7), METHOD, UNKNOWN),
+    "bulkscan_loco-order": (lambda e: _loco(e, (0, 4, 2, 6)), INVALID, "bulkscan_loco: chromosome offsets are not increasing"),
+    "bulkscan_loco-method-after-uploads": (lambda e: _loco(e, method=7), METHOD, UNKNOWN),
+    "kinship_loco-every-marker": (lambda e: _kinship_loco(e, False, (0, 6, 6)), INVALID,
+                                  "kinship_loco: a chromosome holds every marker (no kinship is left)"),
+    "kinship_loco_dev-empty": (lambda e: _kinship_loco(e, True, (0, 3, 3, 6)), INVALID, "kinship_loco: chromosome 1 is empty"),
+    "scan_perms-decomp-after-uploads": (lambda e: _scan_perms(e, decomp="bad"), DECOMP, BAD_DECOMP),
+    "scan_perms_f32-decomp-after-uploads": (lambda e: _scan_perms(e, f32=True, decomp="bad"), DECOMP, BAD_DECOMP),
+    "scan_perms_dev-null": (lambda e: _scan_perms_dev(e, scalars=False), INVALID, "scan_perms: NULL buffer"),
+    "scan_perms_f32_dev-nperms": (lambda e: _scan_perms_dev(e, f32=True, nperms=-1), NPERMS,
+                                  "The required number of permutations must be a positive integer."),
+    "bulkscan_perms-perm_idx": (lambda e: _bulk_perms(e, False, bad_perm=True), INVALID,
+                                "bulkscan_perms: perm_idx entries must lie in 0 .. n - 1"),
+    "bulkscan_perms-decomp": (lambda e: _bulk_perms(e, False, decomp="bad"), DECOMP, BAD_DECOMP),
+    "bulkscan_perms_dev-levels": (lambda e: _bulk_perms(e, True, nprobs=65), INVALID, "bulkscan_perms: 0 .. 64 threshold levels"),
+    "scan_alt-decomp-after-uploads": (lambda e: _scan_alt(e, False, decomp="bad"), DECOMP, BAD_DECOMP),
+    "scan_alt_dev-null": (lambda e: _scan_alt(e, True), INVALID, "scan_alt: NULL buffer"),
+    "bulkscan_alt_exact-decomp-after-uploads": (lambda e: _alt_exact(e, False, decomp="bad"), DECOMP, BAD_DECOMP),
+    "bulkscan_alt_exact_dev-ldH": (lambda e: _alt_exact(e, True, ldH=RP - 1), INVALID, "bulkscan_alt_exact: leading dimension < p"),
+    "rotate-decomp": (lambda e: _rotate(e, decomp="bad"), DECOMP, BAD_DECOMP),
+    "rotate-covariates-after-uploads": (lambda e: _rotate(e, ncov=RN), DIM, "Dimension mismatch."),
+}
+
+
+@pytest.mark.parametrize("case", list(REFUSALS))
+def test_entry_point_refusals(blmm, case):
+    call, code, msg = REFUSALS[case]
+    ctx = blmm.Context(0)
+    e = RefusalEnv(blmm, ctx)
+    rc = call(e)
+    assert (rc, ctx.lib.blmm_last_error(ctx.h).decode()) == (code, msg)
+    ctx.synchronize()
+    ctx.close()
