@@ -1078,7 +1078,7 @@ int blmm_lod_colmax(blmm_ctx* ctx, const double* L, int64_t p, int64_t m, double
 // host-pointer forms of the consumers (upload, reduce on the device, download the small result)
 int blmm_lod2log10p(blmm_ctx* ctx, const double* L, int64_t p, int64_t m, int64_t chisq_df, double* P_out) {
   if (!ctx) return BLMM_ERR_INVALID;
-  if (!L || !P_out || p < 0 || m < 0 || chisq_df < 1) return fail(ctx, BLMM_ERR_INVALID, "lod2log10p: bad arguments");
+  if (!L || !P_out || p < 0 || m < 0 || chisq_df < 1 || chisq_df > 1000000) return fail(ctx, BLMM_ERR_INVALID, "lod2log10p: bad arguments");
   if ((size_t)p * m == 0) return BLMM_OK;
   HostCall hc(ctx);
   int rc;

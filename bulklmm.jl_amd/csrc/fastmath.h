@@ -2,7 +2,8 @@
 // On MI355X the fp64 MFMA and fp64 VALU instructions execute exclusively of each other on a SIMD
 // (tools/mb2_f64.hip), so every VALU instruction of an epilogue is paid in matrix-pipe time: the OCML
 // log10 (~50 instruction slots) and IEEE division (~16) are replaced by a 128-entry table + degree-8
-// polynomial (~20 slots, <= 1 ulp-ish, full relative accuracy as x -> 1) and rcp + 2 Newton steps.
+// polynomial (~20 slots, <= 1.5 ulp measured, full relative accuracy as x -> 1) and rcp + 2 Newton steps.
+// Every figure quoted below is measured by tests/test_gpu_fastmath.py against long double / mpmath references.
 // Table: log_table.h (tools/gen_log_table.py).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -22,7 +23,9 @@ __device__ __forceinline__ void stage_log_table(dpair* lds, const double* __rest
     lds[i] = (dpair){gtab[3 * i], gtab[3 * i + (LOG10 ? 2 : 1)]};
 }
 
-// log10(x) (LOG10) or ln(x) for a positive, finite, normal x.  lds: table staged by stage_log_table.
+// log10(x) (LOG10) or ln(x) for a positive, finite, normal x: <= 1.5 ulp (ln), 1.3 ulp (log10) over every exponent.  A subnormal
+// x gives a wrong value (its mantissa is read as a normal one's): callers keep them away.
+// lds: table staged by stage_log_table.
 template <bool LOG10>
 __device__ __forceinline__ double fast_log(double x, const dpair* __restrict__ lds) {
   const uint32_t hi = (uint32_t)__double2hiint(x), lo = (uint32_t)__double2loint(x);
@@ -47,7 +50,7 @@ __device__ __forceinline__ double fast_log(double x, const dpair* __restrict__ l
 
 // ---- LOD form: scale * log10(x) with `scale` folded into the table and the polynomial ---------------------
 // lds[i] = {invc, scale * log10(c)} (stage_lod_table); one multiply and one polynomial term fewer per output than
-// scale * fast_log<true>(x): relative error <= ~3e-16 on (0, 1].
+// scale * fast_log<true>(x): <= 2.3 ulps (the staged scale * log10(c) is rounded once more).
 __device__ __forceinline__ void stage_lod_table(dpair* lds, const double* __restrict__ gtab, double scale) {
   for (int i = threadIdx.x; i < BLMM_LOG_TABLE_N; i += blockDim.x)
     lds[i] = (dpair){gtab[3 * i], scale * gtab[3 * i + 2]};
@@ -86,8 +89,9 @@ __device__ __forceinline__ double fast_lod(double x, const dpair* __restrict__ l
 // those four octaves the table is indexed by the high word of u alone -- no exponent extraction, no mantissa re-assembly, no
 // int -> double conversion, and |r| <= 2^-10 leaves a degree-5 polynomial: 6 fp64 and 4 integer instructions per output where
 // fast_lod has 11 + 7 (every fp64 VALU instruction of an epilogue is paid in matrix-pipe time, see the file header).
-// Relative error <= ~2e-16 on [2^-4, 1] including u -> 1 (the last entry has c = 1: r = u - 1 exactly); lod_fast_ok(u) tells
-// whether u is in the table's range, lod_slow() serves the rest (u < 2^-4, u <= 0, NaN) with the reference's own operations.
+// Relative error <= 3.2e-16 on [2^-4, 1] (every high word, n = 3 .. 2048) including u -> 1 (the last entry has c = 1: r = u - 1
+// exactly), within 3 ulps of libm's scale * log10(u); lod_fast_ok(u) tells whether u is in the table's range, lod_out_of_range()
+// serves the rest (u < 2^-4, u <= 0, NaN).
 struct LodPoly5 { double c1, c2, c3, c4, c5; };
 // host side: {scale, c1..c5} for ScanArgs::lodc
 inline void lod_poly5_host(double scale, double (&out)[6]) {
@@ -129,7 +133,7 @@ __device__ __forceinline__ bool lod_fast_ok(double u) {
 }
 __device__ __forceinline__ double fast_lod5(double u, const dpair* __restrict__ lds, const LodPoly5& P) {
   uint32_t off = (((uint32_t)__double2hiint(u) + (0x400u - BLMM_LOD_HI0)) >> 7) & 0xfff0u;   // 16 * ((hi - HI0 + 2^10) >> 11)
-  off = off < 16u * (BLMM_LOD_TABLE_N - 1) ? off : 16u * (BLMM_LOD_TABLE_N - 1);             // out-of-range u: any entry (lod_slow replaces the value)
+  off = off < 16u * (BLMM_LOD_TABLE_N - 1) ? off : 16u * (BLMM_LOD_TABLE_N - 1);             // out-of-range u: any entry (lod_out_of_range replaces the value)
   const dpair e = *reinterpret_cast<const dpair*>(reinterpret_cast<const char*>(lds) + off);
   const double r = fma(u, e[0], -1.0);
   double p = P.c5;
@@ -140,7 +144,8 @@ __device__ __forceinline__ double fast_lod5(double u, const dpair* __restrict__ 
   return fma(r, p, e[1]);
 }
 // r2lod outside the table's range (src/bulkscan_helpers.jl:22-24: scale * log10(u)).  0 < u < 2^-4 is brought into the table by
-// an exact power of 16: scale log10(u) = fast_lod5(u 16^sh) - sh (4 scale log10 2), u 16^sh in [2^-4, 1) -- no libm call (its
+// an exact power of 16: scale log10(u) = fast_lod5(u 16^sh) - sh (4 scale log10 2), u 16^sh in [2^-4, 1), <= 2e-16 relative down
+// to the smallest subnormal -- no libm call (its
 // log10 is ~200 instructions and ~40 registers at every call site of kernels that sit at the register limit).  u = 0 -> +Inf;
 // u < 0 (r^2 > 1: DomainError in Julia) or NaN -> NaN, counted in *nnan when `counted`.
 __device__ __forceinline__ double lod_out_of_range(double u, const dpair* __restrict__ lds, const LodPoly5& P, double scale,
@@ -159,7 +164,8 @@ __device__ __forceinline__ double lod_out_of_range(double u, const dpair* __rest
 // ---- -log10 p of a LOD score, one degree of freedom, inside a scan epilogue (`output_pvals`, src/bulkscan.jl:154-157;
 // lod2log10p, src/util.jl:199-206 with chisq_df = 1) --------------------------------------------------------------------------
 //   -log10 erfc(x) = LOD + x w(x),  x = sqrt(LOD ln 10),  w(x) = -log10(erfcx(x)) / x
-// w: bucketed degree-7 polynomials (pval_table.h, tools/gen_pval_table.py: 4.3e-15 relative on the whole range); both terms are
+// w: bucketed degree-7 polynomials (pval_table.h, tools/gen_pval_table.py: 4.3e-15 relative up to x = 16384, the asymptotic series
+// of erfc beyond); both terms are
 // non-negative.  LOD <= 0 -> 0 (the reference's logccdf of a non-positive statistic), NaN -> NaN, +Inf -> +Inf; LOD < 1e-290
 // (p = 1 - 1e-145) -> 0.  ~20 fp64 operations + four 16-byte LDS reads per value, against ~150 of the erfc / erfcx / log route
 // of kernels_post.hip (which stays the general-df path).
@@ -193,7 +199,15 @@ __device__ __forceinline__ double fast_log10p1(double lod, const dpair* __restri
   double x = t * y;
   x = fma(fma(-x, x, t), h, x);
   x = fma(fma(-x, x, t), h, x);
-  if (!(x < 16384.0)) return lod;                         // beyond the table (LOD >= 1.2e8, +Inf): x w(x) < 1e-8 LOD
+  if (!(x < 16384.0)) {
+    // beyond the table (LOD >= 1.166e8; from LOD ~ 7.8e307 on, t overflows and x is NaN): the asymptotic series of erfc,
+    //   x w(x) = -log10 erfcx(x) = log10(x sqrt(pi)) + 1 / (2 ln 10 x^2) + O(x^-4),  log10(x sqrt(pi)) = (log10(LOD) + log10(pi ln 10)) / 2,
+    // log10(LOD) from the fp32 log2 of its mantissa: the term's absolute error (< 3e-8) is < 3e-16 of LOD.  Not on the hot path.
+    if (!(lod < INFINITY)) return lod;
+    const int e = __builtin_amdgcn_frexp_exp(lod);
+    const float lm = __log2f((float)__builtin_amdgcn_ldexp(lod, -e));
+    return lod + (0.5 * fma((double)e + (double)lm, BLMM_LOG10_2, 0.8593655613935971) + 0.09430584850580696 / lod);
+  }
   const uint32_t hi = (uint32_t)__double2hiint(x);
   const bool first = hi < BLMM_PV_HI0;                    // x < 2^-12: bucket 0, polynomial in x itself
   const uint32_t b = first ? 0u : 1u + ((hi - BLMM_PV_HI0) >> BLMM_PV_SHIFT);
@@ -212,7 +226,7 @@ __device__ __forceinline__ double fast_log10p1(double lod, const dpair* __restri
   return fma(x, w, lod);
 }
 
-// 1/x to ~20 ulp (2.2e-15 relative, tools/mb4_rcp.hip): v_rcp_f64 seed (4.6e-8) + ONE Newton step.  Used where the quotient
+// 1/x to ~10 ulp (<= 2.2e-15 relative, 2.0e-15 measured): v_rcp_f64 seed (4.6e-8) + ONE Newton step.  Used where the quotient
 // feeds 1 - r^2 of a LOD: its error there is far below the rounding of the subtraction.
 __device__ __forceinline__ double fast_rcp1(double x) {
   const double y = __builtin_amdgcn_rcp(x);
@@ -220,13 +234,49 @@ __device__ __forceinline__ double fast_rcp1(double x) {
   return fma(y, e, y);
 }
 
-// 1/x to ~1 ulp: v_rcp_f64 seed + two Newton steps (x finite, non-zero, normal)
+// 1/x to <= 1 ulp (0.5 measured over every exponent whose reciprocal is normal): v_rcp_f64 seed + two Newton steps
+// (x finite, non-zero, normal)
 __device__ __forceinline__ double fast_rcp(double x) {
   double y = __builtin_amdgcn_rcp(x);
   double e = fma(-x, y, 1.0);
   y = fma(y, e, y);
   e = fma(-x, y, 1.0);
   return fma(y, e, y);
+}
+
+// 1/sqrt(x), x > 0 normal, <= 1 ulp (0.96 measured): v_rsq_f64 seed + two Newton steps on y (the Jacobi rotations and the Cholesky
+// of the h2 search)
+__device__ __forceinline__ double nr_rsqrt(double x) {
+  double y = __builtin_amdgcn_rsq(x);
+  double h = 0.5 * x * y;
+  y = fma(y, fma(-h, y, 0.5), y);
+  h = 0.5 * x * y;
+  return fma(y, fma(-h, y, 0.5), y);
+}
+
+// 1/sqrt(h) from v_rsq_f64 (good to ~5e-8) and two Newton steps, <= 1 ulp (0.96 measured), for h > 0 normal: the QL rotations take one of these
+// instead of an IEEE sqrt followed by an IEEE division (~400 dependent cycles)
+__device__ __forceinline__ double fast_rsqrt(double h) {
+  double y = __builtin_amdgcn_rsq(h);
+  double e = fma(-h * y, y, 1.0);
+  y = fma(0.5 * y, e, y);
+  e = fma(-h * y, y, 1.0);
+  return fma(0.5 * y, e, y);
+}
+
+// fp32 LOD of the permutation scan (k_scan_f32): scale * ln(u), u = 1 - r^2 (scale = -n / (2 ln 10) in fp32), with the rounding
+// e of the subtraction put back to first order, ln(u + e) ~ ln(u) + e / u.  r^2 = 1 -> +Inf; r^2 > 1 (DomainError in Julia) or
+// NaN -> NaN, counted in *nnan when `counted`.  Over every fp32 r^2 in [0, 1] (n = 2048) against the fp64 log1p: within 2.5e-4 of the
+// permutation scans' contract 1e-3 |ref| + 1e-4, and 2.5e-7 relative wherever LOD >= 1.
+__device__ __forceinline__ float lod_f32(float r2, float scale, bool counted, int* nnan) {
+  const float u = 1.0f - r2;
+  const float e = (1.0f - u) - r2;
+  float lod = scale * fmaf(e, __builtin_amdgcn_rcpf(u), __logf(u));
+  if (__builtin_expect(!(u > 0.0f), 0)) {
+    lod = (u == 0.0f) ? INFINITY : NAN;
+    *nnan += (u != 0.0f) && counted;
+  }
+  return lod;
 }
 
 // Sum over the aligned groups of LPT lanes (LPT a power of two <= 64); every lane of a group gets the group's total.

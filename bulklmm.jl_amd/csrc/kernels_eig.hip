@@ -14,6 +14,7 @@
 // tools/dc_prototype.py is the NumPy model of exactly this data flow (same conventions, same tolerances).
 // Eigenvalues come out ascending; eigenvector i is evec[i*n .. i*n+n) (what k_post_eigen expects).
 #include "blmm_internal.h"
+#include "fastmath.h"
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -81,15 +82,6 @@ __device__ __forceinline__ void wsum4(double& d0, double& d1, double& d2, double
   x = swap_rows_sum(x, false);                                         // rows 0+1, 2+3
   x = swap_rows_sum(x, true);                                          // both half-waves
   d0 = lane_bcast(x, 0); d1 = lane_bcast(x, 1); d2 = lane_bcast(x, 2); d3 = lane_bcast(x, 3);
-}
-// 1/sqrt(h) from v_rsq_f64 (good to ~5e-8) and two Newton steps (~1 ulp), for h > 0: the QL rotations take one of these
-// instead of an IEEE sqrt followed by an IEEE division (~400 dependent cycles)
-__device__ __forceinline__ double fast_rsqrt(double h) {
-  double y = __builtin_amdgcn_rsq(h);
-  double e = fma(-h * y, y, 1.0);
-  y = fma(0.5 * y, e, y);
-  e = fma(-h * y, y, 1.0);
-  return fma(0.5 * y, e, y);
 }
 // sum over the workgroup; every thread gets the result.  red: >= 16 doubles of LDS.  Two barriers.
 __device__ __forceinline__ double block_sum(double x, double* red) {

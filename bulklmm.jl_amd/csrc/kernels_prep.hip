@@ -59,20 +59,6 @@ int launch_design(blmm_ctx* ctx, const double* dK, const double* dCovar, int nco
 // (2) columns p,q of A and V are rotated; (3) rows p,q of A are rotated.  No cross-lane reductions.
 // The work-item -> (pair slot, matrix, row) map is the same in every round and is kept in registers.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double nr_rsqrt(double x) {  // 1/sqrt(x), x > 0 normal: v_rsq_f64 + two Newton steps
-  double y = __builtin_amdgcn_rsq(x);
-  double h = 0.5 * x * y;
-  y = fma(y, fma(-h, y, 0.5), y);
-  h = 0.5 * x * y;
-  return fma(y, fma(-h, y, 0.5), y);
-}
-__device__ __forceinline__ double nr_rcp(double x) {
-  double y = __builtin_amdgcn_rcp(x);
-  double e = fma(-x, y, 1.0);
-  y = fma(y, e, y);
-  e = fma(-x, y, 1.0);
-  return fma(y, e, y);
-}
 
 // LDS variant (n <= JAC_NMAX): every workgroup of the launch runs the SAME deterministic iteration on its own LDS
 // copy of A (bitwise identical rotations, so no inter-workgroup synchronisation is ever needed) and accumulates
@@ -1405,9 +1391,11 @@ __device__ __forceinline__ EllOut null_ell_reg(double h2, const NullRegs<C, LPT>
   const double num = rss + prior_a * prior_b;
   const double den = (reml ? (double)(n - C) : (double)n) + prior_df;
   const double sigma2 = num * fast_rcp(den);
-  const double ls = (sigma2 > 0.0) ? fast_log<false>(sigma2, s_ln) : log(sigma2);
+  // fast_log takes normal x only (a subnormal's mantissa is read as a normal one's): sigma2 and detA below DBL_MIN go to libm.
+  // p1 and p2 are products of t = 1 + delta lambda > 0 factors (delta >= 0, lambda >= 0 up to rounding): >= ~1, never subnormal.
+  const double ls = (sigma2 >= 2.2250738585072014e-308) ? fast_log<false>(sigma2, s_ln) : log(sigma2);
   double ell = -0.5 * (((double)n + prior_b) * ls + logsum + den);  // (rss + a b)/sigma2 = den
-  if (reml) ell += 0.5 * ((double)C * ls - ((detA > 0.0) ? fast_log<false>(detA, s_ln) : log(detA)));
+  if (reml) ell += 0.5 * ((double)C * ls - ((detA >= 2.2250738585072014e-308) ? fast_log<false>(detA, s_ln) : log(detA)));
   EllOut o; o.ell = ell; o.sigma2 = sigma2; o.yy = rss;
   return o;
 }

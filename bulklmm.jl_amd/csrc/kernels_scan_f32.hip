@@ -16,6 +16,7 @@
 // a lane owns NB = 4 consecutive markers: one 16-byte store per (register, permutation), 32 lanes = 512 contiguous
 // bytes of one L_perms column.  Workgroup = 4 waves (2 x 2) = 128 permutations x 256 markers, no LDS.
 #include "blmm_internal.h"
+#include "fastmath.h"
 #include <cmath>
 
 namespace blmm {
@@ -399,15 +400,7 @@ __global__ void __launch_bounds__(256, 2) k_scan_f32(ScanF32Args a, int ntile_i,
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb) {
         const float rr = acc[mb][nb][reg] * sc[nb];
-        const float r2 = rr * rr;
-        const float u = 1.0f - r2;
-        const float e = (1.0f - u) - r2;
-        float lod = scale * fmaf(e, __builtin_amdgcn_rcpf(u), __logf(u));
-        if (__builtin_expect(!(u > 0.0f), 0)) {   // r^2 = 1 -> +Inf; r^2 > 1 -> DomainError in Julia, NaN here
-          lod = (u == 0.0f) ? INFINITY : NAN;
-          nnan += (u != 0.0f) && (ibase + nb < a.p) && (trait < a.m);
-        }
-        out[nb] = lod;
+        out[nb] = lod_f32(rr * rr, scale, (ibase + nb < a.p) && (trait < a.m), &nnan);
       }
       if (trait < a.m) {
         float* dst = a.L + trait * a.ldL + ibase;

@@ -480,7 +480,8 @@ int blmm_lod_colmax_dev(blmm_ctx* ctx, const double* dL, int64_t p, int64_t m, i
 
 /* ---- -log10 p-values: lod2log10p.(L, chisq_df)  (src/util.jl:199-206; `output_pvals`, src/bulkscan.jl:154-157,
  * src/scan.jl:353-355).  df = 1: LOD + x w(x), x = sqrt(LOD ln 10), w = -log10(erfcx(x)) / x from bucketed polynomials
- * (4e-15 relative; BLMM_PVAL_LIBM=1: erfc / erfcx / log instead); general df through ln Q(df/2, .) in log space. */
+ * (4e-15 relative; BLMM_PVAL_LIBM=1: erfc / erfcx / log instead); general df through ln Q(df/2, .) in log space.  chisq_df runs
+ * from 1 to 10^6 at every entry point that takes one (here, blmm_set_log10p_output, blmm_last_log10p): BLMM_ERR_INVALID beyond. */
 int blmm_lod2log10p(blmm_ctx* ctx, const double* L, int64_t p, int64_t m, int64_t chisq_df, double* P_out);
 int blmm_lod2log10p_dev(blmm_ctx* ctx, const double* dL, int64_t p, int64_t m, int64_t ldL, int64_t chisq_df, double* dP_out,
                         int64_t ldP);

@@ -416,6 +416,13 @@ REFUSALS = {
     "rotate-decomp": (lambda e: _rotate(e, decomp="bad"), DECOMP, BAD_DECOMP),
     "rotate-covariates-after-uploads": (lambda e: _rotate(e, ncov=RN), DIM, "Dimension mismatch."),
 }
+# chisq_df runs over [1, 10^6] at every -log10 p entry point (blmm_lod2log10p_dev and blmm_set_log10p_output refuse beyond): a df
+# of 2^32 + 1 must not reach the kernel's int as 1, nor 2^31 as a negative df
+for _df in (1000000 + 1, 1 << 31, (1 << 32) + 1):
+    REFUSALS[f"lod2log10p-df-{_df}"] = (lambda e, df=_df: e.lib.blmm_lod2log10p(e.h, e.hp(e.G), RP, 1, df, e.hp(e.hout[0])), INVALID,
+                                        "lod2log10p: bad arguments")
+    REFUSALS[f"last_log10p-df-{_df}"] = (lambda e, df=_df: e.lib.blmm_last_log10p(e.h, df, e.hp(e.hout[0])), INVALID,
+                                         "last_log10p: bad arguments")
 
 
 @pytest.mark.parametrize("case", list(REFUSALS))
