@@ -31,6 +31,7 @@ EXPORTS = [
     "blmm_bulkscan_reduced_async", "blmm_bulkscan_perms", "blmm_bulkscan_perms_dev",
     "blmm_last_dims", "blmm_last_lod_colmax", "blmm_last_lod_columns", "blmm_multi_last_colmax", "blmm_multi_last_lod_threshold",
     "blmm_kinship_loco", "blmm_kinship_loco_dev", "blmm_bulkscan_loco", "blmm_bulkscan_loco_dev",
+    "blmm_bulkscan_loco_reduced", "blmm_bulkscan_loco_reduced_dev",
 ]
 
 BLMM_NULL_EXACT, BLMM_NULL_GRID, BLMM_ALT_GRID = 0, 1, 2
@@ -205,6 +206,8 @@ def load():
     lib.blmm_kinship_loco_dev.argtypes = [vp, vp, i64, i64, vp, i64, i64, vp]
     lib.blmm_bulkscan_loco.argtypes = [vp, op, vp, i64, i64, vp, i64, vp, i64, i64, vp, i64, vp, vp, i64, vp, vp, sp]
     lib.blmm_bulkscan_loco_dev.argtypes = [vp, op, vp, i64, i64, vp, i64, vp, i64, i64, vp, i64, vp, vp, i64, vp, vp, i64, vp, sp]
+    lib.blmm_bulkscan_loco_reduced.argtypes = [vp, op, vp, i64, i64, vp, i64, vp, i64, i64, vp, i64, vp, vp, i64, rp, vp, vp, vp, sp]
+    lib.blmm_bulkscan_loco_reduced_dev.argtypes = [vp, op, vp, i64, i64, vp, i64, vp, i64, i64, vp, i64, vp, vp, i64, vp, rp, vp, vp, vp, sp]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if a declared symbol is not exported
     _lib = lib

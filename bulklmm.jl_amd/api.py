@@ -1323,3 +1323,116 @@ def bulkscan_loco_dev(ctx: Context, Y, G, chr_start, L_out, h2_out, *, method: s
                                              None if K_loco is None else K_loco.data_ptr(), L_out.data_ptr(), _ld(L_out, p),
                                              None if h2_out is None else h2_out.data_ptr(), C.byref(st) if status else None))
     return st
+
+
+def bulkscan_loco_reduced(Y, G, chrom, Covar=None, *, method: str = "null-grid", h2_grid=None, threshold: Optional[float] = None,
+                          cap: int = 1 << 20, kinship_digits: Optional[int] = None, addIntercept: bool = True, weights=None,
+                          prior_variance: float = 1.0, prior_sample_size: float = 0.0, reml: bool = False, optim_interval: int = 1,
+                          decomp_scheme: str = "eigen", ctx: Optional[Context] = None, return_status: bool = False) -> dict:
+    """bulkscan_loco WITHOUT the LOD matrix (blmm_bulkscan_loco_reduced): the reductions of bulkscan_reduced over the LOCO L, plus
+    every chromosome's peak, computed on the device; no p x m matrix exists there or here.  Bit for bit what lod_colmax /
+    lod_threshold give on bulkscan_loco(...)["L"] with the same arguments.  Returns {"max_lod": m, "argmax": m (0-based global
+    marker), "chr_max_lod": (nchr, m), "chr_argmax": (nchr, m) (row c: the peak over chromosome c's rows, still a global marker;
+    -inf / -1 where every LOD is NaN), "h2_null_list": (nchr, m) (null-* methods), "chromosomes", "chr_start" [, "triplets": (i, j,
+    lod) sorted by (trait, marker)], "route": 1 fused | 3 fused with on-device re-scans | 2 per-chromosome resident block
+    [, "status"]}.  `cap` as bulkscan_reduced: more hits than that and the whole call runs again with the count it reported."""
+    if h2_grid is None:
+        h2_grid = [i / 10.0 for i in range(10)]
+    if method not in _METHODS:
+        raise BulkLMMError("Unknown method `%s`; choose null-exact, null-grid or alt-grid." % method, -5)
+    meth = _METHODS[method]
+    if int(cap) < 0:
+        raise BulkLMMError("bulkscan_loco_reduced: triplet buffers (cap < 0)", -1)
+    Y = _F(Y)
+    G = _F(G)
+    n, m = Y.shape
+    p = G.shape[1]
+    if G.shape[0] != n:
+        raise BulkLMMError("Dimension mismatch.", -2)
+    runs, cs = chromosome_runs(chrom, p)
+    nchr = cs.shape[0] - 1
+    _check_n(n)
+    cov, ncov = None, 0
+    if Covar is not None:
+        cov = _F(Covar)
+        if cov.shape[0] != n:
+            raise BulkLMMError("Dimension mismatch.", -2)
+        ncov = cov.shape[1]
+    else:
+        addIntercept = True
+    w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).ravel())
+    if w is not None and w.shape[0] != n:
+        raise BulkLMMError("Dimension mismatch.", -2)
+    grid, ngrid = None, 0
+    if meth != L.BLMM_NULL_EXACT:
+        grid = np.ascontiguousarray(np.asarray(h2_grid, dtype=np.float64).ravel())
+        ngrid = grid.shape[0]
+    o = _opts(meth, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
+    ctx = ctx or default_context()  # after the argument checks: those must not need a GPU
+    mx = np.empty(m); arg = np.empty(m, dtype=np.int64)
+    cmx = np.empty((nchr, m)); carg = np.empty((nchr, m), dtype=np.int64)     # row c: chromosome c (C order = the library's blocks)
+    h2 = np.empty((nchr, m))
+    st = L.blmm_status()
+    want = threshold is not None
+    cap = int(cap)
+    while True:
+        cnt = C.c_int64(0)
+        ii = np.empty(max(cap, 1), dtype=np.int32); jj = np.empty(max(cap, 1), dtype=np.int32); ll = np.empty(max(cap, 1))
+        r = L.blmm_reduced(mx.ctypes.data, arg.ctypes.data, 1 if want else 0, float(threshold) if want else 0.0, cap if want else 0,
+                           ii.ctypes.data, jj.ctypes.data, ll.ctypes.data, C.addressof(cnt))
+        ctx.check(ctx.lib.blmm_bulkscan_loco_reduced(ctx.h, C.byref(o), _p(Y), n, m, _p(G), p, _p(cs), nchr,
+                                                     -1 if kinship_digits is None else int(kinship_digits), _p(cov), ncov, _p(w),
+                                                     _p(grid), ngrid, C.byref(r), _p(cmx), _p(carg), _p(h2), C.byref(st)))
+        if not want or cnt.value <= cap:
+            break
+        cap = int(cnt.value)
+    _raise_status(st)
+    out = {"max_lod": mx, "argmax": arg, "chr_max_lod": cmx, "chr_argmax": carg, "chromosomes": runs, "chr_start": cs,
+           "route": int(ctx.lib.blmm_last_reduced_route(ctx.h))}
+    if meth != L.BLMM_ALT_GRID:
+        out["h2_null_list"] = h2
+    if want:
+        k = int(cnt.value)
+        order = np.lexsort((ii[:k], jj[:k]))
+        out["triplets"] = (ii[:k][order], jj[:k][order], ll[:k][order])
+    if return_status:
+        out["status"] = st
+    return out
+
+
+def bulkscan_loco_reduced_dev(ctx: Context, Y, G, chr_start, max_out, argmax_out, chr_max_out, chr_argmax_out, h2_out, *,
+                              method: str = "null-exact", h2_grid=None, K_loco=None, kinship_digits: Optional[int] = None, Covar=None,
+                              weights=None, addIntercept: bool = True, prior_variance: float = 1.0, prior_sample_size: float = 0.0,
+                              reml: bool = False, optim_interval: int = 1, decomp_scheme: str = "eigen",
+                              threshold: Optional[float] = None, trip_i=None, trip_j=None, trip_lod=None, trip_count=None,
+                              status: bool = False):
+    """blmm_bulkscan_loco_reduced_dev on torch CUDA tensors (layouts as bulkscan_loco_dev): max_out (m, float64), argmax_out (m,
+    int64), chr_max_out (nchr, m, float64), chr_argmax_out (nchr, m, int64), h2_out (nchr, m; None for alt-grid) -- each may be
+    None; threshold given: trip_i / trip_j (int32, cap), trip_lod (float64, cap), trip_count (int64, 1).  Enqueues on the context's
+    stream; status=True synchronises."""
+    m, n = Y.shape
+    p = G.shape[0]
+    cs = _check_chr_start(chr_start, p)
+    nchr = cs.shape[0] - 1
+    _check_n(n)
+    if method not in _METHODS:
+        raise BulkLMMError("Unknown method `%s`; choose null-exact, null-grid or alt-grid." % method, -5)
+    grid, ngrid = None, 0
+    if method != "null-exact":
+        grid = np.ascontiguousarray(np.asarray(h2_grid if h2_grid is not None else [i / 10.0 for i in range(10)], dtype=np.float64))
+        ngrid = grid.shape[0]
+    ncov = 0 if Covar is None else Covar.shape[0]
+    if Covar is None:
+        addIntercept = True
+    o = _opts(_METHODS[method], reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
+    st = L.blmm_status() if status else None
+    want = threshold is not None
+    dp = lambda t: None if t is None else t.data_ptr()
+    r = L.blmm_reduced(dp(max_out), dp(argmax_out), 1 if want else 0, float(threshold) if want else 0.0,
+                       int(trip_i.numel()) if want else 0, dp(trip_i) if want else None, dp(trip_j) if want else None,
+                       dp(trip_lod) if want else None, dp(trip_count) if want else None)
+    ctx.check(ctx.lib.blmm_bulkscan_loco_reduced_dev(ctx.h, C.byref(o), Y.data_ptr(), n, m, G.data_ptr(), p, _p(cs), nchr,
+                                                     -1 if kinship_digits is None else int(kinship_digits), dp(Covar), ncov, dp(weights),
+                                                     _p(grid), ngrid, dp(K_loco), C.byref(r), dp(chr_max_out), dp(chr_argmax_out),
+                                                     dp(h2_out), C.byref(st) if status else None))
+    return st

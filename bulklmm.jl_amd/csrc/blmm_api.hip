@@ -1359,17 +1359,21 @@ static int reduced_check(blmm_ctx* ctx, const blmm_opts* opts, const double* dY,
   return BLMM_OK;
 }
 
-// The fused route's reduction state over ctx->redbuf: per-(trait, 64-marker slot) partials, the triplet outputs of `out`
-static int reduced_args(blmm_ctx* ctx, const blmm_reduced* out, int64_t p, int64_t m, RedArgs* r, int* nslot) {
-  *nslot = 2 * (int)((p + 127) / 128);
+// The fused route's reduction state over ctx->redbuf: nslot per-(trait, 64-marker slot) partials, the triplet outputs of `out`
+static int red_state(blmm_ctx* ctx, const blmm_reduced* out, int64_t nslot, int64_t m, RedArgs* r) {
   const int64_t ldm = round_up(m, 64);
-  int rc = ensure(ctx, ctx->redbuf, (sizeof(double) + sizeof(int)) * (size_t)*nslot * (size_t)ldm);
+  int rc = ensure(ctx, ctx->redbuf, (sizeof(double) + sizeof(int)) * (size_t)nslot * (size_t)ldm);
   if (rc) return rc;
-  r->pmax = ptr<double>(ctx->redbuf); r->parg = reinterpret_cast<int*>(r->pmax + (size_t)*nslot * ldm); r->ldm = ldm;
+  r->pmax = ptr<double>(ctx->redbuf); r->parg = reinterpret_cast<int*>(r->pmax + (size_t)nslot * ldm); r->ldm = ldm;
   r->want_trip = out->want_triplets ? 1 : 0; r->thr = out->thr; r->cap = out->cap;
   r->ti = out->ti; r->tj = out->tj; r->tl = out->tlod; r->cnt = reinterpret_cast<unsigned long long*>(out->count);
   if (out->count) BLMM_HIP(hipMemsetAsync(out->count, 0, sizeof(int64_t), ctx->stream));
   return BLMM_OK;
+}
+// ... for one scan of p markers: 2 ceil(p / 128) slots
+static int reduced_args(blmm_ctx* ctx, const blmm_reduced* out, int64_t p, int64_t m, RedArgs* r, int* nslot) {
+  *nslot = 2 * (int)((p + 127) / 128);
+  return red_state(ctx, out, *nslot, m, r);
 }
 
 // The route through a resident L: the whole bulkscan into the context's outL (alt-grid: h2_panel, p x m, into the workspace -- it is
@@ -1648,20 +1652,29 @@ int blmm_kinship_loco(blmm_ctx* ctx, const double* G, int64_t n, int64_t p, cons
   return hc.finish(false);
 }
 
+// blmm_bulkscan_loco_reduced: what each chromosome's scan produces instead of its rows of L.  fused: the scan epilogues reduce into
+// the chromosome's own range of r's slot partials (slot0[c], by chromosome index) and append their triplets with the chromosome's
+// first marker as row offset (RedArgs::row0); the guards flag traits into r.flags, zeroed for each chromosome, and k_scan_fix /
+// k_scan_qr re-scan those into the same partials.  Otherwise (route 2) the chromosome's rows go to a resident block of ld rows
+// (outL, sized by the largest chromosome), which k_colmax and k_threshold reduce into cmx / carg and the triplets before the next
+// chromosome overwrites it.  Either way launch_red_final_loco merges the chromosomes after the last one.
+struct LocoRed {
+  const blmm_reduced* out = nullptr;   // device pointers
+  bool fused = false;
+  RedArgs r;
+  std::vector<int64_t> slot0;
+  double* cmx = nullptr; int64_t* carg = nullptr;   // nchr x m (fused: may be null)
+  int64_t ld = 0;
+};
+
 // The pipeline: the kinships (unless given), then per chromosome the whole bulkscan front and scan on its column block, into its rows
-// of L.  The chromosomes run largest first, so that no p-sized workspace grows -- and no buffer is freed under queued work -- after
-// the first of them; each one's status block is copied aside (locoStat) and summed once at the end.
-static int bulkscan_loco_dev_impl(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG,
-                                  int64_t p, const int64_t* chr, int64_t nchr, int64_t kdigits, const double* dCovar, int64_t ncov,
-                                  const double* dweights, const double* h2_grid_host, int64_t ngrid, const double* dK_loco,
-                                  double* dL, int64_t ldL, double* dh2, blmm_status* status, const PvReq& pvreq) {
-  int rc = check_opts(ctx, opts);
-  if (rc) return rc;
-  if (!dY || !dG || !dL || (!dh2 && opts->method != BLMM_ALT_GRID)) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_loco: NULL buffer");
-  if ((rc = check_method(ctx, opts)) || (rc = loco_check(ctx, n, p, chr, nchr, "bulkscan_loco"))) return rc;
-  if (m < 0 || ldL < p || kdigits > 300) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_loco: bad arguments");
-  if (n > 2048) return fail(ctx, BLMM_ERR_UNSUPPORTED, "more than 2048 individuals: the device eigensolver (tridiagonalisation + divide and conquer) stops at n = 2048");
-  if ((rc = enter_device(ctx))) return rc;
+// of L (or, red given, into its reduction).  The chromosomes run largest first, so that no p-sized workspace grows -- and no buffer is
+// freed under queued work -- after the first of them; each one's status block is copied aside (locoStat) and summed once at the end.
+static int loco_pipeline(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG, int64_t p,
+                         const int64_t* chr, int64_t nchr, int64_t kdigits, const double* dCovar, int64_t ncov, const double* dweights,
+                         const double* h2_grid_host, int64_t ngrid, const double* dK_loco, double* dL, int64_t ldL, double* dh2,
+                         blmm_status* status, const PvReq& pvreq, LocoRed* red) {
+  int rc;
   double* dgrid = nullptr;
   if (opts->method != BLMM_NULL_EXACT && (rc = grid_to_device(ctx, h2_grid_host, ngrid, &dgrid))) return rc;
   // one event set for the start of the call (t_total_ms spans the kinships computed inside it, which count in no phase), one for the
@@ -1722,8 +1735,25 @@ static int bulkscan_loco_dev_impl(blmm_ctx* ctx, const blmm_opts* opts, const do
       if ((rc = ensure(ctx, ctx->outH2, sizeof(double) * (size_t)pc * (m > 0 ? m : 1)))) return rc;
       h2c = ptr<double>(ctx->outH2);
     }
-    if ((rc = scan_pipeline(ctx, opts, P, tm, lowrank, lowrank && m > 0, dgrid, h2_grid_host, ngrid, dL + s0, ldL, h2c, nullptr, PvReq(),
-                            (alt && dh2) ? p : pc))) return rc;
+    double* Lc = dL ? dL + s0 : nullptr;
+    int64_t ldc = ldL;
+    if (red && red->fused) {
+      RedArgs r = red->r;
+      r.pmax += (size_t)red->slot0[(size_t)c] * r.ldm; r.parg += (size_t)red->slot0[(size_t)c] * r.ldm; r.row0 = s0;
+      BLMM_HIP(hipMemsetAsync(r.flags, 0, sizeof(int) * (size_t)m, ctx->stream));
+      ctx->red_cur = r;
+    } else if (red) {
+      Lc = ptr<double>(ctx->outL); ldc = red->ld;
+    }
+    rc = scan_pipeline(ctx, opts, P, tm, lowrank, lowrank && m > 0, dgrid, h2_grid_host, ngrid, Lc, ldc, h2c, nullptr, PvReq(),
+                       (alt && dh2) ? p : pc);
+    ctx->red_cur = RedArgs();
+    if (rc) return rc;
+    if (red && !red->fused) {
+      const blmm_reduced* o = red->out;
+      if ((rc = launch_colmax_rows(ctx, Lc, pc, m, ldc, red->cmx + (size_t)c * m, red->carg + (size_t)c * m, s0))) return rc;
+      if (o->want_triplets && (rc = launch_threshold_rows(ctx, Lc, pc, m, ldc, o->thr, o->cap, o->ti, o->tj, o->tlod, o->count, s0))) return rc;
+    }
     audit = audit || ctx->audit_ran;
     // the next chromosome reuses every buffer this one's side-stream work reads: the main stream waits for both side streams
     BLMM_HIP(hipEventRecord(ctx->ev_fork, ctx->side));
@@ -1738,6 +1768,13 @@ static int bulkscan_loco_dev_impl(blmm_ctx* ctx, const blmm_opts* opts, const do
   if (batched && !order.empty()) {
     if ((rc = ensure(ctx, ctx->stat, sizeof(int64_t) * NSTAT))) return rc;
     BLMM_HIP(hipMemcpyAsync(ctx->stat.p, dst_all + (size_t)order.back() * NSTAT, sizeof(int64_t) * NSTAT, hipMemcpyDeviceToDevice, ctx->stream));
+  }
+  if (red) {
+    const int64_t* dchr = nullptr;
+    const bool sl = red->fused;
+    if ((rc = loco_offsets(ctx, chr, nchr, &dchr)) ||
+        (rc = launch_red_final_loco(ctx, sl ? red->r.pmax : nullptr, sl ? red->r.parg : nullptr, red->r.ldm, dchr, nchr, m, red->cmx, red->carg,
+                                    red->out->colmax, red->out->argmax))) return rc;
   }
   PvCall pvc(ctx, pvreq);                    // (never fused: a column pass over the finished L)
   if ((rc = pvc.resolve(p, m)) || (rc = pvc.finish(p, m, dL, ldL))) return rc;
@@ -1767,6 +1804,21 @@ static int bulkscan_loco_dev_impl(blmm_ctx* ctx, const blmm_opts* opts, const do
   }
   *status = sum;
   return BLMM_OK;
+}
+
+static int bulkscan_loco_dev_impl(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG,
+                                  int64_t p, const int64_t* chr, int64_t nchr, int64_t kdigits, const double* dCovar, int64_t ncov,
+                                  const double* dweights, const double* h2_grid_host, int64_t ngrid, const double* dK_loco,
+                                  double* dL, int64_t ldL, double* dh2, blmm_status* status, const PvReq& pvreq) {
+  int rc = check_opts(ctx, opts);
+  if (rc) return rc;
+  if (!dY || !dG || !dL || (!dh2 && opts->method != BLMM_ALT_GRID)) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_loco: NULL buffer");
+  if ((rc = check_method(ctx, opts)) || (rc = loco_check(ctx, n, p, chr, nchr, "bulkscan_loco"))) return rc;
+  if (m < 0 || ldL < p || kdigits > 300) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_loco: bad arguments");
+  if (n > 2048) return fail(ctx, BLMM_ERR_UNSUPPORTED, "more than 2048 individuals: the device eigensolver (tridiagonalisation + divide and conquer) stops at n = 2048");
+  if ((rc = enter_device(ctx))) return rc;
+  return loco_pipeline(ctx, opts, dY, n, m, dG, p, chr, nchr, kdigits, dCovar, ncov, dweights, h2_grid_host, ngrid, dK_loco, dL, ldL, dh2,
+                       status, pvreq, nullptr);
 }
 
 int blmm_bulkscan_loco_dev(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG, int64_t p,
@@ -1807,6 +1859,124 @@ int blmm_bulkscan_loco(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, in
   if (h2_out && h2_elems > 0 && (rc = copy_to_host(ctx, h2_out, ctx->outH2.p, sizeof(double) * h2_elems))) return rc;
   if ((rc = hc.finish())) return rc;
   return check_sticky(ctx);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Leave-one-chromosome-out without the LOD matrix (include/bulklmm_hip.h: blmm_bulkscan_loco_reduced).  `out`, dcmx, dcarg and dh2 are
+// DEVICE pointers here.  Fused (null-grid; null-exact in the low-rank weights form): every chromosome reduces in its scan epilogues
+// into its own slot range, flagged traits are re-scanned into it on the device (route 3), and one k_red_final_loco finishes all of
+// them.  Otherwise every chromosome's rows go through one resident block of the largest chromosome's size (route 2).  Either way no
+// p x m matrix exists.  Only a status makes it wait for the device.
+static int loco_reduced_impl(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG, int64_t p,
+                             const int64_t* chr, int64_t nchr, int64_t kdigits, const double* dCovar, int64_t ncov, const double* dweights,
+                             const double* h2_grid_host, int64_t ngrid, const double* dK_loco, const blmm_reduced* out, double* dcmx,
+                             int64_t* dcarg, double* dh2, blmm_status* status) {
+  int rc = check_opts(ctx, opts);
+  if (rc) return rc;
+  const bool alt = opts->method == BLMM_ALT_GRID;
+  if (!out || !dY || !dG || (!dh2 && !alt)) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_loco_reduced: NULL buffer");
+  if (out->cap < 0 || (out->cap > 0 && (!out->ti || !out->tj || !out->tlod)) || (out->want_triplets && !out->count))
+    return fail(ctx, BLMM_ERR_INVALID, "bulkscan_loco_reduced: triplet buffers");
+  if ((rc = check_method(ctx, opts)) || (rc = loco_check(ctx, n, p, chr, nchr, "bulkscan_loco_reduced"))) return rc;
+  if (m < 0 || kdigits > 300) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_loco_reduced: bad arguments");
+  if (n > 2048) return fail(ctx, BLMM_ERR_UNSUPPORTED, "more than 2048 individuals: the device eigensolver (tridiagonalisation + divide and conquer) stops at n = 2048");
+  if (p > 0x7fffffffLL || m > 0x7fffffffLL) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
+  if ((rc = enter_device(ctx))) return rc;
+  LocoRed red;
+  red.out = out;
+  red.fused = m > 0 && (opts->method == BLMM_NULL_GRID || wants_lowrank(ctx, opts, n, dCovar, ncov));
+  if (red.fused) {
+    red.slot0.resize((size_t)nchr + 1, 0);
+    for (int64_t c = 0; c < nchr; ++c) red.slot0[(size_t)c + 1] = red.slot0[(size_t)c] + 2 * ((chr[c + 1] - chr[c] + 127) / 128);
+    if ((rc = red_state(ctx, out, red.slot0.back(), m, &red.r)) || (rc = ensure(ctx, ctx->redflag, sizeof(int) * (size_t)m))) return rc;
+    red.r.flags = ptr<int>(ctx->redflag);
+    red.cmx = dcmx; red.carg = dcarg;
+  } else {
+    for (int64_t c = 0; c < nchr; ++c) red.ld = std::max(red.ld, chr[c + 1] - chr[c]);
+    const size_t tab = (size_t)nchr * (size_t)(m > 0 ? m : 1);
+    if ((rc = ensure(ctx, ctx->outL, sizeof(double) * (size_t)red.ld * (size_t)(m > 0 ? m : 1)))) return rc;
+    if (!dcmx && (rc = ensure(ctx, ctx->locoCmx, sizeof(double) * tab))) return rc;
+    if (!dcarg && (rc = ensure(ctx, ctx->locoCarg, sizeof(int64_t) * tab))) return rc;
+    red.cmx = dcmx ? dcmx : ptr<double>(ctx->locoCmx);
+    red.carg = dcarg ? dcarg : ptr<int64_t>(ctx->locoCarg);
+    if (out->count) BLMM_HIP(hipMemsetAsync(out->count, 0, sizeof(int64_t), ctx->stream));
+  }
+  rc = loco_pipeline(ctx, opts, dY, n, m, dG, p, chr, nchr, kdigits, dCovar, ncov, dweights, h2_grid_host, ngrid, dK_loco, nullptr, 0,
+                     alt ? nullptr : dh2, status, PvReq(), &red);
+  ctx->red_cur = RedArgs();
+  if (rc) return rc;
+  clear_last(ctx);                          // no p x m matrix of this call: an earlier one is not served as its result
+  // 1 / 3 need the device's counts: known when a status was read, else 0 (fused, not yet known)
+  ctx->last_reduced_route = !red.fused ? 2 : !status ? 0 : (status->lowrank_fallback > 0 || status->n_illcond_rescan > 0) ? 3 : 1;
+  return BLMM_OK;
+}
+
+int blmm_bulkscan_loco_reduced_dev(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG, int64_t p,
+                                   const int64_t* chr_start, int64_t nchr, int64_t kinship_digits, const double* dCovar, int64_t ncov,
+                                   const double* dweights, const double* h2_grid, int64_t ngrid, const double* dK_loco, const blmm_reduced* out,
+                                   double* dchr_max_out, int64_t* dchr_argmax_out, double* dh2_out, blmm_status* status) {
+  if (!ctx) return BLMM_ERR_INVALID;
+  if (pv_take(ctx).armed) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_loco_reduced: a blmm_set_log10p_output request is pending (the reduced call writes no matrix)");
+  if (ncov == 0) dCovar = nullptr;
+  return loco_reduced_impl(ctx, opts, dY, n, m, dG, p, chr_start, nchr, kinship_digits, dCovar, dCovar ? ncov : 0, dweights, h2_grid, ngrid,
+                           dK_loco, out, dchr_max_out, dchr_argmax_out, dh2_out, status);
+}
+
+int blmm_bulkscan_loco_reduced(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, int64_t n, int64_t m, const double* G, int64_t p,
+                               const int64_t* chr_start, int64_t nchr, int64_t kinship_digits, const double* Covar, int64_t ncov,
+                               const double* weights, const double* h2_grid, int64_t ngrid, const blmm_reduced* out, double* chr_max_out,
+                               int64_t* chr_argmax_out, double* h2_out, blmm_status* status) {
+  if (!ctx) return BLMM_ERR_INVALID;
+  if (pv_take(ctx).armed) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_loco_reduced: a blmm_set_log10p_output request is pending (the reduced call writes no matrix)");
+  if (!opts) return fail(ctx, BLMM_ERR_INVALID, "opts is NULL");
+  const bool alt = opts->method == BLMM_ALT_GRID;
+  if (!out || !Y || !G || (!h2_out && !alt)) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_loco_reduced: NULL buffer");
+  if (out->cap < 0 || (out->cap > 0 && (!out->ti || !out->tj || !out->tlod)) || (out->want_triplets && !out->count))
+    return fail(ctx, BLMM_ERR_INVALID, "bulkscan_loco_reduced: triplet buffers");
+  if (m < 0 || ncov < 0) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
+  int rc = loco_check(ctx, n, p, chr_start, nchr, "bulkscan_loco_reduced");
+  if (rc) return rc;
+  if (n > 2048) return fail(ctx, BLMM_ERR_UNSUPPORTED, "more than 2048 individuals: the device eigensolver (tridiagonalisation + divide and conquer) stops at n = 2048");
+  // (loco_reduced_impl checks these again: here they come before the uploads)
+  if ((rc = check_opts(ctx, opts)) || (rc = check_method(ctx, opts))) return rc;
+  if (kinship_digits > 300) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_loco_reduced: bad arguments");
+  if (p > 0x7fffffffLL || m > 0x7fffffffLL) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
+  if (opts->method != BLMM_NULL_EXACT && (rc = check_grid(ctx, h2_grid, ngrid))) return rc;
+  HostCall hc(ctx);
+  const size_t cap = out->cap > 0 ? out->cap : 1, mm = m > 0 ? m : 1, tab = (size_t)nchr * mm;
+  // device side: maxima / arg-maxima (tmpA / tmpB), the per-chromosome tables (locoCmx / locoCarg), triplets + count (redtrip),
+  // h2 (outH2, nchr x m)
+  if ((rc = hc.begin()) || (rc = ensure(ctx, ctx->tmpA, sizeof(double) * mm)) || (rc = ensure(ctx, ctx->tmpB, sizeof(int64_t) * mm)) ||
+      (rc = ensure(ctx, ctx->locoCmx, sizeof(double) * tab)) || (rc = ensure(ctx, ctx->locoCarg, sizeof(int64_t) * tab)) ||
+      (rc = ensure(ctx, ctx->redtrip, (sizeof(double) + 2 * sizeof(int32_t)) * cap + 64)) || (rc = ensure(ctx, ctx->outH2, sizeof(double) * tab)))
+    return rc;
+  blmm_reduced d = *out;
+  d.colmax = (out->colmax || out->argmax) ? ptr<double>(ctx->tmpA) : nullptr;
+  d.argmax = out->argmax ? ptr<int64_t>(ctx->tmpB) : nullptr;
+  d.count = ptr<int64_t>(ctx->redtrip);
+  d.tlod = reinterpret_cast<double*>(d.count + 8);
+  d.ti = reinterpret_cast<int32_t*>(d.tlod + cap);
+  d.tj = d.ti + cap;
+  HostCall::In in;
+  // (the host form always reads the status: it waits for the device anyway, and that is what tells route 1 from route 3)
+  blmm_status st;
+  if ((rc = hc.inputs(Y, n, m, G, p, nullptr, Covar, ncov, weights, false, &in)) ||
+      (rc = loco_reduced_impl(ctx, opts, in.Y, n, m, in.G, p, chr_start, nchr, kinship_digits, in.Cov, in.ncov, in.W, h2_grid, ngrid, nullptr, &d,
+                              ptr<double>(ctx->locoCmx), ptr<int64_t>(ctx->locoCarg), alt ? nullptr : ptr<double>(ctx->outH2), &st))) return rc;
+  if (status) *status = st;
+  if (m > 0 && ((rc = hc.down(out->colmax, d.colmax, sizeof(double) * m)) || (rc = hc.down(out->argmax, d.argmax, sizeof(int64_t) * m)))) return rc;
+  if (m > 0 && ((chr_max_out && (rc = copy_to_host(ctx, chr_max_out, ctx->locoCmx.p, sizeof(double) * (size_t)nchr * m))) ||
+                (chr_argmax_out && (rc = copy_to_host(ctx, chr_argmax_out, ctx->locoCarg.p, sizeof(int64_t) * (size_t)nchr * m))) ||
+                (!alt && h2_out && (rc = copy_to_host(ctx, h2_out, ctx->outH2.p, sizeof(double) * (size_t)nchr * m))))) return rc;
+  if (out->want_triplets) {
+    // the count first: only what it says is copied back
+    if ((rc = hc.down(out->count, d.count, sizeof(int64_t)))) return rc;
+    BLMM_HIP(hipStreamSynchronize(ctx->stream));
+    const size_t got = *out->count < out->cap ? *out->count : out->cap;
+    if ((rc = hc.down(out->tlod, d.tlod, sizeof(double) * got)) || (rc = hc.down(out->ti, d.ti, sizeof(int32_t) * got)) ||
+        (rc = hc.down(out->tj, d.tj, sizeof(int32_t) * got))) return rc;
+  }
+  return (rc = hc.finish()) ? rc : check_sticky(ctx);
 }
 
 // host-pointer form of the reduce-in-epilogue scan: `out` holds HOST pointers; the small results come back, nothing p x m moves

@@ -91,6 +91,9 @@ struct RedArgs {
   // Non-null: the re-scan kernels (k_scan_fix, k_scan_qr) patch the flagged traits' partials and append their triplets on the
   // device, and the scan epilogues append none for a flagged trait (the guards have run before them when triplets are wanted).
   int* flags = nullptr;
+  // the rows this scan's markers are in the caller's result (blmm_bulkscan_loco_reduced: the chromosome's first marker), added to
+  // the marker index of every triplet appended; 0 elsewhere.  The slot partials keep the scan's own marker index.
+  int64_t row0 = 0;
 };
 }  // namespace blmm
 
@@ -105,7 +108,8 @@ struct blmm_ctx {
   // grow-only workspace
   blmm::DevBuf Ks, V, lam, U, Zs, Z0, Rp, Yt, Xt, panels, iyy, h2, h2idx, sig2, ell, isx, stat, gridd, misc, EllTab,
       inY, inG, inK, inCov, inW, outL, outH2, tmpA, tmpB, tmpC, perm, r0, altbuf, logtab, lraw, wbQ, wbW, wbRk, lrT, lrC, lrL, lrFlag, lrPart, lrPerm, lrDen0, eigW, xf32, pf32, brSt, brList, illList, qrSlab, lodtab, dynFac, pvtab, outP, redbuf, redtrip, altC, rf32, btG, redflag, bperm,
-      locoK, locoPart, locoChr, locoStat, locoKs, locoV, locoLraw;   // blmm_kinship_loco / blmm_bulkscan_loco (kernels_loco.hip)
+      locoK, locoPart, locoChr, locoStat, locoKs, locoV, locoLraw,   // blmm_kinship_loco / blmm_bulkscan_loco (kernels_loco.hip)
+      locoCmx, locoCarg;   // blmm_bulkscan_loco_reduced: the per-chromosome maxima / arg-maxima when the caller's tables are not on the device
   // event sets: one per timed call since the last blmm_read_timings (grown on demand, reused afterwards)
   struct EvSet { hipEvent_t e[8]; int n; };
   std::vector<EvSet> evsets;
@@ -306,6 +310,8 @@ int loco_kinship_splits(int64_t n, int64_t nchr);
 int launch_kinship_loco(blmm_ctx* ctx, const double* dG, int64_t n, const int64_t* dchr, int64_t nchr, int64_t digits, double* dK,
                         double* partial, int nsplit);
 int launch_colmax(blmm_ctx* ctx, const double* L, int64_t p, int64_t m, int64_t ldL, double* mx, int64_t* arg);
+// ... of rows row0 .. row0 + p - 1 of a larger matrix: row0 is added to every arg-maximum found (-1 stays -1)
+int launch_colmax_rows(blmm_ctx* ctx, const double* L, int64_t p, int64_t m, int64_t ldL, double* mx, int64_t* arg, int64_t row0);
 // kernels_post.hip
 int launch_lod2log10p(blmm_ctx* ctx, const double* dL, int64_t p, int64_t m, int64_t ldL, int df, double* dP, int64_t ldP);
 // permutation panel: column b = sqrt(w) .* P_w( pi_b(r0) ) / ||r0||  etc.  (see kernels_prep.hip)
@@ -342,7 +348,16 @@ struct ScanArgs {
 // kernels_post.hip: threshold triplets of a resident L; the second pass of the reduce-in-epilogue scan (RedArgs partials -> per trait)
 int launch_threshold(blmm_ctx* ctx, const double* dL, int64_t p, int64_t m, int64_t ldL, double thr, int64_t cap,
                      int32_t* di, int32_t* dj, double* dlod, int64_t* dcount);
+// ... of rows row0 .. row0 + p - 1 of a larger matrix: row0 is added to every triplet's marker index, and *dcount is not zeroed
+// first (the triplets of several row blocks accumulate behind one counter)
+int launch_threshold_rows(blmm_ctx* ctx, const double* dL, int64_t p, int64_t m, int64_t ldL, double thr, int64_t cap,
+                          int32_t* di, int32_t* dj, double* dlod, int64_t* dcount, int64_t row0);
 int launch_red_final(blmm_ctx* ctx, const RedArgs& r, int nslot, int64_t m, double* mx, int64_t* arg);
+// blmm_bulkscan_loco_reduced: per trait, every chromosome's (max, global argmax) -> cmx / carg (nchr x m, chromosome c at + c m) and
+// their merge in ascending chromosome order -> mx / arg.  pmax != nullptr: from the slot partials (chromosome c's at slot
+// sum_{c' < c} 2 ceil(pc' / 128), in the chromosomes' own marker index); nullptr: cmx / carg hold the chromosomes' results already
+int launch_red_final_loco(blmm_ctx* ctx, const double* pmax, const int* parg, int64_t ldm, const int64_t* dchr, int64_t nchr, int64_t m,
+                          double* cmx, int64_t* carg, double* mx, int64_t* arg);
 // blmm_bulkscan_reduced_async: the info block (BLMM_RINFO_*) from the status counters, in stream order; route 0: 3 when a guard
 // flagged a trait, else 1.  Also raises the context's sticky word on a device-side failure (as k_sticky).
 int launch_red_info(blmm_ctx* ctx, const int64_t* stat, int route, const int64_t* count, int64_t* info);

@@ -339,7 +339,7 @@ __device__ __forceinline__ void red_wave64(const RedArgs& R, int64_t trait, int6
   base = __shfl(base, leader, 64);
   if (hit) {
     const unsigned long long slot = base + (unsigned long long)__builtin_popcountll(mask & ((1ull << lane) - 1ull));
-    if ((int64_t)slot < R.cap) { R.ti[slot] = (int32_t)(i0 + lane); R.tj[slot] = (int32_t)trait; R.tl[slot] = lod; }
+    if ((int64_t)slot < R.cap) { R.ti[slot] = (int32_t)(R.row0 + i0 + lane); R.tj[slot] = (int32_t)trait; R.tl[slot] = lod; }
   }
 }
 

@@ -119,7 +119,7 @@ int launch_lod2log10p(blmm_ctx* ctx, const double* dL, int64_t p, int64_t m, int
 // can size a retry from *count.  The order of the triplets is unspecified (the host wrappers sort by (trait, marker)).
 __global__ void __launch_bounds__(256) k_threshold(const double* __restrict__ L, int64_t p, int64_t m, int64_t ldL, double thr,
                                                    int64_t cap, int32_t* __restrict__ oi, int32_t* __restrict__ oj,
-                                                   double* __restrict__ ol, unsigned long long* __restrict__ count) {
+                                                   double* __restrict__ ol, unsigned long long* __restrict__ count, int64_t row0) {
   const int lane = threadIdx.x & 63;
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   for (int64_t j = blockIdx.y; j < m; j += gridDim.y) {
@@ -132,20 +132,30 @@ __global__ void __launch_bounds__(256) k_threshold(const double* __restrict__ L,
     base = __shfl(base, (int)__builtin_ctzll(mask), 64);
     if (hit) {
       const unsigned long long slot = base + (unsigned long long)__builtin_popcountll(mask & ((1ull << lane) - 1ull));
-      if ((int64_t)slot < cap) { oi[slot] = (int32_t)i; oj[slot] = (int32_t)j; ol[slot] = v; }
+      if ((int64_t)slot < cap) { oi[slot] = (int32_t)(i + row0); oj[slot] = (int32_t)j; ol[slot] = v; }
     }
   }
+}
+
+static int threshold_pass(blmm_ctx* ctx, const double* dL, int64_t p, int64_t m, int64_t ldL, double thr, int64_t cap,
+                          int32_t* di, int32_t* dj, double* dlod, int64_t* dcount, int64_t row0) {
+  if (p <= 0 || m <= 0) return BLMM_OK;
+  dim3 grid((unsigned)((p + 255) / 256), (unsigned)(m < 4096 ? m : 4096));
+  hipLaunchKernelGGL(k_threshold, grid, dim3(256), 0, ctx->stream, dL, p, m, ldL, thr, cap, di, dj, dlod,
+                     reinterpret_cast<unsigned long long*>(dcount), row0);
+  KCHECK();
+  return BLMM_OK;
 }
 
 int launch_threshold(blmm_ctx* ctx, const double* dL, int64_t p, int64_t m, int64_t ldL, double thr, int64_t cap,
                      int32_t* di, int32_t* dj, double* dlod, int64_t* dcount) {
   BLMM_HIP(hipMemsetAsync(dcount, 0, sizeof(int64_t), ctx->stream));
-  if (p <= 0 || m <= 0) return BLMM_OK;
-  dim3 grid((unsigned)((p + 255) / 256), (unsigned)(m < 4096 ? m : 4096));
-  hipLaunchKernelGGL(k_threshold, grid, dim3(256), 0, ctx->stream, dL, p, m, ldL, thr, cap, di, dj, dlod,
-                     reinterpret_cast<unsigned long long*>(dcount));
-  KCHECK();
-  return BLMM_OK;
+  return threshold_pass(ctx, dL, p, m, ldL, thr, cap, di, dj, dlod, dcount, 0);
+}
+
+int launch_threshold_rows(blmm_ctx* ctx, const double* dL, int64_t p, int64_t m, int64_t ldL, double thr, int64_t cap,
+                          int32_t* di, int32_t* dj, double* dlod, int64_t* dcount, int64_t row0) {
+  return threshold_pass(ctx, dL, p, m, ldL, thr, cap, di, dj, dlod, dcount, row0);
 }
 
 // Second pass of the reduce-in-epilogue scan (RedArgs, blmm_internal.h): the scan kernels left, per trait and 64-marker slot, the
@@ -163,6 +173,50 @@ __global__ void __launch_bounds__(256) k_red_final(const double* __restrict__ pm
   }
   if (mx) mx[j] = best;
   if (arg) arg[j] = bi;
+}
+
+// blmm_bulkscan_loco_reduced: one thread per trait.  Chromosome c's partials follow those of chromosomes 0 .. c - 1 (2 ceil(pc / 128)
+// slots each, by chromosome index: the chromosomes ran largest first, but their slot ranges are in genome order) and are walked
+// with k_red_final's rule; the chromosome's maximum and its GLOBAL marker (the scan's own index + chr[c]) go to cmx / carg.  Without
+// partials (pmax == nullptr) cmx / carg already hold them (k_colmax over each chromosome's resident block).  Then the chromosomes
+// merge in ascending order by the same rule: their offsets increase, so a tie goes to the lowest global marker, as k_colmax on the
+// whole column would give.
+__global__ void __launch_bounds__(256) k_red_final_loco(const double* __restrict__ pmax, const int* __restrict__ parg, int64_t ldm,
+                                                        const int64_t* __restrict__ chr, int nchr, int64_t m, double* __restrict__ cmx,
+                                                        int64_t* __restrict__ carg, double* __restrict__ mx, int64_t* __restrict__ arg) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= m) return;
+  double gb = -INFINITY; int64_t gi = -1;
+  int64_t s0 = 0;
+  for (int c = 0; c < nchr; ++c) {
+    const int64_t off = chr[c], ns = 2 * ((chr[c + 1] - off + 127) / 128);
+    double best = -INFINITY; int64_t bi = -1;
+    if (pmax) {
+      for (int64_t s = s0; s < s0 + ns; ++s) {
+        const double v = pmax[s * ldm + j];
+        const int64_t i = parg[s * ldm + j];
+        if (v > best || (v == best && i >= 0 && (bi < 0 || i < bi))) { best = v; bi = i; }
+      }
+      if (bi >= 0) bi += off;
+      if (cmx) cmx[(int64_t)c * m + j] = best;
+      if (carg) carg[(int64_t)c * m + j] = bi;
+    } else {
+      best = cmx[(int64_t)c * m + j]; bi = carg[(int64_t)c * m + j];
+    }
+    s0 += ns;
+    if (best > gb || (best == gb && bi >= 0 && (gi < 0 || bi < gi))) { gb = best; gi = bi; }
+  }
+  if (mx) mx[j] = gb;
+  if (arg) arg[j] = gi;
+}
+
+int launch_red_final_loco(blmm_ctx* ctx, const double* pmax, const int* parg, int64_t ldm, const int64_t* dchr, int64_t nchr, int64_t m,
+                          double* cmx, int64_t* carg, double* mx, int64_t* arg) {
+  if (m <= 0) return BLMM_OK;
+  hipLaunchKernelGGL(k_red_final_loco, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, pmax, parg, ldm, dchr, (int)nchr, m,
+                     cmx, carg, mx, arg);
+  KCHECK();
+  return BLMM_OK;
 }
 
 // The info block of blmm_bulkscan_reduced_async (include/bulklmm_hip.h: BLMM_RINFO_*), written in stream order behind the call's

@@ -2919,7 +2919,7 @@ int launch_perm_panel(blmm_ctx* ctx, const NullModel& nm, const double* Yt, int6
 // 16-byte loads, first maximum wins; NaNs are ignored (a column of NaNs gives -inf, marker -1).
 // ------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_colmax(const double* __restrict__ L, int64_t p, int64_t m, int64_t ldL,
-                                                double* __restrict__ mx, int64_t* __restrict__ arg) {
+                                                double* __restrict__ mx, int64_t* __restrict__ arg, int64_t row0) {
   const int lane = threadIdx.x & 63;
   const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (j >= m) return;
@@ -2936,14 +2936,18 @@ __global__ void __launch_bounds__(256) k_colmax(const double* __restrict__ L, in
     const int64_t oi = __shfl_xor(bi, o, 64);
     if (ob > best || (ob == best && oi >= 0 && (bi < 0 || oi < bi))) { best = ob; bi = oi; }
   }
-  if (lane == 0) { mx[j] = best; if (arg) arg[j] = bi; }
+  if (lane == 0) { mx[j] = best; if (arg) arg[j] = bi < 0 ? bi : bi + row0; }
+}
+
+int launch_colmax_rows(blmm_ctx* ctx, const double* L, int64_t p, int64_t m, int64_t ldL, double* mx, int64_t* arg, int64_t row0) {
+  if (m <= 0) return BLMM_OK;
+  hipLaunchKernelGGL(k_colmax, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, ctx->stream, L, p, m, ldL, mx, arg, row0);
+  KCHECK();
+  return BLMM_OK;
 }
 
 int launch_colmax(blmm_ctx* ctx, const double* L, int64_t p, int64_t m, int64_t ldL, double* mx, int64_t* arg) {
-  if (m <= 0) return BLMM_OK;
-  hipLaunchKernelGGL(k_colmax, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, ctx->stream, L, p, m, ldL, mx, arg);
-  KCHECK();
-  return BLMM_OK;
+  return launch_colmax_rows(ctx, L, p, m, ldL, mx, arg, 0);
 }
 
 }  // namespace blmm

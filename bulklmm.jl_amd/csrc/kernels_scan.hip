@@ -168,7 +168,7 @@ __device__ __forceinline__ void red_row(const RedArgs& R, int64_t trait, int64_t
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb)
         if (h[nb]) {
-          if ((int64_t)slot < R.cap) { R.ti[slot] = (int32_t)(i0 + NB * c + nb); R.tj[slot] = (int32_t)trait; R.tl[slot] = out[nb]; }
+          if ((int64_t)slot < R.cap) { R.ti[slot] = (int32_t)(R.row0 + i0 + NB * c + nb); R.tj[slot] = (int32_t)trait; R.tl[slot] = out[nb]; }
           ++slot;
         }
     }

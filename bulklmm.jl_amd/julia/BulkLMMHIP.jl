@@ -11,7 +11,7 @@
 # every `ccall`'s symbol, return type and argument tuple (arity and types) against the prototype in include/bulklmm_hip.h.
 module BulkLMMHIP
 
-export calcKinship_loco, bulkscan_loco, bulkscan_perms, bulkscan_reduced, bulkscan_reduced_async!, synchronize, DeviceLOD, lod_columns, set_tuning, calcKinship, bulkscan, bulkscan_null, bulkscan_null_grid, bulkscan_alt_grid, bulkscan_alt_exact, scan, bulkscan_multi, lod2log10p, get_thresholds,
+export calcKinship_loco, bulkscan_loco, bulkscan_loco_reduced, bulkscan_perms, bulkscan_reduced, bulkscan_reduced_async!, synchronize, DeviceLOD, lod_columns, set_tuning, calcKinship, bulkscan, bulkscan_null, bulkscan_null_grid, bulkscan_alt_grid, bulkscan_alt_exact, scan, bulkscan_multi, lod2log10p, get_thresholds,
        lod_threshold, lod_colmax, pinned_matrix, host_register, host_unregister
 
 const libblmm = get(ENV, "BULKLMM_HIP_LIB", joinpath(@__DIR__, "..", "csrc", "libbulklmm_hip.so"))
@@ -717,6 +717,60 @@ function bulkscan_loco(Y::Array{Float64, 2}, G::Array{Float64, 2}, chrom::Abstra
     Lr = keep_on_device ? DeviceLOD(p, m) : L
     return meth == ALT_GRID ? (L = Lr, h2_panel = h2, chromosomes = runs, chr_start = cs) :
                               (L = Lr, h2_null_list = permutedims(h2), chromosomes = runs, chr_start = cs)
+end
+
+# bulkscan_loco WITHOUT the LOD matrix: the genome-wide peak of every trait, its peak on every chromosome (cis / trans table; the
+# marker index is genome-wide, 1-based) and, `threshold` given, every (marker, trait, LOD) with LOD > threshold -- bit for bit the
+# reductions of bulkscan_loco's L, computed on the device
+function bulkscan_loco_reduced(Y::Array{Float64, 2}, G::Array{Float64, 2}, chrom::AbstractVector;
+                               Covar::Union{Nothing, Array{Float64, 2}} = nothing, method::String = "null-grid",
+                               h2_grid::Array{Float64, 1} = collect(0.0:0.1:0.9), threshold::Union{Nothing, Float64} = nothing,
+                               cap::Int64 = 1048576, kinship_digits::Integer = -1, addIntercept::Bool = true,
+                               weights::Union{Missing, Array{Float64, 1}} = missing, prior_variance::Float64 = 1.0,
+                               prior_sample_size::Float64 = 0.0, reml::Bool = false, optim_interval::Int64 = 1,
+                               decomp_scheme::String = "eigen")
+    (n, m) = size(Y); p = size(G, 2)
+    size(G, 1) != n && error("Dimension mismatch.")
+    runs, cs = chromosome_runs(chrom, p)
+    nchr = length(cs) - 1
+    check_n(n)
+    (Covar !== nothing && size(Covar, 1) != n) && error("Dimension mismatch.")
+    (weights !== missing && length(weights) != n) && error("Dimension mismatch.")
+    cap < 0 && error("bulkscan_loco_reduced: triplet buffers (cap < 0)")
+    meth = method == "null-exact" ? NULL_EXACT : method == "null-grid" ? NULL_GRID : method == "alt-grid" ? ALT_GRID :
+           error("Unknown method `$method`; choose null-exact, null-grid or alt-grid.")
+    ncov = Covar === nothing ? 0 : size(Covar, 2)
+    o = BlmmOpts(meth, reml, Covar === nothing ? true : addIntercept, decomp(decomp_scheme), optim_interval, 0,
+                 prior_variance, prior_sample_size)
+    mx = Vector{Float64}(undef, m); arg = Vector{Int64}(undef, m)
+    cmx = Array{Float64, 2}(undef, m, nchr); carg = Array{Int64, 2}(undef, m, nchr); h2 = Array{Float64, 2}(undef, m, nchr)   # column c: chromosome c
+    want = threshold !== nothing
+    st = BlmmStatus()
+    while true
+        c1 = max(cap, 1)
+        ii = Vector{Int32}(undef, c1); jj = Vector{Int32}(undef, c1); ll = Vector{Float64}(undef, c1); cnt = zeros(Int64, 1)
+        GC.@preserve Y G cs Covar weights h2_grid mx arg cmx carg h2 ii jj ll cnt begin
+            r = BlmmReduced(pointer(mx), pointer(arg), want ? 1 : 0, want ? threshold : 0.0, want ? cap : 0,
+                            pointer(ii), pointer(jj), pointer(ll), pointer(cnt))
+            check(ccall((:blmm_bulkscan_loco_reduced, libblmm), Cint,
+                        (Ptr{Cvoid}, Ref{BlmmOpts}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Int64}, Int64, Int64,
+                         Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Ref{BlmmReduced}, Ptr{Float64}, Ptr{Int64},
+                         Ptr{Float64}, Ref{BlmmStatus}),
+                        context(), o, Y, n, m, G, p, cs, nchr, kinship_digits, ptr_or_null(Covar), ncov, ptr_or_null(weights),
+                        h2_grid, length(h2_grid), r, cmx, carg, h2, st))
+        end
+        if !want || cnt[1] <= cap
+            raise_status(st)
+            res = (max_lod = mx, argmax = arg .+ 1, chr_max_lod = permutedims(cmx), chr_argmax = permutedims(carg) .+ 1,
+                   chromosomes = runs, chr_start = cs)
+            meth == ALT_GRID || (res = merge(res, (h2_null_list = permutedims(h2),)))
+            want || return res
+            k = cnt[1]
+            ord = sortperm(collect(zip(jj[1:k], ii[1:k])))
+            return merge(res, (marker = Int.(ii[1:k][ord]) .+ 1, trait = Int.(jj[1:k][ord]) .+ 1, lod = ll[1:k][ord]))
+        end
+        cap = cnt[1]
+    end
 end
 
 end # module

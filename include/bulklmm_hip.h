@@ -448,6 +448,36 @@ int blmm_bulkscan_loco_dev(blmm_ctx* ctx, const blmm_opts* opts, const double* d
                            const double* dweights, const double* h2_grid, int64_t ngrid, const double* dK_loco, double* dL_out,
                            int64_t ldL, double* dh2_out, blmm_status* status);
 
+/* LOCO without the LOD matrix: what blmm_bulkscan_reduced is to blmm_bulkscan, plus every chromosome's peak (the cis / trans table
+ * of an eQTL study).  Stated against the L that blmm_bulkscan_loco writes under the same opts, tuning and inputs, bit for bit:
+ *   out            as blmm_bulkscan_reduced: colmax / argmax (m each, or NULL) = blmm_lod_colmax of the whole L (argmax: the lowest
+ *                  global 0-based marker; -inf / -1 for a column with no comparable entry; NaN is never the maximum); triplets =
+ *                  the set blmm_lod_threshold gives on L (global marker indices), *count exact also beyond cap (then `cap` genuine,
+ *                  distinct triplets are stored; order unspecified)
+ *   chr_max_out / chr_argmax_out   nchr blocks of m (block c at + c m, the layout of h2_out), or NULL: blmm_lod_colmax of rows
+ *                  chr_start[c] .. chr_start[c + 1] - 1, the argmax still a GLOBAL marker index
+ *   h2_out         null-* methods: as blmm_bulkscan_loco (nchr x m); alt-grid: not written, may be NULL
+ *   status         summed over the chromosomes, as blmm_bulkscan_loco
+ * Refused as blmm_bulkscan_loco (chromosome offsets, n > 2048, NULL buffers) plus blmm_bulkscan_reduced's triplet-buffer checks,
+ * before anything is uploaded; a pending blmm_set_log10p_output request is refused (BLMM_ERR_INVALID) and consumed.
+ * Every chromosome runs blmm_bulkscan_loco's pipeline.  null-grid, and null-exact in the low-rank weights form (up to 3 null
+ * covariates), reduce in the scan epilogues into the chromosome's own partials; traits a guard flags are re-scanned into them on
+ * the device; one final kernel gives the chromosome tables and their merge.  alt-grid, c >= 4 and tuning exact_full_rank scan each
+ * chromosome into a resident block of the largest chromosome's rows and reduce it there.  No p x m matrix is allocated, and none is
+ * left resident (blmm_last_dims reports none).  blmm_last_reduced_route: 1 fused with no trait flagged, 3 fused with on-device
+ * re-scans, 2 through the per-chromosome block; the _dev form reports 0 for a fused call made without a status (it has not waited
+ * for the counts that tell 1 from 3).
+ * The _dev form: device Y / G / Covar / weights / out / tables / h2 and dK_loco as blmm_bulkscan_loco_dev; it only enqueues on the
+ * context's stream, and waits for it only for a status or to copy a host h2_grid. */
+int blmm_bulkscan_loco_reduced(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, int64_t n, int64_t m, const double* G, int64_t p,
+                               const int64_t* chr_start, int64_t nchr, int64_t kinship_digits, const double* Covar, int64_t ncov,
+                               const double* weights, const double* h2_grid, int64_t ngrid, const blmm_reduced* out, double* chr_max_out,
+                               int64_t* chr_argmax_out, double* h2_out, blmm_status* status);
+int blmm_bulkscan_loco_reduced_dev(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG, int64_t p,
+                                   const int64_t* chr_start, int64_t nchr, int64_t kinship_digits, const double* dCovar, int64_t ncov,
+                                   const double* dweights, const double* h2_grid, int64_t ngrid, const double* dK_loco, const blmm_reduced* out,
+                                   double* dchr_max_out, int64_t* dchr_argmax_out, double* dh2_out, blmm_status* status);
+
 /* ---- scan(y, G, [Z], K; assumption = "alt") -> scan_alt (src/scan.jl:397-453): the variance components are re-estimated for
  * every marker (fitlmm on [Z g_i], src/lmm.jl:56-86, one Brent search per marker on the device).
  * scalars_out = [sigma2_e, h2_null]; lod_out p; h2_each_out p (`h2_each_marker`).  opts->compat_flags:

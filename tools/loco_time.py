@@ -10,6 +10,12 @@ BXD shape (n = 79, p = 7321 in the 20 runs of tests/golden/bxd_chr_runs.json, m 
 and kinship_loco against kinship (device forms) at the BXD shape and at n = 1000, p = 1e5 (BASELINE configs[4]); then one
 configs[2]-like shape (n = 500, p = 50000, m = 2500, 20 equal chromosomes: the per-chromosome divide-and-conquer eigen path).
 Every figure is the median over --reps calls after one warm-up call.  Prints one JSON line; --out writes it to a file as well.
+--reduced: bulkscan_loco_reduced at the BXD shape instead (null-exact, null-grid), against the full-matrix forms of the same run:
+  host_reduced_ms  bulkscan_loco_reduced (host arrays in, peaks, chromosome tables and h2 out; no threshold)
+  host_reduced_thr_ms  ... with threshold = 5 (the LOD > 5 triplets too)
+  dev_reduced_ms   bulkscan_loco_reduced_dev on resident torch inputs and outputs (kinships inside the call)
+  host_loco_ms / dev_loco_ms   bulkscan_loco / bulkscan_loco_dev as above
+  phases_reduced_ms  blmm_status phase times of one timed dev call (summed over the chromosomes)
 --eig-trace: the workload for a kernel trace of the eigen phase (single against batched launches); --fold-eig-trace CSV: its summary."""
 import argparse
 import json
@@ -101,6 +107,57 @@ def shape_run(n, p, m, chrom, methods, reps, host):
     return out
 
 
+def reduced_run(reps):
+    n, m = 79, 35554
+    chrom = bxd_chrom()
+    p = len(chrom)
+    rng = np.random.default_rng(20241)
+    G = make_geno(n, p, rng)
+    Y = 10.0 + rng.standard_normal((n, m))
+    _, cs = B.chromosome_runs(chrom, p)
+    nchr = len(cs) - 1
+    dev = torch.device("cuda", 0)
+    ctx = B.Context(0, torch.cuda.current_stream().cuda_stream)
+    sync = torch.cuda.synchronize
+    dY = torch.from_numpy(np.ascontiguousarray(Y.T)).to(dev)
+    dG = torch.from_numpy(np.ascontiguousarray(G.T)).to(dev)
+    dL = torch.empty((m, p), dtype=torch.float64, device=dev)
+    dh = torch.empty((nchr, m), dtype=torch.float64, device=dev)
+    mx = torch.empty(m, dtype=torch.float64, device=dev)
+    ax = torch.empty(m, dtype=torch.int64, device=dev)
+    cmx = torch.empty((nchr, m), dtype=torch.float64, device=dev)
+    cax = torch.empty((nchr, m), dtype=torch.int64, device=dev)
+    out = {"shape": {"n": n, "p": p, "m": m, "nchr": nchr}}
+    for meth in ("null-exact", "null-grid"):
+        r = {}
+
+        def dev_loco():
+            B.bulkscan_loco_dev(ctx, dY, dG, cs, dL, dh, method=meth, h2_grid=GRID)
+            sync()
+
+        def dev_red():
+            B.bulkscan_loco_reduced_dev(ctx, dY, dG, cs, mx, ax, cmx, cax, dh, method=meth, h2_grid=GRID)
+            sync()
+
+        r["host_loco_ms"] = med(lambda: B.bulkscan_loco(Y, G, chrom, method=meth, h2_grid=GRID, ctx=ctx), reps)
+        r["dev_loco_ms"] = med(dev_loco, reps)
+        r["host_reduced_ms"] = med(lambda: B.bulkscan_loco_reduced(Y, G, chrom, method=meth, h2_grid=GRID, ctx=ctx), reps)
+        r["host_reduced_thr_ms"] = med(lambda: B.bulkscan_loco_reduced(Y, G, chrom, method=meth, h2_grid=GRID, threshold=5.0, ctx=ctx), reps)
+        r["dev_reduced_ms"] = med(dev_red, reps)
+        r["host_loco_over_host_reduced"] = r["host_loco_ms"] / r["host_reduced_ms"]
+        r["host_reduced_over_dev_loco"] = r["host_reduced_ms"] / r["dev_loco_ms"]
+        r["route"] = B.bulkscan_loco_reduced(Y[:, :64], G, chrom, method=meth, h2_grid=GRID, ctx=ctx)["route"]
+        ctx.set_timing(True)
+        st = B.bulkscan_loco_reduced_dev(ctx, dY, dG, cs, mx, ax, cmx, cax, dh, method=meth, h2_grid=GRID, status=True)
+        ctx.read_timings()
+        ctx.set_timing(False)
+        names = ("t_eigen_ms", "t_rotate_ms", "t_h2_ms", "t_prep_ms", "t_scan_ms", "t_total_ms")
+        r["phases_reduced_ms"] = {k: round(getattr(st, k), 4) for k in names}
+        out[meth] = r
+        print(meth, json.dumps(r), flush=True)
+    return out
+
+
 def kinship_run(n, p, nchr, reps):
     rng = np.random.default_rng(7)
     G = (rng.random((n, p)) < 0.5).astype(np.float64)
@@ -177,6 +234,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--no-host", action="store_true")
     ap.add_argument("--no-large", action="store_true")
+    ap.add_argument("--reduced", action="store_true")
     a = ap.parse_args()
     if a.fold_eig_trace:
         line = json.dumps(fold_eig_trace(a.fold_eig_trace))
@@ -189,6 +247,15 @@ def main():
         eig_trace(a.reps)
         return
     res = {"device": torch.cuda.get_device_name(0)}
+    if a.reduced:
+        res["reduced_bxd"] = reduced_run(a.reps)
+        line = json.dumps(res)
+        print(line)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
     res["bxd"] = shape_run(79, 7321, 35554, bxd_chrom(), ("null-exact", "null-grid"), a.reps, not a.no_host)
     res["kinship_bxd"] = kinship_run(79, 7321, 20, a.reps)
     res["kinship_n1000_p1e5"] = kinship_run(1000, 100000, 20, a.reps)
