@@ -31,7 +31,7 @@ EXPORTS = [
     "blmm_bulkscan_reduced_async", "blmm_bulkscan_perms", "blmm_bulkscan_perms_dev",
     "blmm_last_dims", "blmm_last_lod_colmax", "blmm_last_lod_columns", "blmm_multi_last_colmax", "blmm_multi_last_lod_threshold",
     "blmm_kinship_loco", "blmm_kinship_loco_dev", "blmm_bulkscan_loco", "blmm_bulkscan_loco_dev",
-    "blmm_bulkscan_loco_reduced", "blmm_bulkscan_loco_reduced_dev",
+    "blmm_bulkscan_loco_reduced", "blmm_bulkscan_loco_reduced_dev", "blmm_bulkscan_loco_perms", "blmm_bulkscan_loco_perms_dev",
 ]
 
 BLMM_NULL_EXACT, BLMM_NULL_GRID, BLMM_ALT_GRID = 0, 1, 2
@@ -208,6 +208,12 @@ def load():
     lib.blmm_bulkscan_loco_dev.argtypes = [vp, op, vp, i64, i64, vp, i64, vp, i64, i64, vp, i64, vp, vp, i64, vp, vp, i64, vp, sp]
     lib.blmm_bulkscan_loco_reduced.argtypes = [vp, op, vp, i64, i64, vp, i64, vp, i64, i64, vp, i64, vp, vp, i64, rp, vp, vp, vp, sp]
     lib.blmm_bulkscan_loco_reduced_dev.argtypes = [vp, op, vp, i64, i64, vp, i64, vp, i64, i64, vp, i64, vp, vp, i64, vp, rp, vp, vp, vp, sp]
+    # opts, Y, n, m, G, p, chr_start, nchr, kinship_digits, Covar, ncov, weights, nperms, seed, perm_idx, probs, nprobs [, dK_loco],
+    # h2, sigma2, lod_max, lod_argmax, max_perms, thr, pval, chr_lod_max, chr_lod_argmax, chr_max_perms, chr_thr, chr_pval, status
+    lib.blmm_bulkscan_loco_perms.argtypes = [vp, op, vp, i64, i64, vp, i64, vp, i64, i64, vp, i64, vp, i64, C.c_uint64, vp, vp, i64,
+                                             vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sp]
+    lib.blmm_bulkscan_loco_perms_dev.argtypes = [vp, op, vp, i64, i64, vp, i64, vp, i64, i64, vp, i64, vp, i64, C.c_uint64, vp, vp, i64,
+                                                 vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sp]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if a declared symbol is not exported
     _lib = lib

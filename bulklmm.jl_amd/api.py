@@ -1436,3 +1436,130 @@ def bulkscan_loco_reduced_dev(ctx: Context, Y, G, chr_start, max_out, argmax_out
                                                      _p(grid), ngrid, dp(K_loco), C.byref(r), dp(chr_max_out), dp(chr_argmax_out),
                                                      dp(h2_out), C.byref(st) if status else None))
     return st
+
+
+# ---- the LOCO permutation test ---------------------------------------------------------------------------------------------------
+BPERM_MAX_NPERMS = 16384   # blmm_api.hip: bperm_check -- k_bperm_summary sorts a trait's maxima in LDS
+BPERM_MAX_COVARIATES = 8   # null covariates incl. the intercept (CTPL)
+
+
+def _loco_perms_checks(n: int, nperms: int, ncov: int, addIntercept: bool, nprobs: int):
+    """The library's refusals of blmm_bulkscan_loco_perms that need no data (blmm_api.hip: loco_perms_check), before any context."""
+    _check_n(n)
+    if nperms < 0:
+        raise BulkLMMError("The required number of permutations must be a positive integer.", -9)
+    if nperms > BPERM_MAX_NPERMS:
+        raise BulkLMMError("bulkscan_loco_perms: more than 16384 permutations (the per-trait sort runs in LDS)", -10)
+    if (ncov + (1 if addIntercept else 0) if ncov > 0 else 1) > BPERM_MAX_COVARIATES:
+        raise BulkLMMError("bulkscan_loco_perms: more than 8 null covariates (incl. intercept) are not supported", -10)
+    if nprobs > 64:
+        raise BulkLMMError("bulkscan_loco_perms: 0 .. 64 threshold levels", -1)
+
+
+def bulkscan_loco_perms(Y, G, chrom, Covar=None, *, nperms: int = 1024, rndseed: int = 0, perm_idx=None, signif_level=(0.10, 0.05),
+                        kinship_digits: Optional[int] = None, weights=None, prior_variance: float = 0.0, prior_sample_size: float = 0.0,
+                        addIntercept: bool = True, reml: bool = False, optim_interval: int = 1, decomp_scheme: str = "eigen",
+                        chr_max_perms: bool = False, ctx: Optional[Context] = None, return_status: bool = False) -> dict:
+    """The leave-one-chromosome-out permutation test (blmm_bulkscan_loco_perms): bulkscan_perms on every chromosome's markers under
+    its LOCO kinship, with ONE permutation set (perm_idx, or the generator seeded once by rndseed) for every chromosome and trait,
+    and the genome-wide tables computed on the device.  With K_c = calcKinship_loco(G, chrom, kinship_digits)[c] and ref_c =
+    bulkscan_perms(Y, G[:, rows_c], K_c, Covar; same options), row c of every "chr_" table is ref_c's, bit for bit (markers global
+    and 0-based: ref_c's lod_argmax + chr_start[c], -1 kept).  Genome-wide: max_perms[b, j] = max_c chr_max_perms[c, b, j]; lod_max /
+    lod_argmax the peak over all chromosomes (lowest global marker on ties, NaN never the maximum, -inf / -1 when nothing compares);
+    thresholds get_thresholds' rule on max_perms[:, j]; pvals_perm (1 + #{b : max_perms[b, j] >= lod_max[j]}) / (nperms + 1).
+    Convention: each chromosome permutes its own rotated, reweighted null residuals (scan_perms_lite under K_c), and permutation b's
+    genome-wide maximum pairs the chromosomes' copies by b -- not one permutation of the individuals across chromosomes.  Keyword
+    defaults are bulkscan_perms'.  Returns {"h2_null", "sigma2_e": (nchr, m); "lod_max", "lod_argmax", "pvals_perm": m;
+    "max_perms": (nperms, m); "thresholds": (len(signif_level), m); "chr_lod_max", "chr_lod_argmax", "chr_pvals_perm": (nchr, m);
+    "chr_thresholds": (nchr, len(signif_level), m) [; "chr_max_perms": (nchr, nperms, m) when chr_max_perms]; "probs";
+    "chromosomes"; "chr_start" [; "status"]}.  nperms = 0: thresholds and p-values NaN."""
+    Y = _F(Y)
+    G = _F(G)
+    n, m = Y.shape
+    p = G.shape[1]
+    if G.shape[0] != n:
+        raise BulkLMMError("Dimension mismatch.", -2)
+    runs, cs = chromosome_runs(chrom, p)
+    nchr = cs.shape[0] - 1
+    nperms = int(nperms)
+    cov, ncov = None, 0
+    if Covar is not None:
+        cov = _F(Covar)
+        if cov.shape[0] != n:
+            raise BulkLMMError("Dimension mismatch.", -2)
+        ncov = cov.shape[1]
+    else:
+        addIntercept = True
+    w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).ravel())
+    if w is not None and w.shape[0] != n:
+        raise BulkLMMError("Dimension mismatch.", -2)
+    probs = np.ascontiguousarray(1.0 - np.atleast_1d(np.asarray(signif_level, dtype=np.float64)))
+    _loco_perms_checks(n, nperms, ncov, addIntercept, probs.shape[0])
+    pidx = None
+    if perm_idx is not None and nperms > 0:
+        pidx = np.asfortranarray(np.asarray(perm_idx, dtype=np.int32))
+        if pidx.shape != (n, nperms):
+            raise BulkLMMError("Dimension mismatch.", -2)
+        if pidx.size and (pidx.min() < 0 or pidx.max() >= n):
+            raise BulkLMMError("bulkscan_loco_perms: perm_idx entries must lie in 0 .. n - 1", -1)
+    o = _opts(L.BLMM_NULL_EXACT, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
+    ctx = ctx or default_context()  # after the argument checks: those must not need a GPU
+    npr = probs.shape[0]
+    h2, s2 = np.empty((nchr, m)), np.empty((nchr, m))          # row c: chromosome c (C order = the library's blocks)
+    mx, pv = np.empty(m), np.empty(m)
+    arg = np.empty(m, dtype=np.int64)
+    mp = np.empty((max(nperms, 1), m), order="F")
+    thr = np.empty((npr, m), order="F")
+    cmx, cpv = np.empty((nchr, m)), np.empty((nchr, m))
+    carg = np.empty((nchr, m), dtype=np.int64)
+    cthr = np.empty((nchr, m, npr))                             # block c: nprobs x m column-major
+    cmp = np.empty((nchr, m, max(nperms, 1))) if chr_max_perms else None
+    st = L.blmm_status()
+    ctx.check(ctx.lib.blmm_bulkscan_loco_perms(ctx.h, C.byref(o), _p(Y), n, m, _p(G), p, _p(cs), nchr,
+                                               -1 if kinship_digits is None else int(kinship_digits), _p(cov), ncov, _p(w), nperms,
+                                               C.c_uint64(int(rndseed)), _p(pidx), _p(probs), npr, _p(h2), _p(s2), _p(mx), _p(arg),
+                                               _p(mp), _p(thr), _p(pv), _p(cmx), _p(carg), _p(cmp), _p(cthr), _p(cpv), C.byref(st)))
+    _raise_status(st)
+    out = {"h2_null": h2, "sigma2_e": s2, "lod_max": mx, "lod_argmax": arg, "max_perms": mp[:nperms], "thresholds": thr,
+           "pvals_perm": pv, "chr_lod_max": cmx, "chr_lod_argmax": carg, "chr_thresholds": cthr.transpose(0, 2, 1),
+           "chr_pvals_perm": cpv, "probs": probs, "chromosomes": runs, "chr_start": cs}
+    if chr_max_perms:
+        out["chr_max_perms"] = cmp.transpose(0, 2, 1)[:, :nperms]
+    if return_status:
+        out["status"] = st
+    return out
+
+
+def bulkscan_loco_perms_dev(ctx: Context, Y, G, chr_start, h2_out, sigma2_out, lod_max_out, lod_argmax_out, max_perms_out=None,
+                            thr_out=None, pval_out=None, chr_lod_max_out=None, chr_lod_argmax_out=None, chr_max_perms_out=None,
+                            chr_thr_out=None, chr_pval_out=None, *, nperms: int, seed: int = 0, perm_idx=None,
+                            signif_level=(0.10, 0.05), K_loco=None, kinship_digits: Optional[int] = None, Covar=None, weights=None,
+                            addIntercept: bool = True, prior_variance: float = 0.0, prior_sample_size: float = 0.0, reml: bool = False,
+                            optim_interval: int = 1, decomp_scheme: str = "eigen", status: bool = False):
+    """blmm_bulkscan_loco_perms_dev on torch CUDA tensors (layouts as bulkscan_loco_dev / bulkscan_perms_dev): Y (m, n), G (p, n);
+    chr_start: nchr + 1 host offsets; K_loco (nchr, n, n) as calcKinship_loco, or None (computed on the device); h2_out /
+    sigma2_out / chr_lod_max_out / chr_pval_out (nchr, m) float64, chr_lod_argmax_out (nchr, m) int64; lod_max_out / pval_out (m,)
+    float64, lod_argmax_out (m,) int64; max_perms_out (m, nperms) [= nperms x m column-major]; thr_out (m, len(signif_level));
+    chr_thr_out (nchr, m, len(signif_level)); chr_max_perms_out (nchr, m, nperms); perm_idx (nperms, n) int32 or None (the
+    library's generator with `seed`).  Outputs after lod_argmax_out may be None.  Enqueues on the context's stream (status=True
+    synchronises it)."""
+    m, n = Y.shape
+    p = G.shape[0]
+    cs = _check_chr_start(chr_start, p)
+    nchr = cs.shape[0] - 1
+    ncov = 0 if Covar is None else Covar.shape[0]
+    if Covar is None:
+        addIntercept = True
+    probs = np.ascontiguousarray(1.0 - np.atleast_1d(np.asarray(signif_level, dtype=np.float64)))
+    _loco_perms_checks(n, int(nperms), ncov, addIntercept, probs.shape[0])
+    o = _opts(L.BLMM_NULL_EXACT, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
+    st = L.blmm_status() if status else None
+    dp = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+    ctx.check(ctx.lib.blmm_bulkscan_loco_perms_dev(ctx.h, C.byref(o), Y.data_ptr(), n, m, G.data_ptr(), p, _p(cs), nchr,
+                                                   -1 if kinship_digits is None else int(kinship_digits), dp(Covar), ncov, dp(weights),
+                                                   int(nperms), C.c_uint64(int(seed)), dp(perm_idx), _p(probs), probs.shape[0],
+                                                   dp(K_loco), dp(h2_out), dp(sigma2_out), dp(lod_max_out), dp(lod_argmax_out),
+                                                   dp(max_perms_out), dp(thr_out), dp(pval_out), dp(chr_lod_max_out),
+                                                   dp(chr_lod_argmax_out), dp(chr_max_perms_out), dp(chr_thr_out), dp(chr_pval_out),
+                                                   C.byref(st) if status else None))
+    return st

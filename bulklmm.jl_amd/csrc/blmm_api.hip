@@ -856,7 +856,8 @@ void blmm_destroy(blmm_ctx* ctx) {
                     &ctx->EllTab, &ctx->inY, &ctx->inG, &ctx->inK, &ctx->inCov, &ctx->inW, &ctx->outL, &ctx->outH2,
                     &ctx->tmpA, &ctx->tmpB, &ctx->tmpC, &ctx->perm, &ctx->r0, &ctx->altbuf, &ctx->logtab, &ctx->lraw,
                     &ctx->wbQ, &ctx->wbW, &ctx->wbRk, &ctx->lrT, &ctx->lrC, &ctx->lrL, &ctx->lrFlag, &ctx->lrPart, &ctx->lrPerm, &ctx->lrDen0, &ctx->eigW, &ctx->xf32, &ctx->pf32, &ctx->brSt, &ctx->brList, &ctx->illList, &ctx->qrSlab, &ctx->lodtab, &ctx->dynFac, &ctx->pvtab, &ctx->outP, &ctx->redbuf, &ctx->redtrip, &ctx->altC, &ctx->rf32, &ctx->btG, &ctx->redflag, &ctx->bperm,
-                    &ctx->locoK, &ctx->locoPart, &ctx->locoChr, &ctx->locoStat, &ctx->locoKs, &ctx->locoV, &ctx->locoLraw};
+                    &ctx->locoK, &ctx->locoPart, &ctx->locoChr, &ctx->locoStat, &ctx->locoKs, &ctx->locoV, &ctx->locoLraw,
+                    &ctx->locoCmx, &ctx->locoCarg, &ctx->locoPerm};
   for (DevBuf* b : bufs) if (b->p) hipFree(b->p);
   for (auto& s : ctx->evsets) for (auto& e : s.e) (void)hipEventDestroy(e);
   if (ctx->side) { (void)hipStreamSynchronize(ctx->side); (void)hipStreamDestroy(ctx->side); }
@@ -1667,6 +1668,76 @@ struct LocoRed {
   int64_t ld = 0;
 };
 
+// The chromosomes largest first (blmm_bulkscan_loco's run order), ties in genome order
+static std::vector<int64_t> loco_order(const int64_t* chr, int64_t nchr) {
+  std::vector<int64_t> order((size_t)nchr);
+  for (int64_t c = 0; c < nchr; ++c) order[(size_t)c] = c;
+  std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return chr[a + 1] - chr[a] > chr[b + 1] - chr[b]; });
+  return order;
+}
+
+// per-matrix strides of the batched eigen phase's workspace (locoKs, locoV, locoLraw)
+static int64_t loco_sA(int64_t n) { return round_up(n * n, 32); }
+static int64_t loco_sE(int64_t n) { return round_up(n * n + 4 * n + 16, 32); }
+static int64_t loco_sL(int64_t n) { return round_up(n, 32); }
+
+// n <= eig_fast_max_n() (the fast path is what a single call runs there): the design of every chromosome's kinship, then ONE set of
+// eigen launches for all of them (launch_eig_fast_batch: matrix c on blockIdx.y, its own workspace and status words); each
+// chromosome's prepare_eigen runs only the Jacobi check behind it and the post-eigen work (loco_eig_pre).  Beyond: per chromosome,
+// unbatched (*batched = false).
+static int loco_eigen_batch(blmm_ctx* ctx, const blmm_opts* opts, int64_t n, const double* dK, int64_t nchr, const double* dCovar,
+                            int64_t ncov, const double* dweights, int64_t* dst_all, Timer& tb, bool* batched) {
+  *batched = n >= 3 && n <= eig_fast_max_n() && !dev_env("BLMM_EIGEN") && ctx->tune.eigen_solver == 0;
+  if (!*batched) return BLMM_OK;
+  const int64_t sA = loco_sA(n), sE = loco_sE(n), sL = loco_sL(n);
+  const NullCov nc = null_cov(opts, dCovar, ncov);
+  if (nc.c < 1 || nc.c > CMAX) return fail(ctx, BLMM_ERR_UNSUPPORTED, BLMM_C_ERR);
+  if (nc.c >= n) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
+  int rc;
+  if ((rc = ensure(ctx, ctx->locoKs, sizeof(double) * (size_t)nchr * sA)) || (rc = ensure(ctx, ctx->locoV, sizeof(double) * (size_t)nchr * sE)) ||
+      (rc = ensure(ctx, ctx->locoLraw, sizeof(double) * (size_t)nchr * sL)) || (rc = ensure(ctx, ctx->Zs, sizeof(double) * n * nc.c))) return rc;
+  BLMM_HIP(hipMemsetAsync(dst_all, 0, sizeof(int64_t) * NSTAT * (size_t)nchr, ctx->stream));
+  tb.mark();
+  for (int64_t c = 0; c < nchr; ++c)
+    if ((rc = launch_design(ctx, dK + (size_t)c * n * n, nc.d, (int)nc.ncov, nc.add_int, dweights, (int)n, ptr<double>(ctx->locoKs) + (size_t)c * sA,
+                            ptr<double>(ctx->Zs)))) return rc;
+  if ((rc = launch_eig_fast_batch(ctx, ptr<double>(ctx->locoKs), sA, (int)n, (int)nchr, ptr<double>(ctx->locoLraw), sL,
+                                  ptr<double>(ctx->locoV), sE, dst_all, NSTAT))) return rc;
+  tb.mark();
+  return BLMM_OK;
+}
+
+// chromosome c's share of the batched eigen phase (prepare's `pre`; used only when loco_eigen_batch ran)
+static EigPre loco_eig_pre(blmm_ctx* ctx, int64_t n, int64_t c, int64_t* dst_all) {
+  return EigPre{ptr<double>(ctx->locoKs) + (size_t)c * loco_sA(n), ptr<double>(ctx->locoV) + (size_t)c * loco_sE(n),
+                ptr<double>(ctx->locoLraw) + (size_t)c * loco_sL(n), dst_all + (size_t)c * NSTAT};
+}
+
+// after chromosome c: the next one reuses every buffer this one's side-stream work reads, so the main stream waits for both side
+// streams; its status block goes aside (dst_all + c NSTAT) unless the batched eigen phase already kept it there
+static int loco_chr_done(blmm_ctx* ctx, const Pipe& P, int64_t c, int64_t* dst_all) {
+  BLMM_HIP(hipEventRecord(ctx->ev_fork, ctx->side));
+  BLMM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_fork, 0));
+  BLMM_HIP(hipEventRecord(ctx->ev_fork, ctx->side2));
+  BLMM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_fork, 0));
+  if (P.stat != dst_all + (size_t)c * NSTAT)
+    BLMM_HIP(hipMemcpyAsync(dst_all + (size_t)c * NSTAT, P.stat, sizeof(int64_t) * NSTAT, hipMemcpyDeviceToDevice, ctx->stream));
+  return BLMM_OK;
+}
+
+// the context's status block is what blmm_lowrank_profile / blmm_lowrank_columns read: the last chromosome's, as after a run of
+// single calls (the batched path kept every chromosome's block in locoStat instead)
+static int loco_last_stat(blmm_ctx* ctx, bool batched, const std::vector<int64_t>& order, const int64_t* dst_all) {
+  if (!batched || order.empty()) return BLMM_OK;
+  int rc;
+  if ((rc = ensure(ctx, ctx->stat, sizeof(int64_t) * NSTAT))) return rc;
+  BLMM_HIP(hipMemcpyAsync(ctx->stat.p, dst_all + (size_t)order.back() * NSTAT, sizeof(int64_t) * NSTAT, hipMemcpyDeviceToDevice, ctx->stream));
+  return BLMM_OK;
+}
+
+static int loco_status(blmm_ctx* ctx, const int64_t* dst_all, int64_t nchr, bool audit, const Timer& t0, const Timer& tb,
+                       const std::vector<Timer>& tms, blmm_status* status);
+
 // The pipeline: the kinships (unless given), then per chromosome the whole bulkscan front and scan on its column block, into its rows
 // of L (or, red given, into its reduction).  The chromosomes run largest first, so that no p-sized workspace grows -- and no buffer is
 // freed under queued work -- after the first of them; each one's status block is copied aside (locoStat) and summed once at the end.
@@ -1691,30 +1762,10 @@ static int loco_pipeline(blmm_ctx* ctx, const blmm_opts* opts, const double* dY,
   }
   if ((rc = ensure(ctx, ctx->locoStat, sizeof(int64_t) * NSTAT * (size_t)nchr))) return rc;
   int64_t* dst_all = ptr<int64_t>(ctx->locoStat);
-  std::vector<int64_t> order((size_t)nchr);
-  for (int64_t c = 0; c < nchr; ++c) order[(size_t)c] = c;
-  std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return chr[a + 1] - chr[a] > chr[b + 1] - chr[b]; });
+  const std::vector<int64_t> order = loco_order(chr, nchr);
   Timer tb(ctx);
-  // n <= eig_fast_max_n() (the fast path is what a single call runs there): the design of every chromosome's kinship, then ONE set of
-  // eigen launches for all of them (launch_eig_fast_batch: matrix c on blockIdx.y, its own workspace and status words); each
-  // chromosome's prepare_eigen runs only the Jacobi check behind it and the post-eigen work.  Beyond: per chromosome, unbatched.
-  const bool batched = n >= 3 && n <= eig_fast_max_n() && !dev_env("BLMM_EIGEN") && ctx->tune.eigen_solver == 0;
-  const int64_t sA = round_up(n * n, 32), sE = round_up(n * n + 4 * n + 16, 32), sL = round_up(n, 32);
-  if (batched) {
-    const NullCov nc = null_cov(opts, dCovar, ncov);
-    if (nc.c < 1 || nc.c > CMAX) return fail(ctx, BLMM_ERR_UNSUPPORTED, BLMM_C_ERR);
-    if (nc.c >= n) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
-    if ((rc = ensure(ctx, ctx->locoKs, sizeof(double) * (size_t)nchr * sA)) || (rc = ensure(ctx, ctx->locoV, sizeof(double) * (size_t)nchr * sE)) ||
-        (rc = ensure(ctx, ctx->locoLraw, sizeof(double) * (size_t)nchr * sL)) || (rc = ensure(ctx, ctx->Zs, sizeof(double) * n * nc.c))) return rc;
-    BLMM_HIP(hipMemsetAsync(dst_all, 0, sizeof(int64_t) * NSTAT * (size_t)nchr, ctx->stream));
-    tb.mark();
-    for (int64_t c = 0; c < nchr; ++c)
-      if ((rc = launch_design(ctx, dK + (size_t)c * n * n, nc.d, (int)nc.ncov, nc.add_int, dweights, (int)n, ptr<double>(ctx->locoKs) + (size_t)c * sA,
-                              ptr<double>(ctx->Zs)))) return rc;
-    if ((rc = launch_eig_fast_batch(ctx, ptr<double>(ctx->locoKs), sA, (int)n, (int)nchr, ptr<double>(ctx->locoLraw), sL,
-                                    ptr<double>(ctx->locoV), sE, dst_all, NSTAT))) return rc;
-    tb.mark();
-  }
+  bool batched = false;
+  if ((rc = loco_eigen_batch(ctx, opts, n, dK, nchr, dCovar, ncov, dweights, dst_all, tb, &batched))) return rc;
   std::vector<Timer> tms;
   tms.reserve((size_t)nchr);
   const bool alt = opts->method == BLMM_ALT_GRID;
@@ -1725,8 +1776,7 @@ static int loco_pipeline(blmm_ctx* ctx, const blmm_opts* opts, const double* dY,
     tms.emplace_back(ctx);
     Timer& tm = tms.back();
     Pipe P;
-    const EigPre pre{ptr<double>(ctx->locoKs) + (size_t)c * sA, ptr<double>(ctx->locoV) + (size_t)c * sE,
-                     ptr<double>(ctx->locoLraw) + (size_t)c * sL, dst_all + (size_t)c * NSTAT};
+    const EigPre pre = loco_eig_pre(ctx, n, c, dst_all);
     if ((rc = prepare(ctx, opts, dY, n, m, dG + (size_t)n * s0, pc, dCovar, ncov, dK + (size_t)c * n * n, dweights, 1, P, tm, lowrank,
                       opts->method != BLMM_NULL_EXACT, false, batched ? &pre : nullptr)))
       return rc;
@@ -1755,20 +1805,9 @@ static int loco_pipeline(blmm_ctx* ctx, const blmm_opts* opts, const double* dY,
       if (o->want_triplets && (rc = launch_threshold_rows(ctx, Lc, pc, m, ldc, o->thr, o->cap, o->ti, o->tj, o->tlod, o->count, s0))) return rc;
     }
     audit = audit || ctx->audit_ran;
-    // the next chromosome reuses every buffer this one's side-stream work reads: the main stream waits for both side streams
-    BLMM_HIP(hipEventRecord(ctx->ev_fork, ctx->side));
-    BLMM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_fork, 0));
-    BLMM_HIP(hipEventRecord(ctx->ev_fork, ctx->side2));
-    BLMM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_fork, 0));
-    if (P.stat != dst_all + (size_t)c * NSTAT)
-      BLMM_HIP(hipMemcpyAsync(dst_all + (size_t)c * NSTAT, P.stat, sizeof(int64_t) * NSTAT, hipMemcpyDeviceToDevice, ctx->stream));
+    if ((rc = loco_chr_done(ctx, P, c, dst_all))) return rc;
   }
-  // the context's status block is what blmm_lowrank_profile / blmm_lowrank_columns read: the last chromosome's, as after a run of
-  // single calls (the batched path kept every chromosome's block in locoStat instead)
-  if (batched && !order.empty()) {
-    if ((rc = ensure(ctx, ctx->stat, sizeof(int64_t) * NSTAT))) return rc;
-    BLMM_HIP(hipMemcpyAsync(ctx->stat.p, dst_all + (size_t)order.back() * NSTAT, sizeof(int64_t) * NSTAT, hipMemcpyDeviceToDevice, ctx->stream));
-  }
+  if ((rc = loco_last_stat(ctx, batched, order, dst_all))) return rc;
   if (red) {
     const int64_t* dchr = nullptr;
     const bool sl = red->fused;
@@ -1778,7 +1817,15 @@ static int loco_pipeline(blmm_ctx* ctx, const blmm_opts* opts, const double* dY,
   }
   PvCall pvc(ctx, pvreq);                    // (never fused: a column pass over the finished L)
   if ((rc = pvc.resolve(p, m)) || (rc = pvc.finish(p, m, dL, ldL))) return rc;
+  return loco_status(ctx, dst_all, nchr, audit, t0, tb, tms, status);
+}
+
+// The chromosomes' status blocks (dst_all, nchr x NSTAT) summed into *status, with the phase times of every chromosome's Timer (tms),
+// the batched eigen phase (tb) and the whole call from t0's mark; nothing without a status.
+static int loco_status(blmm_ctx* ctx, const int64_t* dst_all, int64_t nchr, bool audit, const Timer& t0, const Timer& tb,
+                       const std::vector<Timer>& tms, blmm_status* status) {
   if (!status) return BLMM_OK;
+  int rc;
   std::vector<int64_t> h((size_t)nchr * NSTAT);
   BLMM_HIP(hipMemcpyAsync(h.data(), dst_all, sizeof(int64_t) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
   BLMM_HIP(hipStreamSynchronize(ctx->stream));
@@ -2294,17 +2341,72 @@ struct BpermOut {
   double *h2, *sigma2, *lod_max; int64_t* lod_argmax; double *max_perms, *thr, *pval;
 };
 static int bperm_check(blmm_ctx* ctx, const blmm_opts* opts, int64_t n, int64_t m, int64_t p, const double* Covar, int64_t ncov,
-                       int64_t nperms, const double* probs, int64_t nprobs, bool have_in, const BpermOut& o) {
+                       int64_t nperms, const double* probs, int64_t nprobs, bool have_in, const BpermOut& o,
+                       const char* who = "bulkscan_perms") {
+  const std::string w(who);
   int rc = check_opts(ctx, opts);
   if (rc) return rc;
   if (nperms < 0) return fail(ctx, BLMM_ERR_NPERMS, "The required number of permutations must be a positive integer.");
-  if (!have_in || !o.h2 || !o.sigma2 || !o.lod_max || !o.lod_argmax) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_perms: NULL buffer");
-  if (nprobs < 0 || nprobs > 64 || (nprobs > 0 && !probs)) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_perms: 0 .. 64 threshold levels");
+  if (!have_in || !o.h2 || !o.sigma2 || !o.lod_max || !o.lod_argmax) return fail(ctx, BLMM_ERR_INVALID, w + ": NULL buffer");
+  if (nprobs < 0 || nprobs > 64 || (nprobs > 0 && !probs)) return fail(ctx, BLMM_ERR_INVALID, w + ": 0 .. 64 threshold levels");
   if (n < 1 || m < 0 || p < 0 || ncov < 0 || m > 0x7fffffffLL || p > 0x7fffffffLL) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
   if (nperms > BPERM_MAX_NPERMS)
-    return fail(ctx, BLMM_ERR_UNSUPPORTED, "bulkscan_perms: more than 16384 permutations (the per-trait sort runs in LDS)");
+    return fail(ctx, BLMM_ERR_UNSUPPORTED, w + ": more than 16384 permutations (the per-trait sort runs in LDS)");
   if (null_cov(opts, Covar, ncov).c > CTPL)
-    return fail(ctx, BLMM_ERR_UNSUPPORTED, "bulkscan_perms: more than 8 null covariates (incl. intercept) are not supported");
+    return fail(ctx, BLMM_ERR_UNSUPPORTED, w + ": more than 8 null covariates (incl. intercept) are not supported");
+  return BLMM_OK;
+}
+
+// Traits per chunk: per panel column its k-major panel (npad doubles), its reduction partials (nslot x 12 bytes), bin, maximum and
+// marker; per trait its row of marker norms, r0 and the panel coefficients.  Default budget 4 GiB of workspace.
+static int64_t bperm_chunk_traits(const blmm_ctx* ctx, int64_t npad, int64_t ldx, int64_t n, int64_t p, int64_t nperms) {
+  const int64_t np1 = nperms + 1;
+  const int nslot = 2 * (int)((p + 127) / 128);
+  const double col_bytes = 8.0 * npad + 12.0 * nslot + 20.0 + 8.0 * (CMAX + 1);
+  const double trait_bytes = np1 * col_bytes + 8.0 * (double)ldx + 8.0 * n;
+  int64_t mt_max = ctx->tune.bulk_perm_cols > 0 ? ctx->tune.bulk_perm_cols / np1 : (int64_t)((double)(4ll << 30) / trait_bytes);
+  return std::max<int64_t>(1, std::min<int64_t>(mt_max, 65535));
+}
+
+// The genome-wide buffer of blmm_bulkscan_loco_perms: (nperms + 1) x m column maxima and their global markers
+struct BpermMerge { double* gmx = nullptr; int64_t* garg = nullptr; };
+
+// Chunks of whole traits of one rotation (P: the p markers and the m rotated traits; nm its null model; o.h2 the traits' h2): the
+// isx / panel / reduce-in-epilogue scan / k_red_final chain, then the per-trait summary into o (markers + row0).  mg (LOCO): every
+// chunk's column maxima also fold into the genome-wide buffer.
+static int bperm_chunks(blmm_ctx* ctx, const Pipe& P, const NullModel& nm, int64_t m, int64_t p, const int32_t* perm, int64_t nperms,
+                        int64_t mt_max, const BpermProbs& pr, int64_t nprobs, const BpermOut& o, int64_t row0, const BpermMerge* mg) {
+  int rc;
+  const int64_t np1 = nperms + 1;
+  const int nslot = 2 * (int)((p + 127) / 128);
+  const bool summary = o.lod_max || o.lod_argmax || o.max_perms || o.thr || o.pval;
+  for (int64_t j0 = 0; j0 < m; j0 += mt_max) {
+    const int64_t mt = std::min(mt_max, m - j0), ncols = mt * np1, ldp = round_up(ncols, 128), ldm = round_up(ncols, 64);
+    if ((rc = ensure(ctx, ctx->panels, sizeof(double) * (size_t)P.npad * ldp)) ||
+        (rc = ensure(ctx, ctx->isx, sizeof(double) * (size_t)P.ldx * mt)) ||
+        (rc = ensure(ctx, ctx->redbuf, (sizeof(double) + sizeof(int)) * (size_t)nslot * (size_t)ldm)) ||
+        (rc = ensure(ctx, ctx->bperm, (sizeof(double) + sizeof(int64_t) + sizeof(int)) * (size_t)ldp))) return rc;
+    double* mx = ptr<double>(ctx->bperm);
+    int64_t* arg = reinterpret_cast<int64_t*>(mx + ldp);
+    int* bin = reinterpret_cast<int*>(arg + ldp);
+    const double* h2c = o.h2 + j0;
+    if (p > 0 && (rc = launch_isx(ctx, nm, P.Xt, P.ldx, p, P.Z0, P.lam, h2c, (int)mt, ptr<double>(ctx->isx), P.ldx, P.stat))) return rc;
+    if ((rc = launch_bperm_panels(ctx, nm, P.Yt + j0, P.ldy, P.Z0, P.lam, h2c, mt, perm, nperms, ptr<double>(ctx->panels), ldp, bin, P.stat))) return rc;
+    if (p > 0) {
+      RedArgs r;
+      r.pmax = ptr<double>(ctx->redbuf); r.parg = reinterpret_cast<int*>(r.pmax + (size_t)nslot * ldm); r.ldm = ldm;
+      ScanArgs a = scan_args(ctx, P, ptr<double>(ctx->panels), ldp, nullptr, 0, ncols);
+      a.isx = ptr<double>(ctx->isx); a.ld_isx = P.ldx; a.bin = bin;
+      a.Pv = nullptr; a.red = r;
+      if ((rc = launch_scan_table(ctx, a)) || (rc = launch_red_final(ctx, r, nslot, ncols, mx, arg))) return rc;
+    } else {                                    // no markers: every column's maximum is -inf at marker -1 (k_colmax's empty column)
+      if ((rc = fill(ctx, mx, ncols, -INFINITY))) return rc;
+      BLMM_HIP(hipMemsetAsync(arg, 0xff, sizeof(int64_t) * (size_t)ncols, ctx->stream));
+    }
+    if (summary && (rc = launch_bperm_summary(ctx, mx, arg, mt, nperms, pr, (int)nprobs, j0, o.lod_max, o.lod_argmax, o.max_perms, o.thr,
+                                              o.pval, row0))) return rc;
+    if (mg && (rc = launch_bperm_loco_merge(ctx, mx, arg, ncols, row0, mg->gmx + (size_t)j0 * np1, mg->garg + (size_t)j0 * np1))) return rc;
+  }
   return BLMM_OK;
 }
 
@@ -2334,39 +2436,8 @@ static int bulk_perms_impl(blmm_ctx* ctx, const blmm_opts* opts, const double* d
     ctx->perm_ready = false;                    // consumed here, not by a later launch_perm_panel
     perm = ptr<int32_t>(ctx->perm);
   }
-  // Chunks of whole traits.  Per panel column: its k-major panel (npad doubles), its reduction partials (nslot x 12 bytes), bin,
-  // maximum and marker; per trait: its row of marker norms, r0 and the panel coefficients.  Default budget 4 GiB of workspace.
-  const int64_t np1 = nperms + 1;
-  const int nslot = 2 * (int)((p + 127) / 128);
-  const double col_bytes = 8.0 * P.npad + 12.0 * nslot + 20.0 + 8.0 * (CMAX + 1);
-  const double trait_bytes = np1 * col_bytes + 8.0 * (double)P.ldx + 8.0 * n;
-  int64_t mt_max = ctx->tune.bulk_perm_cols > 0 ? ctx->tune.bulk_perm_cols / np1 : (int64_t)((double)(4ll << 30) / trait_bytes);
-  mt_max = std::max<int64_t>(1, std::min<int64_t>(mt_max, 65535));
-  for (int64_t j0 = 0; j0 < m; j0 += mt_max) {
-    const int64_t mt = std::min(mt_max, m - j0), ncols = mt * np1, ldp = round_up(ncols, 128), ldm = round_up(ncols, 64);
-    if ((rc = ensure(ctx, ctx->panels, sizeof(double) * (size_t)P.npad * ldp)) ||
-        (rc = ensure(ctx, ctx->isx, sizeof(double) * (size_t)P.ldx * mt)) ||
-        (rc = ensure(ctx, ctx->redbuf, (sizeof(double) + sizeof(int)) * (size_t)nslot * (size_t)ldm)) ||
-        (rc = ensure(ctx, ctx->bperm, (sizeof(double) + sizeof(int64_t) + sizeof(int)) * (size_t)ldp))) return rc;
-    double* mx = ptr<double>(ctx->bperm);
-    int64_t* arg = reinterpret_cast<int64_t*>(mx + ldp);
-    int* bin = reinterpret_cast<int*>(arg + ldp);
-    const double* h2c = o.h2 + j0;
-    if (p > 0 && (rc = launch_isx(ctx, nm, P.Xt, P.ldx, p, P.Z0, P.lam, h2c, (int)mt, ptr<double>(ctx->isx), P.ldx, P.stat))) return rc;
-    if ((rc = launch_bperm_panels(ctx, nm, P.Yt + j0, P.ldy, P.Z0, P.lam, h2c, mt, perm, nperms, ptr<double>(ctx->panels), ldp, bin, P.stat))) return rc;
-    if (p > 0) {
-      RedArgs r;
-      r.pmax = ptr<double>(ctx->redbuf); r.parg = reinterpret_cast<int*>(r.pmax + (size_t)nslot * ldm); r.ldm = ldm;
-      ScanArgs a = scan_args(ctx, P, ptr<double>(ctx->panels), ldp, nullptr, 0, ncols);
-      a.isx = ptr<double>(ctx->isx); a.ld_isx = P.ldx; a.bin = bin;
-      a.Pv = nullptr; a.red = r;
-      if ((rc = launch_scan_table(ctx, a)) || (rc = launch_red_final(ctx, r, nslot, ncols, mx, arg))) return rc;
-    } else {                                    // no markers: every column's maximum is -inf at marker -1 (k_colmax's empty column)
-      if ((rc = fill(ctx, mx, ncols, -INFINITY))) return rc;
-      BLMM_HIP(hipMemsetAsync(arg, 0xff, sizeof(int64_t) * (size_t)ncols, ctx->stream));
-    }
-    if ((rc = launch_bperm_summary(ctx, mx, arg, mt, nperms, pr, (int)nprobs, j0, o.lod_max, o.lod_argmax, o.max_perms, o.thr, o.pval))) return rc;
-  }
+  const int64_t mt_max = bperm_chunk_traits(ctx, P.npad, P.ldx, n, p, nperms);
+  if ((rc = bperm_chunks(ctx, P, nm, m, p, perm, nperms, mt_max, pr, nprobs, o, 0, nullptr))) return rc;
   tm.mark();
   return end_call(ctx, P, status, &tm);
 }
@@ -2409,6 +2480,173 @@ int blmm_bulkscan_perms(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, i
       (rc = hc.down(lod_max_out, o.lod_max, sizeof(double) * mm)) || (rc = hc.down(lod_argmax_out, o.lod_argmax, sizeof(int64_t) * mm)) ||
       (rc = hc.down(pval_out, o.pval, sizeof(double) * mm)) || (rc = hc.down(thr_out, o.thr, sizeof(double) * mm * nprobs))) return rc;
   if (max_perms_out && (rc = copy_to_host(ctx, max_perms_out, o.max_perms, sizeof(double) * mm * nperms))) return rc;
+  return (rc = hc.finish()) ? rc : check_sticky(ctx);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The LOCO permutation test (include/bulklmm_hip.h: blmm_bulkscan_loco_perms): blmm_bulkscan_perms on every chromosome's column block
+// under its LOCO kinship, with one permutation set for all of them, and the genome-wide tables from the chromosomes' column maxima
+// paired by permutation index.  g: the genome-wide outputs (g.h2 / g.sigma2: nchr x m); chr_*: the per-chromosome tables, each
+// optional, block c at + c (m, nprobs m, nperms m).
+struct LocoPermOut {
+  BpermOut g;
+  double* chr_lod_max; int64_t* chr_lod_argmax; double *chr_max_perms, *chr_thr, *chr_pval;
+};
+
+// every refusal of the call that needs no device: bperm_check's, loco_check's, n > 2048
+static int loco_perms_check(blmm_ctx* ctx, const blmm_opts* opts, int64_t n, int64_t m, int64_t p, const int64_t* chr, int64_t nchr,
+                            int64_t kdigits, const double* Covar, int64_t ncov, int64_t nperms, const double* probs, int64_t nprobs,
+                            bool have_in, const LocoPermOut& o) {
+  int rc = bperm_check(ctx, opts, n, m, p, Covar, ncov, nperms, probs, nprobs, have_in, o.g, "bulkscan_loco_perms");
+  if (rc || (rc = loco_check(ctx, n, p, chr, nchr, "bulkscan_loco_perms"))) return rc;
+  if (kdigits > 300) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_loco_perms: bad arguments");
+  if (n > 2048) return fail(ctx, BLMM_ERR_UNSUPPORTED, "more than 2048 individuals: the device eigensolver (tridiagonalisation + divide and conquer) stops at n = 2048");
+  return BLMM_OK;
+}
+
+// The kinships (unless given) and the batched eigen phase as blmm_bulkscan_loco; the permutation set once; then per chromosome,
+// largest first, bulk_perms_impl's front (prepare on its column block, launch_rotate_single, launch_brent) and trait chunks, whose
+// column maxima also fold into the genome-wide buffer (locoPerm); one summary of that buffer after the last chromosome.
+static int loco_perms_impl(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG, int64_t p,
+                           const int64_t* chr, int64_t nchr, int64_t kdigits, const double* dCovar, int64_t ncov, const double* dweights,
+                           const double* dK_loco, int64_t nperms, uint64_t seed, const int32_t* dperm_idx, const double* probs,
+                           int64_t nprobs, const LocoPermOut& o, blmm_status* status) {
+  int rc = loco_perms_check(ctx, opts, n, m, p, chr, nchr, kdigits, dCovar, ncov, nperms, probs, nprobs, dY && dG, o);
+  if (rc || (rc = enter_device(ctx))) return rc;
+  BpermProbs pr;
+  for (int t = 0; t < 64; ++t) pr.v[t] = t < nprobs ? probs[t] : 0.0;
+  if (ctx->ev_used + (size_t)nchr + 2 >= 4096) ctx->ev_used = 0;
+  ctx->evsets.reserve(ctx->ev_used + (size_t)nchr + 2);
+  Timer t0(ctx);
+  t0.mark();
+  ctx->perm_ready = false;
+  clear_last(ctx);                              // no matrix of this call (and the workspace it sat in is reused)
+  const double* dK = dK_loco;
+  if (!dK) {
+    if ((rc = ensure(ctx, ctx->locoK, sizeof(double) * (size_t)n * n * nchr)) ||
+        (rc = kinship_loco_impl(ctx, dG, n, chr, nchr, kdigits, ptr<double>(ctx->locoK)))) return rc;
+    dK = ptr<double>(ctx->locoK);
+  }
+  if ((rc = ensure(ctx, ctx->locoStat, sizeof(int64_t) * NSTAT * (size_t)nchr))) return rc;
+  int64_t* dst_all = ptr<int64_t>(ctx->locoStat);
+  const std::vector<int64_t> order = loco_order(chr, nchr);
+  Timer tb(ctx);
+  bool batched = false;
+  if ((rc = loco_eigen_batch(ctx, opts, n, dK, nchr, dCovar, ncov, dweights, dst_all, tb, &batched))) return rc;
+  // the genome-wide column maxima, -inf / -1 until the first chromosome folds in
+  const int64_t np1 = nperms + 1, gcols = np1 * m;
+  BpermMerge mg;
+  if (m > 0) {
+    if ((rc = ensure(ctx, ctx->locoPerm, (sizeof(double) + sizeof(int64_t)) * (size_t)gcols))) return rc;
+    mg.gmx = ptr<double>(ctx->locoPerm);
+    mg.garg = reinterpret_cast<int64_t*>(mg.gmx + gcols);
+    if ((rc = launch_bperm_loco_init(ctx, gcols, mg.gmx, mg.garg))) return rc;
+  }
+  // ONE permutation set for every chromosome and trait: generated here, read by every chromosome's panels, never regenerated
+  const int32_t* perm = dperm_idx;
+  if (m > 0 && nperms > 0 && !perm) {
+    if ((rc = launch_perm_gen(ctx, (int)n, nperms, seed))) return rc;
+    ctx->perm_ready = false;                    // consumed here, not by a later launch_perm_panel
+    perm = ptr<int32_t>(ctx->perm);
+  }
+  std::vector<Timer> tms;
+  tms.reserve((size_t)nchr);
+  bool audit = false;
+  int64_t mt_max = 0;
+  for (int64_t c : order) {
+    const int64_t s0 = chr[c], pc = chr[c + 1] - chr[c];
+    tms.emplace_back(ctx);
+    Timer& tm = tms.back();
+    Pipe P;
+    const EigPre pre = loco_eig_pre(ctx, n, c, dst_all);
+    if ((rc = prepare(ctx, opts, dY, n, 0, dG + (size_t)n * s0, pc, dCovar, ncov, dK + (size_t)c * n * n, dweights, 1, P, tm, false, false,
+                      false, batched ? &pre : nullptr))) return rc;
+    P.m = m; P.ldy = round_up(m > 0 ? m : 1, 128);
+    if ((rc = ensure(ctx, ctx->Yt, sizeof(double) * (size_t)P.npad * P.ldy))) return rc;
+    P.Yt = ptr<double>(ctx->Yt);
+    // (launch_rotate_single, as bulk_perms_impl: the rotation scan gives its one trait, which the bit identity rests on)
+    if ((rc = launch_rotate_single(ctx, ptr<double>(ctx->Rp), P.ldr, P.n, P.npad, dY, m, P.Yt, P.ldy))) return rc;
+    const NullModel nm = null_model(P, opts);
+    const size_t cm = (size_t)c * m;
+    const BpermOut oc{o.g.h2 + cm, o.g.sigma2 + cm, o.chr_lod_max ? o.chr_lod_max + cm : nullptr,
+                      o.chr_lod_argmax ? o.chr_lod_argmax + cm : nullptr, o.chr_max_perms ? o.chr_max_perms + cm * nperms : nullptr,
+                      o.chr_thr ? o.chr_thr + cm * nprobs : nullptr, o.chr_pval ? o.chr_pval + cm : nullptr};
+    if (m > 0 && (rc = launch_brent(ctx, nm, P.Yt, P.ldy, m, P.Z0, P.lam, oc.h2, oc.sigma2, nullptr, P.stat))) return rc;
+    tm.mark();
+    // chunks sized by the first (largest) chromosome for all of them: no workspace grows after it
+    if (!mt_max) mt_max = bperm_chunk_traits(ctx, P.npad, P.ldx, n, pc, nperms);
+    if ((rc = bperm_chunks(ctx, P, nm, m, pc, perm, nperms, mt_max, pr, nprobs, oc, s0, &mg))) return rc;
+    tm.mark();
+    if ((rc = end_call(ctx, P, nullptr, nullptr))) return rc;
+    audit = audit || ctx->audit_ran;
+    if ((rc = loco_chr_done(ctx, P, c, dst_all))) return rc;
+  }
+  if ((rc = loco_last_stat(ctx, batched, order, dst_all))) return rc;
+  for (int64_t j0 = 0; j0 < m; j0 += 65535)     // the genome-wide tables
+    if ((rc = launch_bperm_summary(ctx, mg.gmx + (size_t)j0 * np1, mg.garg + (size_t)j0 * np1, std::min<int64_t>(65535, m - j0), nperms, pr,
+                                   (int)nprobs, j0, o.g.lod_max, o.g.lod_argmax, o.g.max_perms, o.g.thr, o.g.pval))) return rc;
+  return loco_status(ctx, dst_all, nchr, audit, t0, tb, tms, status);
+}
+
+int blmm_bulkscan_loco_perms_dev(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG, int64_t p,
+                                 const int64_t* chr_start, int64_t nchr, int64_t kinship_digits, const double* dCovar, int64_t ncov,
+                                 const double* dweights, int64_t nperms, uint64_t seed, const int32_t* dperm_idx, const double* probs,
+                                 int64_t nprobs, const double* dK_loco, double* dh2_out, double* dsigma2_out, double* dlod_max_out,
+                                 int64_t* dlod_argmax_out, double* dmax_perms_out, double* dthr_out, double* dpval_out,
+                                 double* dchr_lod_max_out, int64_t* dchr_lod_argmax_out, double* dchr_max_perms_out, double* dchr_thr_out,
+                                 double* dchr_pval_out, blmm_status* status) {
+  if (!ctx) return BLMM_ERR_INVALID;
+  if (ncov == 0) dCovar = nullptr;
+  const LocoPermOut o{{dh2_out, dsigma2_out, dlod_max_out, dlod_argmax_out, dmax_perms_out, dthr_out, dpval_out},
+                      dchr_lod_max_out, dchr_lod_argmax_out, dchr_max_perms_out, dchr_thr_out, dchr_pval_out};
+  return loco_perms_impl(ctx, opts, dY, n, m, dG, p, chr_start, nchr, kinship_digits, dCovar, dCovar ? ncov : 0, dweights, dK_loco, nperms,
+                         seed, dperm_idx, probs, nprobs, o, status);
+}
+
+int blmm_bulkscan_loco_perms(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, int64_t n, int64_t m, const double* G, int64_t p,
+                             const int64_t* chr_start, int64_t nchr, int64_t kinship_digits, const double* Covar, int64_t ncov,
+                             const double* weights, int64_t nperms, uint64_t seed, const int32_t* perm_idx, const double* probs,
+                             int64_t nprobs, double* h2_out, double* sigma2_out, double* lod_max_out, int64_t* lod_argmax_out,
+                             double* max_perms_out, double* thr_out, double* pval_out, double* chr_lod_max_out,
+                             int64_t* chr_lod_argmax_out, double* chr_max_perms_out, double* chr_thr_out, double* chr_pval_out,
+                             blmm_status* status) {
+  if (!ctx) return BLMM_ERR_INVALID;
+  const LocoPermOut ho{{h2_out, sigma2_out, lod_max_out, lod_argmax_out, max_perms_out, thr_out, pval_out},
+                       chr_lod_max_out, chr_lod_argmax_out, chr_max_perms_out, chr_thr_out, chr_pval_out};
+  int rc = loco_perms_check(ctx, opts, n, m, p, chr_start, nchr, kinship_digits, Covar, ncov, nperms, probs, nprobs, Y && G, ho);
+  if (rc) return rc;
+  // caller-supplied permutations are indices into the trait's n entries: checked here, before a kernel reads through them
+  if (perm_idx && nperms > 0)
+    for (int64_t e = 0; e < n * nperms; ++e)
+      if (perm_idx[e] < 0 || perm_idx[e] >= n) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_loco_perms: perm_idx entries must lie in 0 .. n - 1");
+  HostCall hc(ctx);
+  // device outputs in outL, m doubles per row: h2, sigma2 (nchr each); lod_max, lod_argmax, pval (1 each); thresholds (nprobs);
+  // chr_lod_max, chr_lod_argmax, chr_pval (nchr each); chr_thresholds (nchr nprobs); then, when asked for, max_perms (nperms) and
+  // chr_max_perms (nchr nperms)
+  const size_t mm = (size_t)m, nc = (size_t)nchr, npr = (size_t)nprobs, npm = (size_t)nperms;
+  const size_t o_thr = 2 * nc + 3, o_cmx = o_thr + npr, o_carg = o_cmx + nc, o_cpv = o_carg + nc, o_cthr = o_cpv + nc, o_mp = o_cthr + nc * npr;
+  const size_t o_cmp = o_mp + (max_perms_out ? npm : 0), rows = o_cmp + (chr_max_perms_out ? nc * npm : 0);
+  if ((rc = hc.begin()) || (rc = ensure(ctx, ctx->outL, sizeof(double) * (mm * rows + 1)))) return rc;
+  double* d = ptr<double>(ctx->outL);
+  const LocoPermOut o{{d, d + nc * mm, d + 2 * nc * mm, reinterpret_cast<int64_t*>(d + (2 * nc + 1) * mm), max_perms_out ? d + o_mp * mm : nullptr,
+                       thr_out ? d + o_thr * mm : nullptr, pval_out ? d + (2 * nc + 2) * mm : nullptr},
+                      chr_lod_max_out ? d + o_cmx * mm : nullptr, chr_lod_argmax_out ? reinterpret_cast<int64_t*>(d + o_carg * mm) : nullptr,
+                      chr_max_perms_out ? d + o_cmp * mm : nullptr, chr_thr_out ? d + o_cthr * mm : nullptr,
+                      chr_pval_out ? d + o_cpv * mm : nullptr};
+  HostCall::In in;
+  const int32_t* dperm;
+  if ((rc = hc.inputs(Y, n, m, G, p, nullptr, Covar, ncov, weights, false, &in)) || (rc = up_perm_idx(hc, perm_idx, n, nperms, &dperm)) ||
+      (rc = loco_perms_impl(ctx, opts, in.Y, n, m, in.G, p, chr_start, nchr, kinship_digits, in.Cov, in.ncov, in.W, nullptr, nperms, seed,
+                            dperm, probs, nprobs, o, status))) return rc;
+  if ((rc = hc.down(h2_out, o.g.h2, sizeof(double) * nc * mm)) || (rc = hc.down(sigma2_out, o.g.sigma2, sizeof(double) * nc * mm)) ||
+      (rc = hc.down(lod_max_out, o.g.lod_max, sizeof(double) * mm)) || (rc = hc.down(lod_argmax_out, o.g.lod_argmax, sizeof(int64_t) * mm)) ||
+      (rc = hc.down(pval_out, o.g.pval, sizeof(double) * mm)) || (rc = hc.down(thr_out, o.g.thr, sizeof(double) * mm * npr)) ||
+      (rc = hc.down(chr_lod_max_out, o.chr_lod_max, sizeof(double) * nc * mm)) ||
+      (rc = hc.down(chr_lod_argmax_out, o.chr_lod_argmax, sizeof(int64_t) * nc * mm)) ||
+      (rc = hc.down(chr_pval_out, o.chr_pval, sizeof(double) * nc * mm)) || (rc = hc.down(chr_thr_out, o.chr_thr, sizeof(double) * nc * mm * npr)))
+    return rc;
+  if (max_perms_out && (rc = copy_to_host(ctx, max_perms_out, o.g.max_perms, sizeof(double) * mm * npm))) return rc;
+  if (chr_max_perms_out && (rc = copy_to_host(ctx, chr_max_perms_out, o.chr_max_perms, sizeof(double) * nc * mm * npm))) return rc;
   return (rc = hc.finish()) ? rc : check_sticky(ctx);
 }
 

@@ -109,7 +109,8 @@ struct blmm_ctx {
   blmm::DevBuf Ks, V, lam, U, Zs, Z0, Rp, Yt, Xt, panels, iyy, h2, h2idx, sig2, ell, isx, stat, gridd, misc, EllTab,
       inY, inG, inK, inCov, inW, outL, outH2, tmpA, tmpB, tmpC, perm, r0, altbuf, logtab, lraw, wbQ, wbW, wbRk, lrT, lrC, lrL, lrFlag, lrPart, lrPerm, lrDen0, eigW, xf32, pf32, brSt, brList, illList, qrSlab, lodtab, dynFac, pvtab, outP, redbuf, redtrip, altC, rf32, btG, redflag, bperm,
       locoK, locoPart, locoChr, locoStat, locoKs, locoV, locoLraw,   // blmm_kinship_loco / blmm_bulkscan_loco (kernels_loco.hip)
-      locoCmx, locoCarg;   // blmm_bulkscan_loco_reduced: the per-chromosome maxima / arg-maxima when the caller's tables are not on the device
+      locoCmx, locoCarg,   // blmm_bulkscan_loco_reduced: the per-chromosome maxima / arg-maxima when the caller's tables are not on the device
+      locoPerm;            // blmm_bulkscan_loco_perms: the genome-wide (nperms + 1) x m column maxima and their global markers
   // event sets: one per timed call since the last blmm_read_timings (grown on demand, reused afterwards)
   struct EvSet { hipEvent_t e[8]; int n; };
   std::vector<EvSet> evsets;
@@ -475,9 +476,14 @@ int launch_bperm_panels(blmm_ctx* ctx, const NullModel& nm, const double* Yt, in
 // quantile levels of the thresholds, passed by value (at most 64, as blmm_get_thresholds)
 struct BpermProbs { double v[64]; };
 // per trait of the chunk: peak and marker, the permutation maxima (max_perms: nperms x m, ld = nperms), thresholds (nprobs x m,
-// ld = nprobs) and the empirical p-value (max_perms / thr / pval may be null)
+// ld = nprobs) and the empirical p-value (lod_max / lod_argmax / max_perms / thr / pval may be null); row0 is added to the markers
 int launch_bperm_summary(blmm_ctx* ctx, const double* mx, const int64_t* arg, int64_t mt, int64_t nperms, const BpermProbs& probs,
-                         int nprobs, int64_t j0, double* lod_max, int64_t* lod_argmax, double* max_perms, double* thr, double* pval);
+                         int nprobs, int64_t j0, double* lod_max, int64_t* lod_argmax, double* max_perms, double* thr, double* pval,
+                         int64_t row0 = 0);
+// blmm_bulkscan_loco_perms: a chunk's ncols column maxima (markers + row0) into the genome-wide buffer at the chunk's columns
+// (gmx / garg already offset), k_red_final's rule; and the buffer's -inf / -1 start
+int launch_bperm_loco_merge(blmm_ctx* ctx, const double* mx, const int64_t* arg, int64_t ncols, int64_t row0, double* gmx, int64_t* garg);
+int launch_bperm_loco_init(blmm_ctx* ctx, int64_t n, double* gmx, int64_t* garg);
 constexpr int BPERM_MAX_NPERMS = 16384;   // k_bperm_summary sorts a trait's maxima in LDS (128 KB)
 
 }  // namespace blmm

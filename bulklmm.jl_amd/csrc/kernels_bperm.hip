@@ -9,6 +9,13 @@
 // chunk with bin[column] = trait (marker norms of the trait's h2: launch_isx with the chunk's h2 as its "grid") and reduces in
 // its epilogue (RedArgs + k_red_final), and k_bperm_summary turns every trait's nperms + 1 column maxima into the peak, the
 // thresholds (k_quantiles' rule on k_bitonic_lds' order) and the empirical p-value.
+//
+// blmm_bulkscan_loco_perms runs the same chunks once per chromosome (its column block of G, its LOCO kinship's eigenbasis and h2),
+// with one permutation set for every chromosome.  k_bperm_summary writes each chromosome's tables into its slot (marker indices
+// shifted to global ones by row0), and k_bperm_loco_merge folds the chunk's column maxima into a genome-wide (nperms + 1) x m buffer,
+// which one more k_bperm_summary turns into the genome-wide tables.  Convention: the genome-wide maximum of permutation b pairs
+// the chromosomes' copies by b -- each chromosome permutes its own rotated, reweighted null residuals, as scan_perms_lite does under
+// that chromosome's kinship; it is not one permutation of the individuals carried across chromosomes.
 #include "blmm_internal.h"
 #include <cmath>
 #include <cstring>
@@ -309,14 +316,15 @@ int launch_bperm_panels(blmm_ctx* ctx, const NullModel& nm, const double* Yt, in
 // mx / arg: the chunk's column maxima and their markers (k_red_final).  The nperms permutation maxima are sorted in LDS by
 // k_bitonic_lds' network (same key order -- NaN last -- and +inf padding to npow), so the quantiles (k_quantiles' rule: Julia's
 // default type 7) equal blmm_get_thresholds on the trait's L_perms bit for bit.  pval = (1 + #{b : max_b >= peak}) / (nperms + 1),
-// a -inf maximum (no finite-comparable LOD) never counted.
+// a -inf maximum (no finite-comparable LOD) never counted.  row0 is added to every marker written (-1 stays -1); lod_max /
+// lod_argmax may be NULL.
 __device__ __forceinline__ bool bperm_key_less(double a, double b) {
   if (a != a) return false;
   if (b != b) return true;
   return a < b;
 }
 __global__ void __launch_bounds__(256) k_bperm_summary(const double* __restrict__ mx, const int64_t* __restrict__ arg, int64_t nperms,
-                                                       int npow, BpermProbs probs, int nprobs, int64_t j0,
+                                                       int npow, BpermProbs probs, int nprobs, int64_t j0, int64_t row0,
                                                        double* __restrict__ lod_max, int64_t* __restrict__ lod_argmax,
                                                        double* __restrict__ max_perms, double* __restrict__ thr,
                                                        double* __restrict__ pval) {
@@ -325,7 +333,11 @@ __global__ void __launch_bounds__(256) k_bperm_summary(const double* __restrict_
   const int64_t jj = blockIdx.x, j = j0 + jj, np1 = nperms + 1;
   const double* c = mx + jj * np1;
   const double peak = c[0];
-  if (threadIdx.x == 0) { s_cnt = 0ull; lod_max[j] = peak; lod_argmax[j] = arg[jj * np1]; }
+  if (threadIdx.x == 0) {
+    s_cnt = 0ull;
+    if (lod_max) lod_max[j] = peak;
+    if (lod_argmax) { const int64_t a = arg[jj * np1]; lod_argmax[j] = a >= 0 ? a + row0 : a; }
+  }
   __syncthreads();
   unsigned long long my = 0;
   for (int e = threadIdx.x; e < npow; e += blockDim.x) {
@@ -369,14 +381,52 @@ __global__ void __launch_bounds__(256) k_bperm_summary(const double* __restrict_
 }
 
 int launch_bperm_summary(blmm_ctx* ctx, const double* mx, const int64_t* arg, int64_t mt, int64_t nperms, const BpermProbs& probs,
-                         int nprobs, int64_t j0, double* lod_max, int64_t* lod_argmax, double* max_perms, double* thr, double* pval) {
+                         int nprobs, int64_t j0, double* lod_max, int64_t* lod_argmax, double* max_perms, double* thr, double* pval,
+                         int64_t row0) {
   if (mt <= 0) return BLMM_OK;
   int npow = 1;
   while (npow < nperms) npow <<= 1;
   const size_t lds = sizeof(double) * (size_t)npow;
   if (lds > 48 * 1024) BLMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bperm_summary), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(k_bperm_summary, dim3((unsigned)mt), dim3(256), lds, ctx->stream, mx, arg, nperms, npow, probs, nprobs, j0,
-                     lod_max, lod_argmax, max_perms, thr, pval);
+                     row0, lod_max, lod_argmax, max_perms, thr, pval);
+  KCHECK();
+  return BLMM_OK;
+}
+
+// ---- blmm_bulkscan_loco_perms: a chunk's column maxima into the genome-wide buffer ------------------------------------------
+// One thread per panel column: column col of the chunk (trait j0 + col / (nperms + 1)) is column j0 (nperms + 1) + col of gmx /
+// garg.  k_red_final's rule: the larger value wins, an equal one only with a lower valid marker, so that NaN (never in mx: k_red_final
+// does not keep one) is never the maximum and a tie goes to the lowest GLOBAL marker whatever order the chromosomes run in.  The
+// chunk's markers are its chromosome's: row0 (its first marker) makes them global.  gmx / garg start at -inf / -1.
+__global__ void __launch_bounds__(256) k_bperm_loco_merge(const double* __restrict__ mx, const int64_t* __restrict__ arg, int64_t ncols,
+                                                          int64_t row0, double* __restrict__ gmx, int64_t* __restrict__ garg) {
+  const int64_t col = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (col >= ncols) return;
+  const double v = mx[col];
+  const int64_t a = arg[col];
+  const int64_t i = a >= 0 ? a + row0 : -1;
+  const double best = gmx[col];
+  const int64_t bi = garg[col];
+  if (v > best || (v == best && i >= 0 && (bi < 0 || i < bi))) { gmx[col] = v; garg[col] = i; }
+}
+
+int launch_bperm_loco_merge(blmm_ctx* ctx, const double* mx, const int64_t* arg, int64_t ncols, int64_t row0, double* gmx, int64_t* garg) {
+  if (ncols <= 0) return BLMM_OK;
+  hipLaunchKernelGGL(k_bperm_loco_merge, dim3((unsigned)((ncols + 255) / 256)), dim3(256), 0, ctx->stream, mx, arg, ncols, row0, gmx, garg);
+  KCHECK();
+  return BLMM_OK;
+}
+
+// gmx / garg = -inf / -1 (the merge's identity), n entries
+__global__ void __launch_bounds__(256) k_bperm_loco_init(int64_t n, double* __restrict__ gmx, int64_t* __restrict__ garg) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e < n) { gmx[e] = -INFINITY; garg[e] = -1; }
+}
+
+int launch_bperm_loco_init(blmm_ctx* ctx, int64_t n, double* gmx, int64_t* garg) {
+  if (n <= 0) return BLMM_OK;
+  hipLaunchKernelGGL(k_bperm_loco_init, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n, gmx, garg);
   KCHECK();
   return BLMM_OK;
 }

@@ -11,7 +11,7 @@
 # every `ccall`'s symbol, return type and argument tuple (arity and types) against the prototype in include/bulklmm_hip.h.
 module BulkLMMHIP
 
-export calcKinship_loco, bulkscan_loco, bulkscan_loco_reduced, bulkscan_perms, bulkscan_reduced, bulkscan_reduced_async!, synchronize, DeviceLOD, lod_columns, set_tuning, calcKinship, bulkscan, bulkscan_null, bulkscan_null_grid, bulkscan_alt_grid, bulkscan_alt_exact, scan, bulkscan_multi, lod2log10p, get_thresholds,
+export calcKinship_loco, bulkscan_loco, bulkscan_loco_reduced, bulkscan_loco_perms, bulkscan_perms, bulkscan_reduced, bulkscan_reduced_async!, synchronize, DeviceLOD, lod_columns, set_tuning, calcKinship, bulkscan, bulkscan_null, bulkscan_null_grid, bulkscan_alt_grid, bulkscan_alt_exact, scan, bulkscan_multi, lod2log10p, get_thresholds,
        lod_threshold, lod_colmax, pinned_matrix, host_register, host_unregister
 
 const libblmm = get(ENV, "BULKLMM_HIP_LIB", joinpath(@__DIR__, "..", "csrc", "libbulklmm_hip.so"))
@@ -771,6 +771,49 @@ function bulkscan_loco_reduced(Y::Array{Float64, 2}, G::Array{Float64, 2}, chrom
         end
         cap = cnt[1]
     end
+end
+
+# The LOCO permutation test (blmm_bulkscan_loco_perms): bulkscan_perms under every chromosome's LOCO kinship with ONE permutation set
+# (rndseed), plus the genome-wide tables -- permutation b's maximum over the chromosomes' copies paired by b.  Rows of the chr_*
+# tables are chromosomes in run order; markers are 1-based and global (0 = no comparable LOD).
+function bulkscan_loco_perms(Y::Array{Float64, 2}, G::Array{Float64, 2}, chrom::AbstractVector;
+                             Covar::Union{Nothing, Array{Float64, 2}} = nothing, nperms::Int64 = 1024, rndseed::Int64 = 0,
+                             signif_level::Array{Float64, 1} = [0.10, 0.05], kinship_digits::Integer = -1,
+                             weights::Union{Missing, Array{Float64, 1}} = missing, prior_variance::Float64 = 0.0,
+                             prior_sample_size::Float64 = 0.0, addIntercept::Bool = true, reml::Bool = false,
+                             optim_interval::Int64 = 1, decomp_scheme::String = "eigen", chr_max_perms::Bool = false)
+    (n, m) = size(Y); p = size(G, 2)
+    size(G, 1) != n && error("Dimension mismatch.")
+    runs, cs = chromosome_runs(chrom, p)
+    nchr = length(cs) - 1
+    check_n(n)
+    (Covar !== nothing && size(Covar, 1) != n) && error("Dimension mismatch.")
+    (weights !== missing && length(weights) != n) && error("Dimension mismatch.")
+    nperms < 0 && error("The required number of permutations must be a positive integer.")
+    o = BlmmOpts(NULL_EXACT, reml, Covar === nothing ? true : addIntercept, decomp(decomp_scheme), optim_interval, 0,
+                 prior_variance, prior_sample_size)
+    probs = 1.0 .- signif_level
+    npr = length(probs)
+    h2 = Array{Float64, 2}(undef, m, nchr); s2 = similar(h2); cmx = similar(h2); cpv = similar(h2)   # column c: chromosome c
+    carg = Array{Int64, 2}(undef, m, nchr)
+    cthr = Array{Float64, 3}(undef, npr, m, nchr)
+    cmp = chr_max_perms ? Array{Float64, 3}(undef, max(nperms, 1), m, nchr) : nothing
+    mx = Vector{Float64}(undef, m); pv = similar(mx); arg = Vector{Int64}(undef, m)
+    mp = Array{Float64, 2}(undef, max(nperms, 1), m); thr = Array{Float64, 2}(undef, npr, m)
+    st = BlmmStatus()
+    ncov = Covar === nothing ? 0 : size(Covar, 2)
+    GC.@preserve Y G cs Covar weights probs h2 s2 mx arg mp thr pv cmx carg cmp cthr cpv check(ccall((:blmm_bulkscan_loco_perms, libblmm), Cint,
+        (Ptr{Cvoid}, Ref{BlmmOpts}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Int64}, Int64, Int64, Ptr{Float64}, Int64,
+         Ptr{Float64}, Int64, UInt64, Ptr{Int32}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{BlmmStatus}),
+        context(), o, Y, n, m, G, p, cs, nchr, kinship_digits, ptr_or_null(Covar), ncov, ptr_or_null(weights), nperms,
+        UInt64(rndseed), C_NULL, probs, npr, h2, s2, mx, arg, mp, thr, pv, cmx, carg, ptr_or_null(cmp), cthr, cpv, st))
+    raise_status(st)
+    res = (h2_null = permutedims(h2), sigma2_e = permutedims(s2), lod_max = mx, lod_argmax = arg .+ 1, max_perms = mp[1:nperms, :],
+           thresholds = thr, pvals_perm = pv, chr_lod_max = permutedims(cmx), chr_lod_argmax = permutedims(carg) .+ 1,
+           chr_thresholds = permutedims(cthr, (3, 1, 2)), chr_pvals_perm = permutedims(cpv), chromosomes = runs, chr_start = cs)
+    chr_max_perms && (res = merge(res, (chr_max_perms = permutedims(cmp, (3, 1, 2))[:, 1:nperms, :],)))
+    return res
 end
 
 end # module

@@ -478,6 +478,51 @@ int blmm_bulkscan_loco_reduced_dev(blmm_ctx* ctx, const blmm_opts* opts, const d
                                    const double* dweights, const double* h2_grid, int64_t ngrid, const double* dK_loco, const blmm_reduced* out,
                                    double* dchr_max_out, int64_t* dchr_argmax_out, double* dh2_out, blmm_status* status);
 
+/* ---- the LOCO permutation test: blmm_bulkscan_perms under every chromosome's LOCO kinship, and genome-wide tables ------------
+ * With K_c = blmm_kinship_loco(G, chr_start, kinship_digits)[c] and ref_c = blmm_bulkscan_perms(Y, G[:, chromosome c], K_c; same opts /
+ * Covar / weights / nperms / seed or perm_idx / probs), bit for bit:
+ *   h2_out, sigma2_out    nchr blocks of m (block c at + c m): ref_c's h2 / sigma2
+ *   chr_lod_max_out       nchr x m as h2_out: ref_c's lod_max; chr_lod_argmax_out: ref_c's lod_argmax + chr_start[c] (a GLOBAL
+ *                         0-based marker; -1 stays -1)
+ *   chr_max_perms_out     nchr blocks of nperms x m (block c at + c nperms m, ld = nperms): ref_c's max_perms (5.7 GB at the BXD shape
+ *                         with 1000 permutations: NULL unless needed)
+ *   chr_thr_out           nchr blocks of nprobs x m (at + c nprobs m, ld = nprobs): ref_c's thresholds; chr_pval_out nchr x m: ref_c's
+ *                         p-values
+ * and genome-wide, from those values exactly:
+ *   max_perms_out         nperms x m (ld = nperms): max over c of chr_max_perms[c]
+ *   lod_max_out           max over c of chr_lod_max; lod_argmax_out its global marker (the lowest on ties, whatever order the
+ *                         chromosomes run in; NaN never the maximum; -inf / -1 for a trait without a comparable LOD)
+ *   thr_out               nprobs x m: blmm_get_thresholds' rule (Julia's type 7) on max_perms[:, j]
+ *   pval_out              (1 + #{b : max_perms[b, j] >= lod_max[j]}) / (nperms + 1), a -inf maximum never counted
+ *   nperms = 0: thresholds and p-values are NaN.
+ * Convention: ONE permutation set (perm_idx, or the generator seeded once by `seed`) serves every chromosome and trait.  Each
+ * chromosome permutes its own rotated, reweighted null residuals, as scan_perms_lite (src/scan.jl:485-557) does under K_c, and the
+ * genome-wide maximum of permutation b pairs the chromosomes' copies by b -- what a loop of blmm_bulkscan_perms over the chromosomes
+ * gives, not one permutation of the individuals carried across chromosomes.
+ * Y, G, Covar and weights go up once, the kinships come from one pass over G, the eigen phase is blmm_bulkscan_loco's (batched
+ * for n <= 124), and the p x m x nperms LOD tensor is never written: each chromosome's trait chunks (blmm_bulkscan_perms' kernels)
+ * reduce to column maxima that fold into a (nperms + 1) x m device buffer, summarised once after the last chromosome.
+ * h2_out, sigma2_out, lod_max_out and lod_argmax_out are required; every other output may be NULL.  status: summed over the
+ * chromosomes, as blmm_bulkscan_loco.  Refused before anything is uploaded: what blmm_bulkscan_loco refuses (chromosome offsets,
+ * n > 2048) and what blmm_bulkscan_perms refuses (nperms < 0: BLMM_ERR_NPERMS; more than 16384 permutations or more than 8 null
+ * covariates: BLMM_ERR_UNSUPPORTED; 0 .. 64 levels; perm_idx entries outside 0 .. n - 1 in the host form).
+ * The _dev form: device Y / G / Covar / weights / perm_idx and outputs (probs and chr_start still host), dK_loco as
+ * blmm_bulkscan_loco_dev (NULL: computed on the device).  It enqueues on the context's stream and waits for it only for a status. */
+int blmm_bulkscan_loco_perms(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, int64_t n, int64_t m, const double* G, int64_t p,
+                             const int64_t* chr_start, int64_t nchr, int64_t kinship_digits, const double* Covar, int64_t ncov,
+                             const double* weights, int64_t nperms, uint64_t seed, const int32_t* perm_idx, const double* probs,
+                             int64_t nprobs, double* h2_out, double* sigma2_out, double* lod_max_out, int64_t* lod_argmax_out,
+                             double* max_perms_out, double* thr_out, double* pval_out, double* chr_lod_max_out,
+                             int64_t* chr_lod_argmax_out, double* chr_max_perms_out, double* chr_thr_out, double* chr_pval_out,
+                             blmm_status* status);
+int blmm_bulkscan_loco_perms_dev(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG, int64_t p,
+                                 const int64_t* chr_start, int64_t nchr, int64_t kinship_digits, const double* dCovar, int64_t ncov,
+                                 const double* dweights, int64_t nperms, uint64_t seed, const int32_t* dperm_idx, const double* probs,
+                                 int64_t nprobs, const double* dK_loco, double* dh2_out, double* dsigma2_out, double* dlod_max_out,
+                                 int64_t* dlod_argmax_out, double* dmax_perms_out, double* dthr_out, double* dpval_out,
+                                 double* dchr_lod_max_out, int64_t* dchr_lod_argmax_out, double* dchr_max_perms_out, double* dchr_thr_out,
+                                 double* dchr_pval_out, blmm_status* status);
+
 /* ---- scan(y, G, [Z], K; assumption = "alt") -> scan_alt (src/scan.jl:397-453): the variance components are re-estimated for
  * every marker (fitlmm on [Z g_i], src/lmm.jl:56-86, one Brent search per marker on the device).
  * scalars_out = [sigma2_e, h2_null]; lod_out p; h2_each_out p (`h2_each_marker`).  opts->compat_flags:
