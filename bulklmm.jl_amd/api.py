@@ -1563,3 +1563,122 @@ def bulkscan_loco_perms_dev(ctx: Context, Y, G, chr_start, h2_out, sigma2_out, l
                                                    dp(chr_lod_argmax_out), dp(chr_max_perms_out), dp(chr_thr_out), dp(chr_pval_out),
                                                    C.byref(st) if status else None))
     return st
+
+
+# ---- the k-degree-of-freedom scan (blmm_bulkscan_multidf) ----------------------------------------------------------------------
+_MULTIDF_KMAX = {"null-grid": L.BLMM_MULTIDF_MAX_K_GRID, "null-exact": L.BLMM_MULTIDF_MAX_K_EXACT}
+
+
+def _multidf_checks(method: str, n: int, p: int, k, ncov: int, addIntercept: bool):
+    """The library's refusals of blmm_bulkscan_multidf that need no data (blmm_api.hip: multidf_check), before any context."""
+    if method not in _METHODS:
+        raise BulkLMMError("Unknown method; choose null-exact, null-grid or alt-grid.", -5)
+    k = int(k)
+    if k < 1 or p % k != 0:
+        raise BulkLMMError("bulkscan_multidf: the number of columns of G must be a multiple of k >= 1", -2)
+    if method == "alt-grid":
+        raise BulkLMMError("bulkscan_multidf: alt-grid is not supported; use null-grid or null-exact", -10)
+    if k > _MULTIDF_KMAX[method]:
+        raise BulkLMMError("bulkscan_multidf: %s takes 1 <= k <= %d" % (method, _MULTIDF_KMAX[method]), -10)
+    if (ncov + (1 if addIntercept else 0) if ncov > 0 else 1) > L.BLMM_MULTIDF_MAX_COVARIATES:
+        raise BulkLMMError("bulkscan_multidf: more than 8 null covariates (incl. intercept) are not supported", -10)
+    _check_n(n)
+    return k
+
+
+def bulkscan_multidf(Y, G, K, k: int, Covar=None, *, method: str = "null-grid", h2_grid=None, addIntercept: bool = True, weights=None,
+                     prior_variance: float = 1.0, prior_sample_size: float = 0.0, reml: bool = False, optim_interval: int = 1,
+                     decomp_scheme: str = "eigen", output_pvals: bool = False, chisq_df: Optional[int] = None,
+                     keep_on_device: bool = False, ctx: Optional[Context] = None, return_status: bool = False) -> dict:
+    """k-degree-of-freedom bulkscan (blmm_bulkscan_multidf; the reference's README lists it as future work): G is n x (P k), locus l
+    is the columns l k .. l k + k - 1 (genotype or founder probabilities, additive + dominance codings) and every (locus, trait)
+    pair gets one test of all its columns at once, L[l, j] = -(n/2) log10(1 - R^2) with R^2 the share of the trait's null residual
+    that the locus explains.  Columns of a locus that add nothing beyond the covariates and the locus's earlier columns (|r|^2 <=
+    1e-8 |x|^2: complements, duplicates, absent genotypes) are dropped.  Every other argument is bulkscan's; h2_null_list is
+    bulkscan's, bit for bit.  `chisq_df` (output_pvals) defaults to k -- callers who pass complement columns choose k - 1.
+    Returns {"L": P x m ndarray (DeviceLOD when keep_on_device), "h2_null_list": m [, "log10Pvals_mat", "Chisq_df"] [, "status"]}."""
+    if h2_grid is None:
+        h2_grid = [i / 10.0 for i in range(10)]  # collect(0.0:0.1:0.9)
+    Y = _F(Y)
+    G = _F(G)
+    K = _F(K)
+    n, m = Y.shape
+    p = G.shape[1]
+    if G.shape[0] != n or K.shape[0] != n or K.shape[1] != n:
+        raise BulkLMMError("Dimension mismatch.", -2)
+    cov, ncov = None, 0
+    if Covar is not None:
+        cov = _F(Covar)
+        if cov.shape[0] != n:
+            raise BulkLMMError("Dimension mismatch.", -2)
+        ncov = cov.shape[1]
+    else:
+        addIntercept = True
+    w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).ravel())
+    if w is not None and w.shape[0] != n:
+        raise BulkLMMError("Dimension mismatch.", -2)
+    k = _multidf_checks(method, n, p, k, ncov, addIntercept)
+    df = k if chisq_df is None else int(chisq_df)
+    if output_pvals and not 1 <= df <= 1000000:
+        raise BulkLMMError("chisq_df must lie in 1 .. 10^6", -1)
+    grid = None
+    ngrid = 0
+    if method != "null-exact":
+        grid = np.ascontiguousarray(np.asarray(h2_grid, dtype=np.float64).ravel())
+        ngrid = grid.shape[0]
+    o = _opts(_METHODS[method], reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
+    ctx = ctx or default_context()  # after the argument checks: those must not need a GPU
+    P = p // k
+    Lout = None if keep_on_device else np.empty((P, m), dtype=np.float64, order="F")
+    h2 = np.empty(m, dtype=np.float64)
+    st = L.blmm_status()
+    if output_pvals:
+        ctx.check(ctx.lib.blmm_set_log10p_output(ctx.h, None, 0, df))
+    try:
+        ctx.check(ctx.lib.blmm_bulkscan_multidf(ctx.h, C.byref(o), _p(Y), n, m, _p(G), p, k, _p(cov), ncov, _p(K), _p(w), _p(grid), ngrid,
+                                                _p(Lout), _p(h2), C.byref(st)))
+    finally:
+        if output_pvals:
+            ctx.lib.blmm_set_log10p_output(ctx.h, None, 0, 0)
+    _raise_status(st)
+    out = {"L": DeviceLOD(ctx, P, m) if keep_on_device else Lout, "h2_null_list": h2}
+    if output_pvals:
+        out["log10Pvals_mat"] = _last_log10p(ctx, (P, m), df)
+        out["Chisq_df"] = df
+    if return_status:
+        out["status"] = st
+    return out
+
+
+def bulkscan_multidf_dev(ctx: Context, Y, G, K, k: int, L_out, h2_out, *, method: str = "null-grid", h2_grid=None, Covar=None,
+                         weights=None, addIntercept: bool = True, prior_variance: float = 1.0, prior_sample_size: float = 0.0,
+                         reml: bool = False, optim_interval: int = 1, decomp_scheme: str = "eigen", status: bool = False,
+                         log10p_out=None, chisq_df: Optional[int] = None):
+    """blmm_bulkscan_multidf_dev on torch tensors in bulkscan_dev's layout: Y (m, n), G (p, n) with p = P k, K (n, n), L_out (m, P)
+    (= P x m column-major; rows may be padded), h2_out (m).  `log10p_out` (L_out's layout): -log10 p with chisq_df (default k) from
+    the same call (blmm_set_log10p_output).  Enqueues on the context's stream; synchronises only for `status`."""
+    m, n = Y.shape
+    p = G.shape[0]
+    ncov = 0 if Covar is None else Covar.shape[0]
+    if Covar is None:
+        addIntercept = True
+    k = _multidf_checks(method, n, p, k, ncov, addIntercept)
+    P = p // k
+    grid = None
+    ngrid = 0
+    if method != "null-exact":
+        grid = np.ascontiguousarray(np.asarray(h2_grid if h2_grid is not None else [i / 10.0 for i in range(10)], dtype=np.float64))
+        ngrid = grid.shape[0]
+    o = _opts(_METHODS[method], reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
+    st = L.blmm_status() if status else None
+    if log10p_out is not None:
+        ctx.check(ctx.lib.blmm_set_log10p_output(ctx.h, log10p_out.data_ptr(), _ld(log10p_out, P), k if chisq_df is None else int(chisq_df)))
+    try:
+        ctx.check(ctx.lib.blmm_bulkscan_multidf_dev(ctx.h, C.byref(o), Y.data_ptr(), n, m, G.data_ptr(), p, k,
+                                                    None if Covar is None else Covar.data_ptr(), ncov, K.data_ptr(),
+                                                    None if weights is None else weights.data_ptr(), _p(grid), ngrid,
+                                                    L_out.data_ptr(), _ld(L_out, P), h2_out.data_ptr(), C.byref(st) if status else None))
+    finally:
+        if log10p_out is not None:
+            ctx.lib.blmm_set_log10p_output(ctx.h, None, 0, 0)
+    return st

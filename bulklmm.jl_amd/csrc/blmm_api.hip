@@ -857,7 +857,7 @@ void blmm_destroy(blmm_ctx* ctx) {
                     &ctx->tmpA, &ctx->tmpB, &ctx->tmpC, &ctx->perm, &ctx->r0, &ctx->altbuf, &ctx->logtab, &ctx->lraw,
                     &ctx->wbQ, &ctx->wbW, &ctx->wbRk, &ctx->lrT, &ctx->lrC, &ctx->lrL, &ctx->lrFlag, &ctx->lrPart, &ctx->lrPerm, &ctx->lrDen0, &ctx->eigW, &ctx->xf32, &ctx->pf32, &ctx->brSt, &ctx->brList, &ctx->illList, &ctx->qrSlab, &ctx->lodtab, &ctx->dynFac, &ctx->pvtab, &ctx->outP, &ctx->redbuf, &ctx->redtrip, &ctx->altC, &ctx->rf32, &ctx->btG, &ctx->redflag, &ctx->bperm,
                     &ctx->locoK, &ctx->locoPart, &ctx->locoChr, &ctx->locoStat, &ctx->locoKs, &ctx->locoV, &ctx->locoLraw,
-                    &ctx->locoCmx, &ctx->locoCarg, &ctx->locoPerm};
+                    &ctx->locoCmx, &ctx->locoCarg, &ctx->locoPerm, &ctx->mdfR, &ctx->mdfT};
   for (DevBuf* b : bufs) if (b->p) hipFree(b->p);
   for (auto& s : ctx->evsets) for (auto& e : s.e) (void)hipEventDestroy(e);
   if (ctx->side) { (void)hipStreamSynchronize(ctx->side); (void)hipStreamDestroy(ctx->side); }
@@ -2884,6 +2884,141 @@ int blmm_liteqtl_given_h2(blmm_ctx* ctx, const double* Y0, int64_t n, int64_t m,
   }
   if ((rc = hc.down(LOD_out, ctx->outL.p, sizeof(double) * (size_t)p * m))) return rc;
   return (rc = hc.finish()) ? rc : finish_status(ctx, status, nullptr);
+}
+
+
+// ---------------------------------------------------------------------------------------------------
+// The k-degree-of-freedom scan (include/bulklmm_hip.h: blmm_bulkscan_multidf; kernels_mdf.hip).  Every refusal that needs no device
+// comes first, in the same order in the host and the device forms.
+static int multidf_check(blmm_ctx* ctx, const blmm_opts* opts, int64_t n, int64_t m, int64_t p, int64_t k, const double* Covar,
+                         int64_t ncov) {
+  int rc = check_opts(ctx, opts);
+  if (rc) return rc;
+  if (n < 1 || m < 0 || p < 0 || ncov < 0 || p > 0x7fffffffLL || m > 0x7fffffffLL) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
+  if (k < 1 || p % k != 0) return fail(ctx, BLMM_ERR_DIM, "bulkscan_multidf: the number of columns of G must be a multiple of k >= 1");
+  if ((rc = check_method(ctx, opts))) return rc;
+  if (opts->method == BLMM_ALT_GRID) return fail(ctx, BLMM_ERR_UNSUPPORTED, "bulkscan_multidf: alt-grid is not supported; use null-grid or null-exact");
+  const int64_t kmax = opts->method == BLMM_NULL_EXACT ? BLMM_MULTIDF_MAX_K_EXACT : BLMM_MULTIDF_MAX_K_GRID;
+  if (k > kmax)
+    return fail(ctx, BLMM_ERR_UNSUPPORTED, std::string("bulkscan_multidf: ") + (opts->method == BLMM_NULL_EXACT ? "null-exact" : "null-grid") +
+                " takes 1 <= k <= " + std::to_string((long long)kmax));
+  if (null_cov(opts, Covar, ncov).c > BLMM_MULTIDF_MAX_COVARIATES)
+    return fail(ctx, BLMM_ERR_UNSUPPORTED, "bulkscan_multidf: more than 8 null covariates (incl. intercept) are not supported");
+  if (n > 2048) return fail(ctx, BLMM_ERR_UNSUPPORTED, "more than 2048 individuals: the device eigensolver (tridiagonalisation + divide and conquer) stops at n = 2048");
+  return BLMM_OK;
+}
+
+static int multidf_dev_impl(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG, int64_t p,
+                            int64_t k, const double* dCovar, int64_t ncov, const double* dK, const double* dweights,
+                            const double* h2_grid_host, int64_t ngrid, double* dL_out, int64_t ldL, double* dh2_out,
+                            blmm_status* status, const PvReq& pvreq) {
+  int rc = multidf_check(ctx, opts, n, m, p, k, dCovar, ncov);
+  if (rc) return rc;
+  const int64_t nloci = p / k;
+  if (!dY || !dG || !dK || !dL_out || !dh2_out) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_multidf: NULL buffer");
+  if (ldL < nloci) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_multidf: ldL < p / k");
+  const bool exact = opts->method == BLMM_NULL_EXACT;
+  if ((rc = enter_device(ctx))) return rc;
+  Timer tm(ctx);
+  Pipe P;
+  double* dgrid = nullptr;
+  if (!exact && (rc = grid_to_device(ctx, h2_grid_host, ngrid, &dgrid))) return rc;
+  // blmm_bulkscan's design, eigen phase and trait rotation (so the null model is its own, bit for bit); the markers are rotated
+  // below without the centring projection
+  const bool g_in_flight = ctx->up_pending || ctx->in_wait;   // (host form) G may still be on its way up: ev_in says when it is there
+  if ((rc = prepare(ctx, opts, dY, n, m, dG, p, dCovar, ncov, dK, dweights, 1, P, tm, false, false, /*skip_markers*/ true))) return rc;
+  if (g_in_flight) BLMM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_in, 0));
+  const NullModel nm = null_model(P, opts);
+  PvCall pvc(ctx, pvreq);
+  if ((rc = pvc.resolve(nloci, m))) return rc;   // always the column pass over the finished L (fused stays false)
+  if (m == 0) { tm.mark(); tm.mark(); tm.mark(); return end_call(ctx, P, status, &tm); }
+  if (nloci == 0) {
+    if (exact) {
+      if ((rc = launch_brent(ctx, nm, P.Yt, P.ldy, m, P.Z0, P.lam, dh2_out, nullptr, nullptr, P.stat))) return rc;
+    } else {
+      if ((rc = ensure(ctx, ctx->h2idx, sizeof(int) * (size_t)m))) return rc;
+      if ((rc = launch_loglik_grid(ctx, nm, P.Yt, P.ldy, m, P.Z0, P.lam, dgrid, (int)ngrid, nullptr, ptr<int>(ctx->h2idx), dh2_out, P.stat))) return rc;
+    }
+    tm.mark(); tm.mark(); tm.mark();
+    return end_call(ctx, P, status, &tm);
+  }
+  if ((rc = ensure(ctx, ctx->mdfR, sizeof(double) * (size_t)P.npad * P.ldr)) ||
+      (rc = ensure(ctx, ctx->Xt, sizeof(double) * (size_t)P.npad * P.ldx))) return rc;
+  if ((rc = launch_mdf_rawrot(ctx, ptr<double>(ctx->U), dweights, P.n, P.npad, P.ldr, ptr<double>(ctx->mdfR)))) return rc;
+  P.Xt = ptr<double>(ctx->Xt);
+  if ((rc = launch_rotate(ctx, ptr<double>(ctx->mdfR), P.ldr, P.n, P.npad, dG, p, P.Xt, P.ldx, P.ldx))) return rc;
+  MdfArgs a;
+  a.Xt = P.Xt; a.ldx = P.ldx; a.nloci = nloci; a.k = (int)k; a.n = P.n; a.m = m;
+  a.ldp = P.ldy; a.pstride = (int64_t)P.npad * P.ldy; a.c = P.c;
+  a.T = nullptr; a.bin = nullptr; a.L = dL_out; a.ldL = ldL; a.stat = P.stat;
+  const int64_t ldp = P.ldy;
+  if (exact) {
+    if ((rc = launch_brent(ctx, nm, P.Yt, P.ldy, m, P.Z0, P.lam, dh2_out, nullptr, nullptr, P.stat))) return rc;
+    tm.mark();
+    if ((rc = ensure(ctx, ctx->panels, sizeof(double) * (size_t)(2 + P.c) * P.npad * ldp))) return rc;
+    if ((rc = launch_panels(ctx, nm, P.Yt, P.ldy, m, P.Z0, P.lam, dh2_out, 1, ptr<double>(ctx->panels), ldp, P.stat))) return rc;
+    tm.mark();
+    a.P = ptr<double>(ctx->panels);
+    if ((rc = launch_mdf_scan(ctx, a, true))) return rc;
+    // conditioning guard (c >= 2): the flagged traits' columns again, orthogonalised
+    if (P.c >= 2) {
+      if ((rc = ensure(ctx, ctx->illList, sizeof(int) * (size_t)m))) return rc;
+      if ((rc = launch_illcond_flag(ctx, nm, m, P.Z0, P.lam, dh2_out, ptr<int>(ctx->illList), P.stat))) return rc;
+      if ((rc = launch_mdf_qr(ctx, nm, P.Yt, P.ldy, P.Xt, P.ldx, nloci, (int)k, P.Z0, P.lam, dh2_out, ptr<int>(ctx->illList), dL_out, ldL, P.stat))) return rc;
+    }
+    tm.mark();
+  } else {
+    if ((rc = ensure(ctx, ctx->h2idx, sizeof(int) * (size_t)m))) return rc;
+    if ((rc = launch_loglik_grid(ctx, nm, P.Yt, P.ldy, m, P.Z0, P.lam, dgrid, (int)ngrid, nullptr, ptr<int>(ctx->h2idx), dh2_out, P.stat))) return rc;
+    tm.mark();
+    if ((rc = ensure(ctx, ctx->panels, sizeof(double) * (size_t)P.npad * ldp))) return rc;
+    if ((rc = launch_panels(ctx, nm, P.Yt, P.ldy, m, P.Z0, P.lam, dh2_out, 0, ptr<double>(ctx->panels), ldp, P.stat))) return rc;
+    const int64_t np = k * (k + 1) / 2;
+    if ((rc = ensure(ctx, ctx->mdfT, sizeof(double) * (size_t)ngrid * nloci * np))) return rc;
+    if ((rc = launch_mdf_table(ctx, nm, P.Xt, P.ldx, nloci, (int)k, P.Z0, P.lam, dgrid, (int)ngrid, ptr<double>(ctx->mdfT)))) return rc;
+    tm.mark();
+    a.P = ptr<double>(ctx->panels); a.T = ptr<double>(ctx->mdfT); a.bin = ptr<int>(ctx->h2idx);
+    if ((rc = launch_mdf_scan(ctx, a, false))) return rc;
+    tm.mark();
+  }
+  if ((rc = pvc.finish(nloci, m, dL_out, ldL))) return rc;
+  return end_call(ctx, P, status, &tm);
+}
+
+int blmm_bulkscan_multidf_dev(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG,
+                              int64_t p, int64_t k, const double* dCovar, int64_t ncov, const double* dK, const double* dweights,
+                              const double* h2_grid, int64_t ngrid, double* dL_out, int64_t ldL, double* dh2_out,
+                              blmm_status* status) {
+  if (!ctx) return BLMM_ERR_INVALID;
+  const PvReq pvreq = pv_take(ctx);
+  ctx->red_cur = RedArgs();
+  return multidf_dev_impl(ctx, opts, dY, n, m, dG, p, k, dCovar, ncov, dK, dweights, h2_grid, ngrid, dL_out, ldL, dh2_out, status, pvreq);
+}
+
+// L_out == NULL: L (P x m) stays resident for the blmm_last_* consumers, as blmm_bulkscan
+int blmm_bulkscan_multidf(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, int64_t n, int64_t m, const double* G, int64_t p,
+                          int64_t k, const double* Covar, int64_t ncov, const double* K, const double* weights,
+                          const double* h2_grid, int64_t ngrid, double* L_out, double* h2_out, blmm_status* status) {
+  if (!ctx) return BLMM_ERR_INVALID;
+  const PvReq pvreq = pv_take(ctx);
+  int rc = multidf_check(ctx, opts, n, m, p, k, Covar, ncov);
+  if (rc) return rc;
+  if (!Y || !G || !K || !h2_out) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_multidf: NULL buffer");
+  const int64_t nloci = p / k;
+  HostCall hc(ctx);
+  if ((rc = hc.begin()) || (rc = ensure(ctx, ctx->outL, sizeof(double) * (size_t)(nloci > 0 ? nloci : 1) * (m > 0 ? m : 1))) ||
+      (rc = ensure(ctx, ctx->outH2, sizeof(double) * (size_t)(m > 0 ? m : 1))))
+    return rc;
+  HostCall::In d;
+  if ((rc = hc.inputs(Y, n, m, G, p, K, Covar, ncov, weights, /*defer*/ true, &d))) return rc;
+  ctx->red_cur = RedArgs();
+  if ((rc = multidf_dev_impl(ctx, opts, d.Y, n, m, d.G, p, k, d.Cov, d.ncov, d.K, d.W, h2_grid, ngrid, ptr<double>(ctx->outL),
+                             nloci > 0 ? nloci : 1, ptr<double>(ctx->outH2), status, pvreq))) return rc;
+  set_last(ctx, ptr<double>(ctx->outL), nloci, m);
+  if (L_out && (size_t)nloci * m > 0 && (rc = copy_to_host(ctx, L_out, ctx->outL.p, sizeof(double) * (size_t)nloci * m))) return rc;
+  if (m > 0 && (rc = copy_to_host(ctx, h2_out, ctx->outH2.p, sizeof(double) * (size_t)m))) return rc;
+  if ((rc = hc.finish())) return rc;
+  return check_sticky(ctx);
 }
 
 }  // extern "C"

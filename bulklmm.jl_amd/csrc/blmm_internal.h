@@ -110,7 +110,8 @@ struct blmm_ctx {
       inY, inG, inK, inCov, inW, outL, outH2, tmpA, tmpB, tmpC, perm, r0, altbuf, logtab, lraw, wbQ, wbW, wbRk, lrT, lrC, lrL, lrFlag, lrPart, lrPerm, lrDen0, eigW, xf32, pf32, brSt, brList, illList, qrSlab, lodtab, dynFac, pvtab, outP, redbuf, redtrip, altC, rf32, btG, redflag, bperm,
       locoK, locoPart, locoChr, locoStat, locoKs, locoV, locoLraw,   // blmm_kinship_loco / blmm_bulkscan_loco (kernels_loco.hip)
       locoCmx, locoCarg,   // blmm_bulkscan_loco_reduced: the per-chromosome maxima / arg-maxima when the caller's tables are not on the device
-      locoPerm;            // blmm_bulkscan_loco_perms: the genome-wide (nperms + 1) x m column maxima and their global markers
+      locoPerm,            // blmm_bulkscan_loco_perms: the genome-wide (nperms + 1) x m column maxima and their global markers
+      mdfR, mdfT;          // blmm_bulkscan_multidf: the uncentred rotation and the null-grid factor table (kernels_mdf.hip)
   // event sets: one per timed call since the last blmm_read_timings (grown on demand, reused afterwards)
   struct EvSet { hipEvent_t e[8]; int n; };
   std::vector<EvSet> evsets;
@@ -484,7 +485,26 @@ int launch_bperm_summary(blmm_ctx* ctx, const double* mx, const int64_t* arg, in
 // (gmx / garg already offset), k_red_final's rule; and the buffer's -inf / -1 start
 int launch_bperm_loco_merge(blmm_ctx* ctx, const double* mx, const int64_t* arg, int64_t ncols, int64_t row0, double* gmx, int64_t* garg);
 int launch_bperm_loco_init(blmm_ctx* ctx, int64_t n, double* gmx, int64_t* garg);
-constexpr int BPERM_MAX_NPERMS = 16384;   // k_bperm_summary sorts a trait's maxima in LDS (128 KB)
+constexpr int BPERM_MAX_NPERMS = 16384;
+
+// kernels_mdf.hip: blmm_bulkscan_multidf, the k-degree-of-freedom scan (loci of k adjacent columns of G)
+constexpr double MDF_TAU = BLMM_MULTIDF_TAU;          // rank rule: a locus column is kept iff |r_a|^2 > MDF_TAU |x~_a|^2
+constexpr int MDF_CMAX = BLMM_MULTIDF_MAX_COVARIATES;  // null covariates incl. the intercept
+struct MdfArgs {
+  const double* Xt; int64_t ldx;       // rotated markers (uncentred: k_mdf_rawrot), npad x ldx row-major, locus l = columns l k ..
+  int64_t nloci; int k; int n; int64_t m;
+  const double* P; int64_t ldp; int64_t pstride;   // k_panels' panels (grid: panel 0; exact: 2 + c panels, pstride apart)
+  int c;
+  const double* T; const int* bin;     // null-grid: k_mdf_table's ngrid x nloci factors, each trait's grid bin
+  double* L; int64_t ldL; int64_t* stat;
+};
+int launch_mdf_rawrot(blmm_ctx* ctx, const double* U, const double* wd, int n, int npad, int ldr, double* R);
+int launch_mdf_table(blmm_ctx* ctx, const NullModel& nm, const double* Xt, int64_t ldx, int64_t nloci, int k, const double* Z0,
+                     const double* lam, const double* grid_dev, int ngrid, double* T);
+int launch_mdf_scan(blmm_ctx* ctx, const MdfArgs& a, bool exact);
+int launch_mdf_qr(blmm_ctx* ctx, const NullModel& nm, const double* Yt, int64_t ldy, const double* Xt, int64_t ldx, int64_t nloci, int k,
+                  const double* Z0, const double* lam, const double* h2, const int* list, double* L, int64_t ldL, int64_t* stat);
+   // k_bperm_summary sorts a trait's maxima in LDS (128 KB)
 
 }  // namespace blmm
 

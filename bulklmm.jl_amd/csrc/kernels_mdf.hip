@@ -1,0 +1,550 @@
+// kernels_mdf.hip -- the k-degree-of-freedom scan: one test per LOCUS, a span of k adjacent columns of G (blmm_bulkscan_multidf).
+//
+// Locus l is the columns l k .. l k + k - 1.  For trait j with weights w = |makeweights(h2_j)| and s = sqrt(w):
+//   x~_a = s .* x0_a (the locus's rotated columns),  e~ = s .* (y0 - Z0 beta) / |s .* (y0 - Z0 beta)|  (unit norm, orthogonal to span(Z~))
+//   b_a  = x~_a' e~                              = x_a' panel0_j              (k_panels' panel 0, kernels_prep.hip)
+//   P_ab = x~_a' x~_b                            = (x_a .* x_b)' panel1_j     (panel 1 = w)
+//   u_aq = x~_a' q~_q                            = x_a' panel(2+q)_j          (q~ = s .* Z0 L^-T: orthonormal basis of span(Z~))
+//   S    = P - U U'   (Gram of the locus columns' residuals on span(Z~))
+//   S    = L L' by an unpivoted Cholesky with the RANK RULE: column a is accepted iff its pivot (= |r_a|^2, the part of x~_a
+//          orthogonal to span(Z~) and to the accepted columns before it) exceeds MDF_TAU |x~_a|^2 = MDF_TAU P_aa; a dropped column
+//          gets a zero row and column of L
+//   R^2  = |L^-1 b|^2 over the accepted columns,   LOD = -(n/2) log10(1 - R^2)   (scan_null's (-n/2)(log10 rss1 - log10 rss0))
+// k = 1 is computeR_LMM's r^2 (kernels_scan.hip) through the same panels.
+//
+// The markers are rotated WITHOUT the centring projection of the 1-df path (R = U' Wd, not Q U' Wd: k_mdf_rawrot), because the
+// rank rule compares against the norm of the rotated column itself; the statistic is the same either way.
+//
+//   null-grid  (weights shared per grid bin): k_mdf_table forms, per (bin g, locus l), T = L^-1 (packed k(k+1)/2, the rank rule
+//              applied) from the bin's Gram; k_mdf_grid contracts b = X_l' panel0 for every (locus, trait) and its epilogue is
+//              z = T[bin_j, l] b, R^2 = |z|^2.
+//   null-exact (per-trait weights): k_mdf_exact accumulates b, P (from products x_a x_b formed in registers) and, one covariate
+//              per pass, u_q -- folded into S at once -- then factors S per (locus, trait) in its epilogue.
+//   guard      (null-exact, c >= 2, traits launch_illcond_flag listed: nearly collinear weighted covariates at h2 -> 1):
+//              k_mdf_qr recomputes their columns with an orthonormal basis of span(Z~) from Gram-Schmidt with re-orthogonalisation
+//              and explicit residuals (k_scan_qr's method, kernels_dyn.hip).
+//
+// Layout of the scan kernels: one wave = 64 consecutive loci (one per lane) x TJ traits; the traits are wave-uniform, so their
+// panel values come in through scalar loads and every lane reuses them for its own locus (k vector loads per individual, k TJ
+// FMAs for the grid form).  Four waves per workgroup share the loci (the Xt rows hit L1) and take four trait groups.
+#include "blmm_internal.h"
+#include <cmath>
+
+namespace blmm {
+
+#define KCHECK()                                                                                      \
+  do {                                                                                                \
+    hipError_t e__ = hipGetLastError();                                                               \
+    if (e__ != hipSuccess) return fail(ctx, BLMM_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e__)); \
+  } while (0)
+
+// ---- the per-(locus, trait) algebra ---------------------------------------------------------------------------------------------
+// S (packed lower, row q at q (q + 1) / 2) -> its Cholesky factor with the rank rule against d0 (the raw norms |x~_a|^2), in place.
+template <int K>
+__device__ __forceinline__ void mdf_chol(double (&S)[K * (K + 1) / 2], const double (&d0)[K]) {
+#pragma unroll
+  for (int q = 0; q < K; ++q) {
+#pragma unroll
+    for (int r = 0; r <= q; ++r) {
+      double s = S[q * (q + 1) / 2 + r];
+#pragma unroll
+      for (int u = 0; u < r; ++u) s = fma(-S[q * (q + 1) / 2 + u], S[r * (r + 1) / 2 + u], s);
+      if (r == q) {
+        S[q * (q + 1) / 2 + q] = (s > MDF_TAU * d0[q]) ? sqrt(s) : 0.0;   // NaN / not above the threshold: dropped
+      } else {
+        const double lrr = S[r * (r + 1) / 2 + r];
+        S[q * (q + 1) / 2 + r] = (lrr > 0.0) ? s / lrr : 0.0;
+      }
+    }
+  }
+}
+// |L^-1 b|^2 over the accepted columns (L from mdf_chol)
+template <int K>
+__device__ __forceinline__ double mdf_r2(const double (&Lc)[K * (K + 1) / 2], const double (&b)[K]) {
+  double z[K], r2 = 0.0;
+#pragma unroll
+  for (int q = 0; q < K; ++q) {
+    double s = b[q];
+#pragma unroll
+    for (int u = 0; u < q; ++u) s = fma(-Lc[q * (q + 1) / 2 + u], z[u], s);
+    const double lqq = Lc[q * (q + 1) / 2 + q];
+    z[q] = (lqq > 0.0) ? s / lqq : 0.0;
+    r2 = fma(z[q], z[q], r2);
+  }
+  return r2;
+}
+// r2lod (src/bulkscan_helpers.jl:22-24) for the k-df R^2: 1 - R^2 = 0 -> +Inf; < 0 (R^2 > 1) or NaN -> NaN, counted when `valid`
+__device__ __forceinline__ double mdf_lod(double r2, double scale, bool valid, int* nnan) {
+  const double u = 1.0 - r2;
+  if (u > 0.0) return scale * log10(u);
+  if (u == 0.0) return INFINITY;
+  *nnan += valid ? 1 : 0;
+  return NAN;
+}
+
+// ---- the uncentred rotation  Rraw[i][k] = U[k][i] wd_i  (k_post_eigen's R with centered = 0), zero padded to npad x ldr --------
+__global__ void __launch_bounds__(256) k_mdf_rawrot(const double* __restrict__ U, const double* __restrict__ wd, int n, int npad,
+                                                    int ldr, double* __restrict__ R) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (int64_t)npad * ldr) return;
+  const int k = (int)(e % ldr), i = (int)(e / ldr);
+  R[e] = (i < n && k < n) ? U[(size_t)k * n + i] * (wd ? wd[i] : 1.0) : 0.0;
+}
+
+int launch_mdf_rawrot(blmm_ctx* ctx, const double* U, const double* wd, int n, int npad, int ldr, double* R) {
+  const int64_t tot = (int64_t)npad * ldr;
+  hipLaunchKernelGGL(k_mdf_rawrot, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, U, wd, n, npad, ldr, R);
+  KCHECK();
+  return BLMM_OK;
+}
+
+// ---- null-grid: T[g][l] = L^-1 of the locus's residual Gram under grid point g's weights ----------------------------------------
+// grid = (loci / 256, ngrid); LDS: the weights and Z0 (n (1 + c) doubles), L_Z^-1 of Z0'W_g Z0 (thread 0, as k_isx).
+template <int K>
+__global__ void __launch_bounds__(256) k_mdf_table(int n, int c, const double* __restrict__ Xt, int64_t ldx, int64_t nloci,
+                                                   const double* __restrict__ Z0, const double* __restrict__ lam,
+                                                   const double* __restrict__ grid, double* __restrict__ T) {
+  constexpr int NP = K * (K + 1) / 2;
+  extern __shared__ __attribute__((aligned(16))) double sh[];
+  double* sW = sh;
+  double* sZ = sh + n;
+  __shared__ double sLi[MDF_CMAX * MDF_CMAX];
+  const int g = blockIdx.y;
+  const double h2 = grid[g];
+  const double delta = h2 / (1.0 - h2);
+  for (int e = threadIdx.x; e < n; e += blockDim.x) sW[e] = fabs(1.0 / fma(delta, lam[e], 1.0));
+  for (int e = threadIdx.x; e < n * c; e += blockDim.x) sZ[e] = Z0[e];
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    constexpr int NA = MDF_CMAX * (MDF_CMAX + 1) / 2;
+    double A[NA], Lz[NA];
+    for (int a = 0; a < NA; ++a) A[a] = 0.0;
+    for (int k = 0; k < n; ++k)
+      for (int q = 0; q < c; ++q)
+        for (int r = 0; r <= q; ++r) A[q * (q + 1) / 2 + r] = fma(sW[k] * sZ[q * n + k], sZ[r * n + k], A[q * (q + 1) / 2 + r]);
+    for (int q = 0; q < c; ++q)
+      for (int r = 0; r <= q; ++r) {
+        double s = A[q * (q + 1) / 2 + r];
+        for (int u = 0; u < r; ++u) s = fma(-Lz[q * (q + 1) / 2 + u], Lz[r * (r + 1) / 2 + u], s);
+        Lz[q * (q + 1) / 2 + r] = (r == q) ? sqrt(s) : s / Lz[r * (r + 1) / 2 + r];
+      }
+    for (int q = 0; q < c; ++q)
+      for (int r = 0; r < MDF_CMAX; ++r) {
+        double s = 0.0;
+        if (r <= q) {
+          s = (r == q) ? 1.0 : 0.0;
+          for (int u = r; u < q; ++u) s = fma(-Lz[q * (q + 1) / 2 + u], sLi[u * MDF_CMAX + r], s);
+          s /= Lz[q * (q + 1) / 2 + q];
+        }
+        sLi[q * MDF_CMAX + r] = s;
+      }
+  }
+  __syncthreads();
+  const int64_t l = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (l >= nloci) return;
+  double S[NP], d0[K], xz[K][MDF_CMAX];
+#pragma unroll
+  for (int a = 0; a < NP; ++a) S[a] = 0.0;
+#pragma unroll
+  for (int a = 0; a < K; ++a)
+#pragma unroll
+    for (int q = 0; q < MDF_CMAX; ++q) xz[a][q] = 0.0;
+  const double* xp = Xt + l * K;
+  for (int k = 0; k < n; ++k) {
+    double x[K];
+#pragma unroll
+    for (int a = 0; a < K; ++a) x[a] = xp[(int64_t)k * ldx + a];
+    const double w = sW[k];
+#pragma unroll
+    for (int a = 0; a < K; ++a) {
+      const double wx = w * x[a];
+#pragma unroll
+      for (int b = 0; b <= a; ++b) S[a * (a + 1) / 2 + b] = fma(wx, x[b], S[a * (a + 1) / 2 + b]);
+#pragma unroll
+      for (int q = 0; q < MDF_CMAX; ++q)
+        if (q < c) xz[a][q] = fma(wx, sZ[q * n + k], xz[a][q]);
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < K; ++a) d0[a] = S[a * (a + 1) / 2 + a];
+  // u_aq = (L_Z^-1 Z'W x_a)_q, folded into S one covariate at a time
+#pragma unroll
+  for (int q = 0; q < MDF_CMAX; ++q) {
+    if (q >= c) break;
+    double u[K];
+#pragma unroll
+    for (int a = 0; a < K; ++a) {
+      double s = 0.0;
+#pragma unroll
+      for (int r = 0; r <= q; ++r) s = fma(sLi[q * MDF_CMAX + r], xz[a][r], s);
+      u[a] = s;
+    }
+#pragma unroll
+    for (int a = 0; a < K; ++a)
+#pragma unroll
+      for (int b = 0; b <= a; ++b) S[a * (a + 1) / 2 + b] = fma(-u[a], u[b], S[a * (a + 1) / 2 + b]);
+  }
+  mdf_chol<K>(S, d0);
+  // T = L^-1 (packed lower), rows / columns of dropped loci columns zero
+  double Ti[NP];
+#pragma unroll
+  for (int q = 0; q < K; ++q) {
+    const double lqq = S[q * (q + 1) / 2 + q];
+#pragma unroll
+    for (int r = 0; r <= q; ++r) {
+      double s = (r == q) ? 1.0 : 0.0;
+#pragma unroll
+      for (int u = r; u < q; ++u) s = fma(-S[q * (q + 1) / 2 + u], Ti[u * (u + 1) / 2 + r], s);
+      Ti[q * (q + 1) / 2 + r] = (lqq > 0.0) ? s / lqq : 0.0;
+    }
+  }
+  double* out = T + ((int64_t)g * nloci + l) * NP;
+#pragma unroll
+  for (int a = 0; a < NP; ++a) out[a] = Ti[a];
+}
+
+// ---- null-grid scan ----------------------------------------------------------------------------------------------------------
+template <int K, int TJ>
+__global__ void __launch_bounds__(256) k_mdf_grid(MdfArgs a) {
+  constexpr int NP = K * (K + 1) / 2;
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t j0 = ((int64_t)blockIdx.y * 4 + wv) * TJ;
+  if (j0 >= a.m) return;                                     // the whole wave
+  const int64_t l = (int64_t)blockIdx.x * 64 + lane;
+  const int64_t lc = l < a.nloci ? l : a.nloci - 1;
+  const double* __restrict__ xp = a.Xt + lc * K;
+  const double* __restrict__ ap = a.P + j0;                 // panel 0, traits j0 .. j0 + TJ - 1 (padding columns are zero: j0 + TJ <= ldp)
+  double acc[TJ][K];
+#pragma unroll
+  for (int t = 0; t < TJ; ++t)
+#pragma unroll
+    for (int q = 0; q < K; ++q) acc[t][q] = 0.0;
+  for (int i = 0; i < a.n; ++i) {
+    double x[K], av[TJ];
+#pragma unroll
+    for (int q = 0; q < K; ++q) x[q] = xp[(int64_t)i * a.ldx + q];
+#pragma unroll
+    for (int t = 0; t < TJ; ++t) av[t] = ap[(int64_t)i * a.ldp + t];
+#pragma unroll
+    for (int t = 0; t < TJ; ++t)
+#pragma unroll
+      for (int q = 0; q < K; ++q) acc[t][q] = fma(x[q], av[t], acc[t][q]);
+  }
+  const double scale = -0.5 * (double)a.n;
+  const bool valid = l < a.nloci;
+  int nnan = 0;
+#pragma unroll
+  for (int t = 0; t < TJ; ++t) {
+    const int64_t j = j0 + t;
+    if (j >= a.m) break;
+    const double* Tp = a.T + ((int64_t)a.bin[j] * a.nloci + lc) * NP;
+    double r2 = 0.0;
+#pragma unroll
+    for (int q = 0; q < K; ++q) {
+      double z = 0.0;
+#pragma unroll
+      for (int r = 0; r <= q; ++r) z = fma(Tp[q * (q + 1) / 2 + r], acc[t][r], z);
+      r2 = fma(z, z, r2);
+    }
+    const double lod = mdf_lod(r2, scale, valid, &nnan);
+    if (valid) a.L[j * a.ldL + l] = lod;
+  }
+  if (nnan) atomicAdd((unsigned long long*)&a.stat[ST_NAN_LOD], (unsigned long long)nnan);
+}
+
+// ---- null-exact scan ---------------------------------------------------------------------------------------------------------
+template <int K, int TJ>
+__global__ void __launch_bounds__(256) k_mdf_exact(MdfArgs a) {
+  constexpr int NP = K * (K + 1) / 2;
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t j0 = ((int64_t)blockIdx.y * 4 + wv) * TJ;
+  if (j0 >= a.m) return;
+  const int64_t l = (int64_t)blockIdx.x * 64 + lane;
+  const int64_t lc = l < a.nloci ? l : a.nloci - 1;
+  const double* __restrict__ xp = a.Xt + lc * K;
+  const double* __restrict__ a0 = a.P + j0;
+  const double* __restrict__ a1 = a.P + a.pstride + j0;
+  double b[TJ][K], S[TJ][NP], d0[TJ][K];
+#pragma unroll
+  for (int t = 0; t < TJ; ++t) {
+#pragma unroll
+    for (int q = 0; q < K; ++q) b[t][q] = 0.0;
+#pragma unroll
+    for (int q = 0; q < NP; ++q) S[t][q] = 0.0;
+  }
+  // pass 0: numerators b and the weighted Gram P of the locus columns
+  for (int i = 0; i < a.n; ++i) {
+    double x[K], xx[NP], v0[TJ], v1[TJ];
+#pragma unroll
+    for (int q = 0; q < K; ++q) x[q] = xp[(int64_t)i * a.ldx + q];
+#pragma unroll
+    for (int q = 0; q < K; ++q)
+#pragma unroll
+      for (int r = 0; r <= q; ++r) xx[q * (q + 1) / 2 + r] = x[q] * x[r];
+#pragma unroll
+    for (int t = 0; t < TJ; ++t) { v0[t] = a0[(int64_t)i * a.ldp + t]; v1[t] = a1[(int64_t)i * a.ldp + t]; }
+#pragma unroll
+    for (int t = 0; t < TJ; ++t) {
+#pragma unroll
+      for (int q = 0; q < K; ++q) b[t][q] = fma(x[q], v0[t], b[t][q]);
+#pragma unroll
+      for (int q = 0; q < NP; ++q) S[t][q] = fma(xx[q], v1[t], S[t][q]);
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < TJ; ++t)
+#pragma unroll
+    for (int q = 0; q < K; ++q) d0[t][q] = S[t][q * (q + 1) / 2 + q];
+  // one pass per covariate: u_q = X_l' panel(2+q), S -= u_q u_q'
+  for (int cq = 0; cq < a.c; ++cq) {
+    const double* __restrict__ aq = a.P + (int64_t)(2 + cq) * a.pstride + j0;
+    double u[TJ][K];
+#pragma unroll
+    for (int t = 0; t < TJ; ++t)
+#pragma unroll
+      for (int q = 0; q < K; ++q) u[t][q] = 0.0;
+    for (int i = 0; i < a.n; ++i) {
+      double x[K], v[TJ];
+#pragma unroll
+      for (int q = 0; q < K; ++q) x[q] = xp[(int64_t)i * a.ldx + q];
+#pragma unroll
+      for (int t = 0; t < TJ; ++t) v[t] = aq[(int64_t)i * a.ldp + t];
+#pragma unroll
+      for (int t = 0; t < TJ; ++t)
+#pragma unroll
+        for (int q = 0; q < K; ++q) u[t][q] = fma(x[q], v[t], u[t][q]);
+    }
+#pragma unroll
+    for (int t = 0; t < TJ; ++t)
+#pragma unroll
+      for (int q = 0; q < K; ++q)
+#pragma unroll
+        for (int r = 0; r <= q; ++r) S[t][q * (q + 1) / 2 + r] = fma(-u[t][q], u[t][r], S[t][q * (q + 1) / 2 + r]);
+  }
+  const double scale = -0.5 * (double)a.n;
+  const bool valid = l < a.nloci;
+  int nnan = 0;
+#pragma unroll
+  for (int t = 0; t < TJ; ++t) {
+    const int64_t j = j0 + t;
+    if (j >= a.m) break;
+    mdf_chol<K>(S[t], d0[t]);
+    const double lod = mdf_lod(mdf_r2<K>(S[t], b[t]), scale, valid, &nnan);
+    if (valid) a.L[j * a.ldL + l] = lod;
+  }
+  if (nnan) atomicAdd((unsigned long long*)&a.stat[ST_NAN_LOD], (unsigned long long)nnan);
+}
+
+// ---- the conditioning guard's re-scan of listed traits (null-exact, c >= 2) ------------------------------------------------------
+// block-wide sums of NV values per thread (256 threads), fixed order
+template <int NV>
+__device__ __forceinline__ void mdf_block_sum(double (&v)[NV], double* s_red /* [4][NV] */) {
+#pragma unroll
+  for (int q = 0; q < NV; ++q)
+    for (int off = 32; off > 0; off >>= 1) v[q] += __shfl_xor(v[q], off);
+  const int w = threadIdx.x >> 6;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int q = 0; q < NV; ++q) s_red[w * NV + q] = v[q];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < NV; ++q) v[q] = (s_red[q] + s_red[NV + q]) + (s_red[2 * NV + q] + s_red[3 * NV + q]);
+}
+// tgt (n doubles) -= its components along the orthonormal columns Qb[0 .. nq)
+__device__ __forceinline__ void mdf_project_out(double* tgt, const double* Qb, int nq, int n, double* s_red) {
+  for (int r = 0; r < nq; ++r) {
+    double t[1] = {0.0};
+    for (int k = threadIdx.x; k < n; k += 256) t[0] = fma(Qb[(size_t)r * n + k], tgt[k], t[0]);
+    mdf_block_sum<1>(t, s_red);
+    for (int k = threadIdx.x; k < n; k += 256) tgt[k] = fma(-t[0], Qb[(size_t)r * n + k], tgt[k]);
+  }
+}
+
+// One workgroup per listed trait at a time (grid-stride over the device count stat[ST_ILLCOND]); buf: (c + 2) n doubles (weights'
+// square roots, the orthonormal basis, the unit trait residual), in LDS or in a per-workgroup slab of global memory.
+template <int K>
+__global__ void __launch_bounds__(256) k_mdf_qr(int n, int c, const double* __restrict__ Yt, int64_t ldy,
+                                                const double* __restrict__ Xt, int64_t ldx, int64_t nloci,
+                                                const double* __restrict__ Z0, const double* __restrict__ lam,
+                                                const double* __restrict__ h2v, const int* __restrict__ list, double* slab,
+                                                double* __restrict__ L, int64_t ldL, int64_t* stat) {
+  constexpr int NP = K * (K + 1) / 2;
+  extern __shared__ __attribute__((aligned(16))) double sh[];
+  __shared__ double s_red[4];
+  const int64_t cnt = stat[ST_ILLCOND];
+  if (cnt <= 0) return;
+  double* buf = slab ? slab + (size_t)blockIdx.x * (size_t)(c + 2) * n : sh;
+  double* Sw = buf;
+  double* Qb = buf + n;
+  double* yb = buf + (size_t)(1 + c) * n;
+  const double scale = -0.5 * (double)n;
+  int nnan = 0;
+  for (int64_t item = blockIdx.x; item < cnt; item += gridDim.x) {
+    const int64_t j = list[item];
+    const double h2 = h2v[j];
+    const double delta = h2 / (1.0 - h2);
+    __syncthreads();
+    for (int k = threadIdx.x; k < n; k += 256) {
+      const double s = sqrt(fabs(1.0 / fma(delta, lam[k], 1.0)));
+      Sw[k] = s;
+      for (int q = 0; q < c; ++q) Qb[(size_t)q * n + k] = s * Z0[(size_t)q * n + k];
+      yb[k] = s * Yt[(int64_t)k * ldy + j];
+    }
+    for (int q = 0; q < c; ++q) {
+      double* col = Qb + (size_t)q * n;
+      mdf_project_out(col, Qb, q, n, s_red);
+      mdf_project_out(col, Qb, q, n, s_red);   // twice is enough
+      double nn[1] = {0.0};
+      for (int k = threadIdx.x; k < n; k += 256) nn[0] = fma(col[k], col[k], nn[0]);
+      mdf_block_sum<1>(nn, s_red);
+      const double inv = 1.0 / sqrt(nn[0]);
+      for (int k = threadIdx.x; k < n; k += 256) col[k] *= inv;
+    }
+    mdf_project_out(yb, Qb, c, n, s_red);
+    mdf_project_out(yb, Qb, c, n, s_red);
+    {
+      double nn[1] = {0.0};
+      for (int k = threadIdx.x; k < n; k += 256) nn[0] = fma(yb[k], yb[k], nn[0]);
+      mdf_block_sum<1>(nn, s_red);
+      const double inv = 1.0 / sqrt(nn[0]);
+      for (int k = threadIdx.x; k < n; k += 256) yb[k] *= inv;
+    }
+    __syncthreads();
+    for (int64_t l = threadIdx.x; l < nloci; l += 256) {
+      const double* xp = Xt + l * K;
+      double t[K][MDF_CMAX], t2[K][MDF_CMAX];
+#pragma unroll
+      for (int a = 0; a < K; ++a)
+#pragma unroll
+        for (int q = 0; q < MDF_CMAX; ++q) { t[a][q] = 0.0; t2[a][q] = 0.0; }
+      for (int k = 0; k < n; ++k) {
+#pragma unroll
+        for (int a = 0; a < K; ++a) {
+          const double x = Sw[k] * xp[(int64_t)k * ldx + a];
+#pragma unroll
+          for (int q = 0; q < MDF_CMAX; ++q)
+            if (q < c) t[a][q] = fma(Qb[(size_t)q * n + k], x, t[a][q]);
+        }
+      }
+      for (int k = 0; k < n; ++k) {                  // second projection pass on the first residual
+#pragma unroll
+        for (int a = 0; a < K; ++a) {
+          double x = Sw[k] * xp[(int64_t)k * ldx + a];
+#pragma unroll
+          for (int q = 0; q < MDF_CMAX; ++q)
+            if (q < c) x = fma(-t[a][q], Qb[(size_t)q * n + k], x);
+#pragma unroll
+          for (int q = 0; q < MDF_CMAX; ++q)
+            if (q < c) t2[a][q] = fma(Qb[(size_t)q * n + k], x, t2[a][q]);
+        }
+      }
+#pragma unroll
+      for (int a = 0; a < K; ++a)
+#pragma unroll
+        for (int q = 0; q < MDF_CMAX; ++q) t[a][q] += t2[a][q];
+      double S[NP], bb[K], d0[K];
+#pragma unroll
+      for (int a = 0; a < NP; ++a) S[a] = 0.0;
+#pragma unroll
+      for (int a = 0; a < K; ++a) { bb[a] = 0.0; d0[a] = 0.0; }
+      for (int k = 0; k < n; ++k) {
+        double r[K];
+#pragma unroll
+        for (int a = 0; a < K; ++a) {
+          const double x = Sw[k] * xp[(int64_t)k * ldx + a];
+          d0[a] = fma(x, x, d0[a]);
+          double v = x;
+#pragma unroll
+          for (int q = 0; q < MDF_CMAX; ++q)
+            if (q < c) v = fma(-t[a][q], Qb[(size_t)q * n + k], v);
+          r[a] = v;
+          bb[a] = fma(v, yb[k], bb[a]);
+        }
+#pragma unroll
+        for (int a = 0; a < K; ++a)
+#pragma unroll
+          for (int b = 0; b <= a; ++b) S[a * (a + 1) / 2 + b] = fma(r[a], r[b], S[a * (a + 1) / 2 + b]);
+      }
+      mdf_chol<K>(S, d0);
+      L[j * ldL + l] = mdf_lod(mdf_r2<K>(S, bb), scale, true, &nnan);
+    }
+  }
+  if (nnan) atomicAdd((unsigned long long*)&stat[ST_NAN_LOD], (unsigned long long)nnan);
+}
+
+// ---- launchers -------------------------------------------------------------------------------------------------------------------
+int launch_mdf_table(blmm_ctx* ctx, const NullModel& nm, const double* Xt, int64_t ldx, int64_t nloci, int k, const double* Z0,
+                     const double* lam, const double* grid_dev, int ngrid, double* T) {
+  if (nloci <= 0 || ngrid <= 0) return BLMM_OK;
+  const dim3 grid((unsigned)((nloci + 255) / 256), (unsigned)ngrid);
+  const size_t lds = sizeof(double) * (size_t)nm.n * (1 + nm.c);
+#define TB(K) do { if (lds > 48 * 1024) BLMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mdf_table<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+    hipLaunchKernelGGL(k_mdf_table<K>, grid, dim3(256), lds, ctx->stream, nm.n, nm.c, Xt, ldx, nloci, Z0, lam, grid_dev, T); } while (0)
+  switch (k) {
+    case 1: TB(1); break; case 2: TB(2); break; case 3: TB(3); break; case 4: TB(4); break;
+    case 5: TB(5); break; case 6: TB(6); break; case 7: TB(7); break; case 8: TB(8); break;
+    default: return fail(ctx, BLMM_ERR_UNSUPPORTED, "bulkscan_multidf: null-grid takes 1 <= k <= 8");
+  }
+#undef TB
+  KCHECK();
+  return BLMM_OK;
+}
+
+// traits per wave: the accumulators of one lane stay within ~64 doubles
+template <int K> constexpr int mdf_tj_grid() { return K <= 4 ? 16 : 8; }
+template <int K> constexpr int mdf_tj_exact() { return K == 1 ? 16 : K == 2 ? 8 : 4; }
+
+int launch_mdf_scan(blmm_ctx* ctx, const MdfArgs& a, bool exact) {
+  if (a.nloci <= 0 || a.m <= 0) return BLMM_OK;
+  const unsigned gx = (unsigned)((a.nloci + 63) / 64);
+#define SG(K) do { constexpr int TJ = mdf_tj_grid<K>(); \
+    hipLaunchKernelGGL((k_mdf_grid<K, TJ>), dim3(gx, (unsigned)((a.m + 4 * TJ - 1) / (4 * TJ))), dim3(256), 0, ctx->stream, a); } while (0)
+#define SE(K) do { constexpr int TJ = mdf_tj_exact<K>(); \
+    hipLaunchKernelGGL((k_mdf_exact<K, TJ>), dim3(gx, (unsigned)((a.m + 4 * TJ - 1) / (4 * TJ))), dim3(256), 0, ctx->stream, a); } while (0)
+  if (exact) {
+    switch (a.k) {
+      case 1: SE(1); break; case 2: SE(2); break; case 3: SE(3); break; case 4: SE(4); break;
+      default: return fail(ctx, BLMM_ERR_UNSUPPORTED, "bulkscan_multidf: null-exact takes 1 <= k <= 4");
+    }
+  } else {
+    switch (a.k) {
+      case 1: SG(1); break; case 2: SG(2); break; case 3: SG(3); break; case 4: SG(4); break;
+      case 5: SG(5); break; case 6: SG(6); break; case 7: SG(7); break; case 8: SG(8); break;
+      default: return fail(ctx, BLMM_ERR_UNSUPPORTED, "bulkscan_multidf: null-grid takes 1 <= k <= 8");
+    }
+  }
+#undef SG
+#undef SE
+  KCHECK();
+  return BLMM_OK;
+}
+
+int launch_mdf_qr(blmm_ctx* ctx, const NullModel& nm, const double* Yt, int64_t ldy, const double* Xt, int64_t ldx, int64_t nloci, int k,
+                  const double* Z0, const double* lam, const double* h2, const int* list, double* L, int64_t ldL, int64_t* stat) {
+  if (nloci <= 0 || nm.c < 2) return BLMM_OK;
+  const size_t per = (size_t)(nm.c + 2) * nm.n;
+  const unsigned grid = (unsigned)(2 * (ctx->num_cus > 0 ? ctx->num_cus : 256));
+  double* slab = nullptr;
+  size_t lds = sizeof(double) * per;
+  if (lds > 64 * 1024) {
+    int rc = ensure(ctx, ctx->qrSlab, sizeof(double) * per * grid);
+    if (rc) return rc;
+    slab = ptr<double>(ctx->qrSlab);
+    lds = 0;
+  }
+#define QR(K) do { if (lds > 48 * 1024) BLMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mdf_qr<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+    hipLaunchKernelGGL(k_mdf_qr<K>, dim3(grid), dim3(256), lds, ctx->stream, nm.n, nm.c, Yt, ldy, Xt, ldx, nloci, Z0, lam, h2, list, slab, L, ldL, stat); } while (0)
+  switch (k) {
+    case 1: QR(1); break; case 2: QR(2); break; case 3: QR(3); break; case 4: QR(4); break;
+    default: return fail(ctx, BLMM_ERR_UNSUPPORTED, "bulkscan_multidf: null-exact takes 1 <= k <= 4");
+  }
+#undef QR
+  KCHECK();
+  return BLMM_OK;
+}
+
+}  // namespace blmm

@@ -11,7 +11,7 @@
 # every `ccall`'s symbol, return type and argument tuple (arity and types) against the prototype in include/bulklmm_hip.h.
 module BulkLMMHIP
 
-export calcKinship_loco, bulkscan_loco, bulkscan_loco_reduced, bulkscan_loco_perms, bulkscan_perms, bulkscan_reduced, bulkscan_reduced_async!, synchronize, DeviceLOD, lod_columns, set_tuning, calcKinship, bulkscan, bulkscan_null, bulkscan_null_grid, bulkscan_alt_grid, bulkscan_alt_exact, scan, bulkscan_multi, lod2log10p, get_thresholds,
+export bulkscan_multidf, calcKinship_loco, bulkscan_loco, bulkscan_loco_reduced, bulkscan_loco_perms, bulkscan_perms, bulkscan_reduced, bulkscan_reduced_async!, synchronize, DeviceLOD, lod_columns, set_tuning, calcKinship, bulkscan, bulkscan_null, bulkscan_null_grid, bulkscan_alt_grid, bulkscan_alt_exact, scan, bulkscan_multi, lod2log10p, get_thresholds,
        lod_threshold, lod_colmax, pinned_matrix, host_register, host_unregister
 
 const libblmm = get(ENV, "BULKLMM_HIP_LIB", joinpath(@__DIR__, "..", "csrc", "libbulklmm_hip.so"))
@@ -355,6 +355,50 @@ function bulkscan(Y::Array{Float64, 2}, G::Array{Float64, 2}, Covar::Array{Float
     end
     if output_pvals   # src/bulkscan.jl:154-157
         return merge(res, (log10Pvals_mat = _last_log10p(size(res.L), chisq_df), Chisq_df = chisq_df))
+    end
+    return res
+end
+
+# ---- k-degree-of-freedom bulkscan (blmm_bulkscan_multidf; the reference's README lists it as future work): locus l is the columns
+# (l - 1) k + 1 .. l k of G and each (locus, trait) pair gets one test of all its columns; L is P x m (P = size(G, 2) / k).  Columns that
+# add nothing beyond the covariates and the locus's earlier ones are dropped (complements, duplicates, absent genotypes).  Other
+# keywords as bulkscan; chisq_df (output_pvals) defaults to k.  null-grid: k <= 8; null-exact: k <= 4; at most 8 null covariates.
+function bulkscan_multidf(Y::Array{Float64, 2}, G::Array{Float64, 2}, K::Array{Float64, 2}, k::Integer; kwargs...)
+    return bulkscan_multidf(Y, G, ones(size(Y, 1), 1), K, k; kwargs..., addIntercept = false)
+end
+function bulkscan_multidf(Y::Array{Float64, 2}, G::Array{Float64, 2}, Covar::Array{Float64, 2}, K::Array{Float64, 2}, k::Integer;
+                          method::String = "null-grid", h2_grid::Array{Float64, 1} = collect(0.0:0.1:0.9), addIntercept::Bool = true,
+                          weights::Union{Missing, Array{Float64, 1}} = missing, prior_variance::Float64 = 1.0,
+                          prior_sample_size::Float64 = 0.0, reml::Bool = false, optim_interval::Int64 = 1,
+                          decomp_scheme::String = "eigen", output_pvals::Bool = false, chisq_df::Int64 = Int64(k),
+                          keep_on_device::Bool = false)
+    (n, m) = size(Y); p = size(G, 2)
+    (size(G, 1) != n || size(K, 1) != n || size(K, 2) != n || size(Covar, 1) != n) && error("Dimension mismatch.")
+    (weights !== missing && length(weights) != n) && error("Dimension mismatch.")
+    method in ("null-grid", "null-exact", "alt-grid") || error("Unknown method `$method`; choose null-exact, null-grid or alt-grid.")
+    (k < 1 || p % k != 0) && error("bulkscan_multidf: the number of columns of G must be a multiple of k >= 1")
+    check_n(n)
+    meth = method == "null-exact" ? NULL_EXACT : method == "null-grid" ? NULL_GRID : ALT_GRID
+    o = BlmmOpts(meth, reml, addIntercept, decomp(decomp_scheme), optim_interval, 0, prior_variance, prior_sample_size)
+    P = div(p, k)
+    L = keep_on_device ? nothing : Array{Float64, 2}(undef, P, m)
+    h2 = Array{Float64, 1}(undef, m)
+    st = BlmmStatus()
+    if output_pvals
+        check(ccall((:blmm_set_log10p_output, libblmm), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64),
+                    context(), Ptr{Float64}(C_NULL), Int64(0), chisq_df))
+    end
+    GC.@preserve Y G Covar K weights h2_grid L h2 begin
+        check(ccall((:blmm_bulkscan_multidf, libblmm), Cint,
+                    (Ptr{Cvoid}, Ref{BlmmOpts}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64,
+                     Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ref{BlmmStatus}),
+                    context(), o, Y, n, m, G, p, Int64(k), Covar, size(Covar, 2), K, ptr_or_null(weights), h2_grid,
+                    length(h2_grid), ptr_or_null(L), h2, st))
+    end
+    raise_status(st)
+    res = (L = keep_on_device ? DeviceLOD(P, m) : L, h2_null_list = h2)
+    if output_pvals
+        return merge(res, (log10Pvals_mat = _last_log10p((P, m), chisq_df), Chisq_df = chisq_df))
     end
     return res
 end

@@ -523,6 +523,45 @@ int blmm_bulkscan_loco_perms_dev(blmm_ctx* ctx, const blmm_opts* opts, const dou
                                  double* dchr_lod_max_out, int64_t* dchr_lod_argmax_out, double* dchr_max_perms_out, double* dchr_thr_out,
                                  double* dchr_pval_out, blmm_status* status);
 
+/* ---- k-degree-of-freedom bulkscan: one test per LOCUS of k adjacent columns (F2 / dominance codings, founder probabilities) --
+ * G is n x p with p = P k; locus l is the columns l k .. l k + k - 1.  Y, K, Covar / add_intercept, weights (their pre-scaling
+ * scales every column of G), reml, the prior, optim_interval, decomp_scheme and h2_grid are used as blmm_bulkscan uses them, and
+ * h2_out (m) is blmm_bulkscan's h2_null_list for the same method and options, bit for bit (the null model does not involve G).
+ * For trait j, with s = sqrt(|w(h2_j)|) and the rotated data: y~ = s .* y0, Z~ = s .* Z0, x~_a = s .* (rotated column a of the
+ * locus); e = the residual of y~ on span(Z~).  Rank rule: taking the locus columns in order, column a is kept iff the part r_a of
+ * x~_a orthogonal to span(Z~) and to the kept columns before it has |r_a|^2 > BLMM_MULTIDF_TAU |x~_a|^2 -- complement columns
+ * (probabilities summing to 1 beside the intercept), duplicated columns and absent genotypes drop out.  With Q = span of the kept
+ * r_a, R^2 = |P_Q e|^2 / |e|^2 and
+ *   L[l, j] = -(n/2) log10(1 - R^2)     (scan_null's (-n/2)(log10 rss1 - log10 rss0), src/scan.jl, with the design [Z, G_l]).
+ * k = 1 is blmm_bulkscan's LOD except where the rule drops the column (a constant marker: LOD 0 here).  1 - R^2 = 0 gives +Inf,
+ * R^2 > 1 or NaN gives NaN (counted in n_nan_lod); a trait with e = 0 is counted in n_zero_norm, as blmm_bulkscan does.
+ *   L_out      P x m (ld = P), or NULL: L stays resident (blmm_last_dims = (P, m), blmm_last_lod_colmax, .._threshold, .._columns,
+ *              blmm_last_log10p see it)
+ *   status     as blmm_bulkscan fills it; n_illcond_rescan: null-exact traits whose columns the conditioning guard recomputed
+ *              with an orthogonalised projection (c >= 2)
+ * Limits: null-grid 1 <= k <= BLMM_MULTIDF_MAX_K_GRID, null-exact 1 <= k <= BLMM_MULTIDF_MAX_K_EXACT, at most
+ * BLMM_MULTIDF_MAX_COVARIATES null covariates (incl. the intercept), n <= 2048.  Refused before anything is uploaded: k < 1 or p not
+ * a multiple of k (BLMM_ERR_DIM); k above the method's limit, more covariates, alt-grid (BLMM_ERR_UNSUPPORTED); an unknown method
+ * (BLMM_ERR_METHOD); n > 2048 (BLMM_ERR_UNSUPPORTED, blmm_bulkscan's message).  A pending blmm_set_log10p_output request is
+ * honoured with the request's chisq_df, by a column pass over the finished L (callers pass chisq_df = the number of kept columns,
+ * usually k, or k - 1 for complement columns).
+ * Kernels (kernels_mdf.hip): null-grid forms per (grid point, locus) the factor of the locus's residual Gram, then one contraction
+ * of the markers with the traits' residual panel, 2 n p m flop; null-exact contracts each (locus, trait) pair's numerators, weighted
+ * Gram and covariate products and factors in the epilogue.
+ * The _dev form: device Y / G / Covar / weights / L_out (ld ldL >= P) / h2_out; it enqueues on the context's stream and waits only
+ * for a status or to copy the host h2_grid. */
+#define BLMM_MULTIDF_TAU 1e-8
+#define BLMM_MULTIDF_MAX_K_GRID 8
+#define BLMM_MULTIDF_MAX_K_EXACT 4
+#define BLMM_MULTIDF_MAX_COVARIATES 8
+int blmm_bulkscan_multidf(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, int64_t n, int64_t m, const double* G, int64_t p,
+                          int64_t k, const double* Covar, int64_t ncov, const double* K, const double* weights,
+                          const double* h2_grid, int64_t ngrid, double* L_out, double* h2_out, blmm_status* status);
+int blmm_bulkscan_multidf_dev(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG,
+                              int64_t p, int64_t k, const double* dCovar, int64_t ncov, const double* dK, const double* dweights,
+                              const double* h2_grid, int64_t ngrid, double* dL_out, int64_t ldL, double* dh2_out,
+                              blmm_status* status);
+
 /* ---- scan(y, G, [Z], K; assumption = "alt") -> scan_alt (src/scan.jl:397-453): the variance components are re-estimated for
  * every marker (fitlmm on [Z g_i], src/lmm.jl:56-86, one Brent search per marker on the device).
  * scalars_out = [sigma2_e, h2_null]; lod_out p; h2_each_out p (`h2_each_marker`).  opts->compat_flags:
