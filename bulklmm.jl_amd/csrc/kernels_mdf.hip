@@ -470,10 +470,15 @@ __global__ void __launch_bounds__(256) k_mdf_qr(int n, int c, const double* __re
           for (int b = 0; b <= a; ++b) S[a * (a + 1) / 2 + b] = fma(r[a], r[b], S[a * (a + 1) / 2 + b]);
       }
       mdf_chol<K>(S, d0);
-      L[j * ldL + l] = mdf_lod(mdf_r2<K>(S, bb), scale, true, &nnan);
+      // the scan already wrote (and counted, if NaN) this entry: n_nan_lod counts the NaNs of the finished L, so the re-scan
+      // adds its own NaN and takes back the scan's
+      int now = 0;
+      const double lod = mdf_lod(mdf_r2<K>(S, bb), scale, true, &now);
+      nnan += now - (isnan(L[j * ldL + l]) ? 1 : 0);
+      L[j * ldL + l] = lod;
     }
   }
-  if (nnan) atomicAdd((unsigned long long*)&stat[ST_NAN_LOD], (unsigned long long)nnan);
+  if (nnan) atomicAdd((unsigned long long*)&stat[ST_NAN_LOD], (unsigned long long)(long long)nnan);   // (two's complement: may be < 0)
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------------------------------

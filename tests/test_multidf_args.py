@@ -6,8 +6,8 @@ import re
 import numpy as np
 import pytest
 
-from common import make_data
-from multidf_ref import bulkscan_multidf_ref
+from common import bxd_kinship, make_data
+from multidf_ref import _rotate, bulkscan_multidf_ref
 from oracle import bulklmm_oracle as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -113,3 +113,63 @@ def test_oracle_lod_is_invariant_under_mixing_a_locus():
     h2 = rng.uniform(0, 0.9, 6)
     np.testing.assert_allclose(bulkscan_multidf_ref(Y, Gm, K, k, h2, Covar=Cov), bulkscan_multidf_ref(Y, G, K, k, h2, Covar=Cov),
                                rtol=1e-9, atol=1e-10)
+
+
+def test_oracle_tau_is_a_switch():
+    """A complement perturbed by 1e-4 N(0, 1) has rho ~ 1e-8 .. 1e-9 (n = 30): kept at tau = 1e-10, dropped at 1e-6, where L is the
+    scan of the other column alone."""
+    rng = np.random.default_rng(15)
+    n, P = 30, 11
+    Y, _, K, _ = make_data(n=n, p=10, m=4, seed=16, bxd=False)
+    g = rng.random((n, P))
+    G2 = np.stack([g, 1.0 - g + 1e-4 * rng.standard_normal((n, P))], axis=2).reshape(n, 2 * P)
+    h2 = rng.uniform(0, 0.9, 4)
+    L1 = bulkscan_multidf_ref(Y, g, K, 1, h2)
+    lo, rho = bulkscan_multidf_ref(Y, G2, K, 2, h2, tau=1e-10, return_rho=True)
+    hi = bulkscan_multidf_ref(Y, G2, K, 2, h2, tau=1e-6)
+    assert rho.shape == (P, 2, 4) and (rho[:, 0] > 0.1).all() and ((rho[:, 1] > 1e-10) & (rho[:, 1] < 1e-6)).all()
+    np.testing.assert_allclose(hi, L1, rtol=1e-9, atol=1e-10)
+    assert (lo > L1 + 1e-6).all()                       # the kept column explains a little more of every trait
+    np.testing.assert_array_equal(bulkscan_multidf_ref(Y, G2, K, 2, h2), bulkscan_multidf_ref(Y, G2, K, 2, h2, tau=1e-8))
+
+
+def test_oracle_rho_of_an_exact_complement_is_at_rounding_level():
+    rng = np.random.default_rng(17)
+    n, P = 79, 25
+    Y, _, K, Cov = make_data(n=n, p=10, m=6, seed=18, ncov=2)
+    g = rng.random((n, P))
+    G2 = np.stack([g, 1.0 - g], axis=2).reshape(n, 2 * P)
+    _, rho = bulkscan_multidf_ref(Y, G2, K, 2, rng.uniform(0, 0.9, 6), Covar=Cov, return_rho=True)
+    assert (rho[:, 0] > 1e-2).all() and (rho[:, 1] < 1e-25).all(), float(rho[:, 1].max())
+
+
+def test_oracle_r2_form_agrees_with_least_squares_at_strong_signals():
+    """The oracle's L = -(n/2) log10(1 - |Q'e|^2) against the rss form u = |r1|^2 / |r0|^2 (np.linalg.lstsq on the weighted design
+    with and without the locus), on traits y = 10 + X_l beta + sigma e with sigma log-uniform: LODs up to ~270 at n = 79, k = 3.
+    1 - R^2 cancels: its error grows as 1 / u.  Both forms agree to 1e-9 relative up to LOD 290 (worst seen ~5e-10 near 270, ~1e-12
+    at 200), so the oracle holds the device's 1e-6 bound with a wide margin out to the strong-signal cap (LOD 238)."""
+    rng = np.random.default_rng(9100)
+    n, P, k, m = 79, 40, 3, 96
+    G = rng.dirichlet(np.full(k + 1, 0.7), size=(n, P))[:, :, :k].reshape(n, P * k)
+    K = bxd_kinship()
+    Y = rng.standard_normal((n, m))
+    q = rng.integers(0, P, m)
+    sig = 2.0 ** rng.uniform(-12, 0, m)
+    for t in range(m):
+        Y[:, t] = 10 + G[:, q[t] * k:(q[t] + 1) * k] @ rng.standard_normal(k) * 2 + sig[t] * Y[:, t]
+    h2 = np.array([0.0, 0.3, 0.7])[np.arange(m) % 3]
+    L = bulkscan_multidf_ref(Y, G, K, k, h2)
+    Y0, Z0, X0, lam = _rotate(Y, G, K, None, True, None, "eigen")
+    Lls = np.empty_like(L)
+    for h in np.unique(h2):
+        idx = np.flatnonzero(h2 == h)
+        s = np.sqrt(np.abs(O.makeweights(h, lam)))
+        Zs, ys = s[:, None] * Z0, s[:, None] * Y0[:, idx]
+        r0 = ys - Zs @ np.linalg.lstsq(Zs, ys, rcond=None)[0]
+        for l in range(P):
+            A = np.hstack([Zs, s[:, None] * X0[:, l * k:(l + 1) * k]])
+            r1 = ys - A @ np.linalg.lstsq(A, ys, rcond=None)[0]
+            Lls[l, idx] = -(n / 2.0) * np.log10(np.sum(r1 ** 2, axis=0) / np.sum(r0 ** 2, axis=0))
+    ok = L <= 290.0
+    assert (L[ok] > 200.0).sum() >= 10 and ok.sum() >= 0.95 * L.size
+    np.testing.assert_allclose(L[ok], Lls[ok], rtol=1e-9, atol=1e-10)
