@@ -6,6 +6,7 @@ src/transform_helpers.jl:1-54; src/bulkscan_helpers.jl:175-201), so the parity t
 reference's own tests.  All arithmetic happens on the GPU; there is no CPU fallback."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import warnings
 from typing import NamedTuple, Optional
@@ -244,6 +245,133 @@ class BulkscanAltResult(NamedTuple):
 _METHODS = {"null-exact": L.BLMM_NULL_EXACT, "null-grid": L.BLMM_NULL_GRID, "alt-grid": L.BLMM_ALT_GRID}
 
 
+# ---- the argument plumbing every entry point shares (each raises the reference's error, before any context exists) -----------
+
+def _method(method: str) -> int:
+    if method not in _METHODS:
+        raise BulkLMMError("Unknown method `%s`; choose null-exact, null-grid or alt-grid." % method, -5)
+    return _METHODS[method]
+
+
+def _grid(meth: int, h2_grid):
+    """(grid, ngrid) of a scan: none for null-exact; otherwise h2_grid raveled, None meaning collect(0.0:0.1:0.9)."""
+    if meth == L.BLMM_NULL_EXACT:
+        return None, 0
+    grid = np.ascontiguousarray(np.asarray([i / 10.0 for i in range(10)] if h2_grid is None else h2_grid, dtype=np.float64).ravel())
+    return grid, grid.shape[0]
+
+
+def _host_arrays(Y, G, *K):
+    """Y, G and K (the LOCO forms pass none) through _F, and n, m, p.  G must have n rows, K be n x n (src/transform_helpers.jl:9-11)."""
+    Y = _F(Y)
+    G = _F(G)
+    K = _F(K[0]) if K else None
+    n, m = Y.shape
+    p = G.shape[1]
+    if G.shape[0] != n or (K is not None and (K.shape[0] != n or K.shape[1] != n)):
+        raise BulkLMMError("Dimension mismatch.", -2)
+    return Y, G, K, n, m, p
+
+
+def _host_covariates(Covar, weights, n: int, addIntercept: bool):
+    """(cov, ncov, w, addIntercept): Covar through _F and the weights as a flat float64 array, n rows each.  Without Covar the
+    intercept is the only covariate (bulkscan(Y, G, K): ones(n,1), src/bulkscan.jl:97-104)."""
+    cov, ncov = None, 0
+    if Covar is not None:
+        cov = _F(Covar)
+        if cov.shape[0] != n:
+            raise BulkLMMError("Dimension mismatch.", -2)
+        ncov = cov.shape[1]
+    else:
+        addIntercept = True
+    w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).ravel())
+    if w is not None and w.shape[0] != n:
+        raise BulkLMMError("Dimension mismatch.", -2)
+    return cov, ncov, w, addIntercept
+
+
+def _perm_idx(perm_idx, n: int, nperms: int):
+    """perm_idx as an n x nperms column-major int32 array, or None (no permutations, or the library draws them)."""
+    if perm_idx is None or nperms <= 0:
+        return None
+    pidx = np.asfortranarray(np.asarray(perm_idx, dtype=np.int32))
+    if pidx.shape != (n, nperms):
+        raise BulkLMMError("Dimension mismatch.", -2)
+    return pidx
+
+
+def _null_covariates(ncov: int, addIntercept: bool) -> int:
+    """Columns of the null design: the covariates and the intercept, or the intercept alone."""
+    return ncov + (1 if addIntercept else 0) if ncov > 0 else 1
+
+
+def _probs(signif_level) -> np.ndarray:
+    return np.ascontiguousarray(1.0 - np.atleast_1d(np.asarray(signif_level, dtype=np.float64)))
+
+
+def _kdigits(kinship_digits: Optional[int]) -> int:
+    """The LOCO kinships' rounding: -1 for none."""
+    return -1 if kinship_digits is None else int(kinship_digits)
+
+
+def _dptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _dev_args(Covar, addIntercept: bool, status: bool):
+    """(ncov, addIntercept, status struct or None) of a device form; Covar is (ncov, n), and without it the intercept is the only
+    covariate."""
+    st = L.blmm_status() if status else None
+    if Covar is None:
+        return 0, True, st
+    return Covar.shape[0], addIntercept, st
+
+
+@contextlib.contextmanager
+def _log10p_output(ctx, df, out=None, rows: int = 0):
+    """`output_pvals` (src/bulkscan.jl:154-157) for the one library call in the block: asked for with df (None: not at all) into
+    `out` (a tensor holding a rows x cols column-major matrix) or a buffer of the context.  Enter it after every check that can
+    raise, so that no request is left armed by an exception; the library consumes it first thing in the call whatever happens next,
+    and it is disarmed on the way out."""
+    if df is None:
+        yield
+        return
+    ctx.check(ctx.lib.blmm_set_log10p_output(ctx.h, _dptr(out), 0 if out is None else _ld(out, rows), int(df)))
+    try:
+        yield
+    finally:
+        ctx.lib.blmm_set_log10p_output(ctx.h, None, 0, 0)
+
+
+def _reduced_host(ctx: Context, m: int, threshold, cap, call, extra: dict, h2, return_status: bool) -> dict:
+    """The reduced host forms' call: call(r, st) runs the library once with byrefs of the blmm_reduced and the status; more than
+    `cap` triplets and the WHOLE call runs again with the count it reported.  Returns {"max_lod", "argmax", **extra, "route"
+    [, "h2_null_list": h2 unless None] [, "triplets": (i, j, lod) sorted by (trait, marker)] [, "status"]}."""
+    mx = np.empty(m); arg = np.empty(m, dtype=np.int64)
+    st = L.blmm_status()
+    want = threshold is not None
+    while True:
+        cnt = C.c_int64(0)
+        ii = np.empty(max(cap, 1), dtype=np.int32); jj = np.empty(max(cap, 1), dtype=np.int32); ll = np.empty(max(cap, 1))
+        r = L.blmm_reduced(mx.ctypes.data, arg.ctypes.data, 1 if want else 0, float(threshold) if want else 0.0, int(cap) if want else 0,
+                           ii.ctypes.data, jj.ctypes.data, ll.ctypes.data, C.addressof(cnt))
+        ctx.check(call(C.byref(r), C.byref(st)))
+        if not want or cnt.value <= cap:
+            break
+        cap = int(cnt.value)
+    _raise_status(st)
+    out = {"max_lod": mx, "argmax": arg, **extra, "route": int(ctx.lib.blmm_last_reduced_route(ctx.h))}
+    if h2 is not None:
+        out["h2_null_list"] = h2
+    if want:
+        k = int(cnt.value)
+        order = np.lexsort((ii[:k], jj[:k]))
+        out["triplets"] = (ii[:k][order], jj[:k][order], ll[:k][order])
+    if return_status:
+        out["status"] = st
+    return out
+
+
 def calcKinship(geno, ctx: Optional[Context] = None, digits: Optional[int] = None) -> np.ndarray:
     """src/kinship.jl:4-14.  `digits=12` gives `round.(calcKinship(geno), digits = 12)`, the README's convention
     (README.md:176-181), rounded on the device."""
@@ -358,46 +486,18 @@ class DeviceLOD:
 
 def _bulkscan_call(method, Y, G, K, Covar, h2_grid, addIntercept, weights, prior_variance, prior_sample_size, reml,
                    optim_interval, decomp_scheme, compat_flags, ctx, return_status=False, keep_on_device=False, pvals_df=None):
-    Y = _F(Y)
-    G = _F(G)
-    K = _F(K)
-    n, m = Y.shape
-    p = G.shape[1]
-    if G.shape[0] != n or K.shape[0] != n or K.shape[1] != n:
-        raise BulkLMMError("Dimension mismatch.", -2)  # src/transform_helpers.jl:9-11
+    Y, G, K, n, m, p = _host_arrays(Y, G, K)
     _check_n(n)
-    cov = None
-    ncov = 0
-    if Covar is not None:
-        cov = _F(Covar)
-        if cov.shape[0] != n:
-            raise BulkLMMError("Dimension mismatch.", -2)
-        ncov = cov.shape[1]
-    else:
-        addIntercept = True  # bulkscan(Y, G, K): ones(n,1) as the only covariate (src/bulkscan.jl:97-104)
-    w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).ravel())
-    if w is not None and w.shape[0] != n:
-        raise BulkLMMError("Dimension mismatch.", -2)
-    grid = None
-    ngrid = 0
-    if method != L.BLMM_NULL_EXACT:
-        grid = np.ascontiguousarray(np.asarray(h2_grid, dtype=np.float64).ravel())
-        ngrid = grid.shape[0]
+    cov, ncov, w, addIntercept = _host_covariates(Covar, weights, n, addIntercept)
+    grid, ngrid = _grid(method, h2_grid)
     o = _opts(method, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size, compat_flags)
     ctx = ctx or default_context()  # after the argument checks: those must not need a GPU
     Lout = None if keep_on_device else np.empty((p, m), dtype=np.float64, order="F")
     h2 = np.empty((p, m) if method == L.BLMM_ALT_GRID else (m,), dtype=np.float64, order="F")
     st = L.blmm_status()
-    # `output_pvals` (src/bulkscan.jl:154-157) is asked for right in front of the call -- after every check above, so that no
-    # request is left armed by an exception -- and the library consumes it first thing in the call whatever happens next
-    if pvals_df is not None:
-        ctx.check(ctx.lib.blmm_set_log10p_output(ctx.h, None, 0, int(pvals_df)))
-    try:
+    with _log10p_output(ctx, pvals_df):
         ctx.check(ctx.lib.blmm_bulkscan(ctx.h, C.byref(o), _p(Y), n, m, _p(G), p, _p(cov), ncov, _p(K), _p(w), _p(grid), ngrid,
                                         _p(Lout), _p(h2), C.byref(st)))
-    finally:
-        if pvals_df is not None:
-            ctx.lib.blmm_set_log10p_output(ctx.h, None, 0, 0)
     _raise_status(st)
     if keep_on_device:
         Lout = DeviceLOD(ctx, p, m)
@@ -427,10 +527,7 @@ def bulkscan_into(ctx: Context, method: int, Y, G, K, L_out: np.ndarray, h2_out:
     assert L_out.flags.f_contiguous and L_out.shape == (p, m)
     if h2_out is None:
         h2_out = np.empty((p, m) if method == L.BLMM_ALT_GRID else (m,), order="F")
-    grid, ngrid = None, 0
-    if method != L.BLMM_NULL_EXACT:
-        grid = np.ascontiguousarray(np.asarray(h2_grid if h2_grid is not None else [i / 10.0 for i in range(10)], dtype=np.float64))
-        ngrid = grid.shape[0]
+    grid, ngrid = _grid(method, h2_grid)
     o = _opts(method, reml, True, "eigen", optim_interval, prior_variance, prior_sample_size)
     ctx.check(ctx.lib.blmm_bulkscan(ctx.h, C.byref(o), _p(Y), n, m, _p(G), p, None, 0, _p(K), None, _p(grid), ngrid,
                                     _p(L_out), _p(h2_out), None))
@@ -477,25 +574,11 @@ def bulkscan_alt_exact(Y, G, K, Covar=None, *, reml: bool = False, prior_varianc
     heritability under the alternative, one Brent search per test on the device.  Returns L (p x m), h2_panel (p x m),
     h2_null_list (m), sigma2_e (m); column j equals scan(Y[:, j], ...; assumption = "alt") bit for bit.  Defaults are
     scan's (prior 0 / 0), not bulkscan's."""
-    Y = _F(Y); G = _F(G); K = _F(K)
-    n, m = Y.shape
-    p = G.shape[1]
-    if G.shape[0] != n or K.shape[0] != n or K.shape[1] != n:
-        raise BulkLMMError("Dimension mismatch.", -2)
+    Y, G, K, n, m, p = _host_arrays(Y, G, K)
     _check_n(n)
     if Covar is None and not addIntercept:
         raise BulkLMMError("Intercept has to be added when no other covariate is given.", -7)
-    cov, ncov = None, 0
-    if Covar is not None:
-        cov = _F(Covar)
-        if cov.shape[0] != n:
-            raise BulkLMMError("Dimension mismatch.", -2)
-        ncov = cov.shape[1]
-    else:
-        addIntercept = True
-    w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).ravel())
-    if w is not None and w.shape[0] != n:
-        raise BulkLMMError("Dimension mismatch.", -2)
+    cov, ncov, w, addIntercept = _host_covariates(Covar, weights, n, addIntercept)
     o = _opts(L.BLMM_NULL_EXACT, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
     if alt_true_weights:
         o.compat_flags |= L.BLMM_COMPAT_ALT_TRUE_WEIGHTS
@@ -515,32 +598,13 @@ def bulkscan_multi(mctx: MultiContext, Y, G, K, Covar=None, *, method: str = "nu
     """bulkscan over every GPU of `mctx` in ONE call (blmm_bulkscan_multi): the trait blocks the reference deals to its
     threads (src/bulkscan.jl:263-309) go to the devices.  Same result fields as `bulkscan`; `gather` = "host_shards"
     (default), "none" or "allgather" (include/bulklmm_hip.h)."""
-    if method not in _METHODS:
-        raise BulkLMMError("Unknown method `%s`; choose null-exact, null-grid or alt-grid." % method, -5)
+    meth = _method(method)
     if gather not in _GATHER:
         raise BulkLMMError("gather must be one of none, host_shards, allgather")
-    Y = _F(Y); G = _F(G); K = _F(K)
-    n, m = Y.shape
-    p = G.shape[1]
-    if G.shape[0] != n or K.shape[0] != n or K.shape[1] != n:
-        raise BulkLMMError("Dimension mismatch.", -2)
+    Y, G, K, n, m, p = _host_arrays(Y, G, K)
     _check_n(n)
-    cov, ncov = None, 0
-    if Covar is not None:
-        cov = _F(Covar)
-        if cov.shape[0] != n:
-            raise BulkLMMError("Dimension mismatch.", -2)
-        ncov = cov.shape[1]
-    else:
-        addIntercept = True
-    w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).ravel())
-    if w is not None and w.shape[0] != n:
-        raise BulkLMMError("Dimension mismatch.", -2)
-    meth = _METHODS[method]
-    grid, ngrid = None, 0
-    if meth != L.BLMM_NULL_EXACT:
-        grid = np.ascontiguousarray(np.asarray(h2_grid if h2_grid is not None else [i / 10.0 for i in range(10)], dtype=np.float64))
-        ngrid = grid.shape[0]
+    cov, ncov, w, addIntercept = _host_covariates(Covar, weights, n, addIntercept)
+    grid, ngrid = _grid(meth, h2_grid)
     o = _opts(meth, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
     mo = L.blmm_multi_opts(_GATHER[gather], 0)
     # keep_on_device: no L_out -- every device keeps its block in HBM; mctx.last_colmax() / last_lod_threshold() reduce them there
@@ -604,10 +668,7 @@ def bulkscan(Y, G, K, Covar=None, *, method: str = "null-grid", h2_grid=None, nb
     reference): `L` is a DeviceLOD handle -- the p x m matrix stays in HBM and is reduced there (colmax, threshold triplets,
     permutation quantiles, single columns); the call then costs ~2 ms at BXD size instead of ~39 ms, 36 of which are L's trip
     over PCIe."""
-    if h2_grid is None:
-        h2_grid = [i / 10.0 for i in range(10)]  # collect(0.0:0.1:0.9)
-    if method not in _METHODS:
-        raise BulkLMMError("Unknown method `%s`; choose null-exact, null-grid or alt-grid." % method, -5)
+    _method(method)
     # lod2log10p.(L, chisq_df) merged into the result (src/bulkscan.jl:154-157): asked for with the scan, so that the scan
     # kernels write it from their epilogues (chisq_df = 1, null-* methods) into a buffer of the context
     pv = int(chisq_df) if output_pvals else None
@@ -642,58 +703,19 @@ def bulkscan_reduced(Y, G, K, Covar=None, *, method: str = "null-grid", h2_grid=
     "h2_null_list": m [, "triplets": (i, j, lod) sorted by (trait, marker)], "route": 1 fused | 2 through a resident matrix}.
     `cap`: room for the triplets (16 bytes each, untouched pages cost nothing); more hits than that and the WHOLE call runs again
     with the count it reported -- at the BXD shape, LOD > 5 gives 1e5 triplets, hence the default of 2^20."""
-    if h2_grid is None:
-        h2_grid = [i / 10.0 for i in range(10)]
-    if method not in _METHODS:
-        raise BulkLMMError("Unknown method `%s`; choose null-exact, null-grid or alt-grid." % method, -5)
-    meth = _METHODS[method]
-    Y = _F(Y); G = _F(G); K = _F(K)
-    n, m = Y.shape
-    p = G.shape[1]
-    if G.shape[0] != n or K.shape[0] != n or K.shape[1] != n:
-        raise BulkLMMError("Dimension mismatch.", -2)
+    meth = _method(method)
+    Y, G, K, n, m, p = _host_arrays(Y, G, K)
     _check_n(n)
-    cov, ncov = None, 0
-    if Covar is not None:
-        cov = _F(Covar)
-        if cov.shape[0] != n:
-            raise BulkLMMError("Dimension mismatch.", -2)
-        ncov = cov.shape[1]
-    else:
-        addIntercept = True
-    w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).ravel())
-    if w is not None and w.shape[0] != n:
-        raise BulkLMMError("Dimension mismatch.", -2)
-    grid, ngrid = None, 0
-    if meth != L.BLMM_NULL_EXACT:
-        grid = np.ascontiguousarray(np.asarray(h2_grid, dtype=np.float64).ravel())
-        ngrid = grid.shape[0]
+    cov, ncov, w, addIntercept = _host_covariates(Covar, weights, n, addIntercept)
+    grid, ngrid = _grid(meth, h2_grid)
     o = _opts(meth, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
     ctx = ctx or default_context()
-    mx = np.empty(m); arg = np.empty(m, dtype=np.int64); h2 = np.empty(m)
-    st = L.blmm_status()
-    want = threshold is not None
-    while True:
-        cnt = C.c_int64(0)
-        ii = np.empty(max(cap, 1), dtype=np.int32); jj = np.empty(max(cap, 1), dtype=np.int32); ll = np.empty(max(cap, 1))
-        r = L.blmm_reduced(mx.ctypes.data, arg.ctypes.data, 1 if want else 0, float(threshold) if want else 0.0, int(cap) if want else 0,
-                           ii.ctypes.data, jj.ctypes.data, ll.ctypes.data, C.addressof(cnt))
-        ctx.check(ctx.lib.blmm_bulkscan_reduced(ctx.h, C.byref(o), _p(Y), n, m, _p(G), p, _p(cov), ncov, _p(K), _p(w), _p(grid), ngrid,
-                                                C.byref(r), _p(h2), C.byref(st)))
-        if not want or cnt.value <= cap:
-            break
-        cap = int(cnt.value)
-    _raise_status(st)
-    out = {"max_lod": mx, "argmax": arg, "route": int(ctx.lib.blmm_last_reduced_route(ctx.h))}
-    if meth != L.BLMM_ALT_GRID:
-        out["h2_null_list"] = h2
-    if want:
-        k = int(cnt.value)
-        order = np.lexsort((ii[:k], jj[:k]))
-        out["triplets"] = (ii[:k][order], jj[:k][order], ll[:k][order])
-    if return_status:
-        out["status"] = st
-    return out
+    h2 = np.empty(m)
+
+    def call(r, st):
+        return ctx.lib.blmm_bulkscan_reduced(ctx.h, C.byref(o), _p(Y), n, m, _p(G), p, _p(cov), ncov, _p(K), _p(w), _p(grid), ngrid,
+                                             r, _p(h2), st)
+    return _reduced_host(ctx, m, threshold, cap, call, {}, None if meth == L.BLMM_ALT_GRID else h2, return_status)
 
 
 def scan(y, g, K, covar=None, *, weights=None, prior_variance: float = 0.0, prior_sample_size: float = 0.0,
@@ -721,36 +743,16 @@ def scan(y, g, K, covar=None, *, weights=None, prior_variance: float = 0.0, prio
         raise BulkLMMError("Assumption keyword is not supported. Please enter null or alt.")
     if y.shape[1] != 1:
         raise BulkLMMError("Can only handle one trait.", -6)  # src/scan.jl:496-498
-    G = _F(g)
-    K = _F(K)
-    n = y.shape[0]
-    p = G.shape[1]
-    if G.shape[0] != n or K.shape[0] != n or K.shape[1] != n:
-        raise BulkLMMError("Dimension mismatch.", -2)
+    y, G, K, n, _, p = _host_arrays(y, g, K)
     _check_n(n)
-    cov = None
-    ncov = 0
-    if covar is not None:
-        cov = _F(covar)
-        if cov.shape[0] != n:
-            raise BulkLMMError("Dimension mismatch.", -2)
-        ncov = cov.shape[1]
-    else:
-        addIntercept = True
-    w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).ravel())
-    if w is not None and w.shape[0] != n:
-        raise BulkLMMError("Dimension mismatch.", -2)
+    cov, ncov, w, addIntercept = _host_covariates(covar, weights, n, addIntercept)
     o = _opts(L.BLMM_NULL_EXACT, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
     st = L.blmm_status()
     if not permutation_test:
         nperms = 0
     if nperms < 0:
         raise BulkLMMError("The required number of permutations must be a positive integer.", -9)
-    pidx = None
-    if perm_idx is not None and nperms > 0:
-        pidx = np.asfortranarray(np.asarray(perm_idx, dtype=np.int32))
-        if pidx.shape != (n, nperms):
-            raise BulkLMMError("Dimension mismatch.", -2)
+    pidx = _perm_idx(perm_idx, n, nperms)
     if perm_precision not in ("f64", "f32"):
         raise BulkLMMError("perm_precision must be \"f64\" or \"f32\".")
     ctx = ctx or default_context()
@@ -800,7 +802,7 @@ def get_thresholds(L_perms, signif_level, ctx: Optional[Context] = None):
     ctx = ctx or default_context()
     Lm = _F(L_perms)
     p, nperms = Lm.shape
-    thr_probs = np.ascontiguousarray(1.0 - np.atleast_1d(np.asarray(signif_level, dtype=np.float64)))
+    thr_probs = _probs(signif_level)
     thrs = np.empty(thr_probs.shape[0])
     ctx.check(ctx.lib.blmm_get_thresholds(ctx.h, _p(Lm), p, nperms, _p(thr_probs), thr_probs.shape[0], _p(thrs)))
     return {"probs": thr_probs, "thrs": thrs}
@@ -816,34 +818,13 @@ def bulkscan_perms(Y, G, K, Covar=None, *, nperms: int = 1024, rndseed: int = 0,
     permuted copy); "thresholds": len(signif_level) x m (get_thresholds(L_perms_j, signif_level)); "pvals_perm": m,
     (1 + #{k : max_perms[k, j] >= lod_max[j]}) / (nperms + 1); "probs": 1 - signif_level}.  nperms = 0: the fit and the peaks,
     thresholds and p-values NaN."""
-    Y = _F(Y)
-    G = _F(G)
-    K = _F(K)
-    n, m = Y.shape
-    p = G.shape[1]
-    if G.shape[0] != n or K.shape[0] != n or K.shape[1] != n:
-        raise BulkLMMError("Dimension mismatch.", -2)
+    Y, G, K, n, m, p = _host_arrays(Y, G, K)
     _check_n(n)
     if nperms < 0:
         raise BulkLMMError("The required number of permutations must be a positive integer.", -9)
-    cov = None
-    ncov = 0
-    if Covar is not None:
-        cov = _F(Covar)
-        if cov.shape[0] != n:
-            raise BulkLMMError("Dimension mismatch.", -2)
-        ncov = cov.shape[1]
-    else:
-        addIntercept = True
-    w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).ravel())
-    if w is not None and w.shape[0] != n:
-        raise BulkLMMError("Dimension mismatch.", -2)
-    pidx = None
-    if perm_idx is not None and nperms > 0:
-        pidx = np.asfortranarray(np.asarray(perm_idx, dtype=np.int32))
-        if pidx.shape != (n, nperms):
-            raise BulkLMMError("Dimension mismatch.", -2)
-    probs = np.ascontiguousarray(1.0 - np.atleast_1d(np.asarray(signif_level, dtype=np.float64)))
+    cov, ncov, w, addIntercept = _host_covariates(Covar, weights, n, addIntercept)
+    pidx = _perm_idx(perm_idx, n, nperms)
+    probs = _probs(signif_level)
     ctx = ctx or default_context()
     o = _opts(L.BLMM_NULL_EXACT, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
     st = L.blmm_status()
@@ -962,27 +943,14 @@ def bulkscan_dev(ctx: Context, Y, G, K, L_out, h2_out, *, method: str = "null-ex
     Enqueues on the context's stream and does not synchronise unless `status` is requested."""
     m, n = Y.shape
     p = G.shape[0]
-    grid = None
-    ngrid = 0
-    if method != "null-exact":
-        grid = np.ascontiguousarray(np.asarray(h2_grid if h2_grid is not None else [i / 10.0 for i in range(10)], dtype=np.float64))
-        ngrid = grid.shape[0]
-    ncov = 0 if Covar is None else Covar.shape[0]
-    if Covar is None:
-        addIntercept = True
-    o = _opts(_METHODS[method], reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
-    st = L.blmm_status() if status else None
-    # armed right in front of the call (after everything above that can raise); the library consumes the request first thing
-    if log10p_out is not None:
-        ctx.check(ctx.lib.blmm_set_log10p_output(ctx.h, log10p_out.data_ptr(), _ld(log10p_out, p), int(chisq_df)))
-    try:
-        ctx.check(ctx.lib.blmm_bulkscan_dev(ctx.h, C.byref(o), Y.data_ptr(), n, m, G.data_ptr(), p,
-                                            None if Covar is None else Covar.data_ptr(), ncov, K.data_ptr(),
-                                            None if weights is None else weights.data_ptr(), _p(grid), ngrid,
-                                            L_out.data_ptr(), _ld(L_out, p), h2_out.data_ptr(), C.byref(st) if status else None))
-    finally:
-        if log10p_out is not None:
-            ctx.lib.blmm_set_log10p_output(ctx.h, None, 0, 0)
+    meth = _method(method)
+    grid, ngrid = _grid(meth, h2_grid)
+    ncov, addIntercept, st = _dev_args(Covar, addIntercept, status)
+    o = _opts(meth, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
+    with _log10p_output(ctx, None if log10p_out is None else chisq_df, log10p_out, p):
+        ctx.check(ctx.lib.blmm_bulkscan_dev(ctx.h, C.byref(o), Y.data_ptr(), n, m, G.data_ptr(), p, _dptr(Covar), ncov, K.data_ptr(),
+                                            _dptr(weights), _p(grid), ngrid, L_out.data_ptr(), _ld(L_out, p), h2_out.data_ptr(),
+                                            C.byref(st) if status else None))
     return st
 
 
@@ -994,24 +962,17 @@ def bulkscan_reduced_dev(ctx: Context, Y, G, K, max_out, argmax_out, h2_out, *, 
     threshold given: trip_i / trip_j (int32, cap), trip_lod (float64, cap), trip_count (int64, 1).  Synchronises the stream."""
     m, n = Y.shape
     p = G.shape[0]
-    grid, ngrid = None, 0
-    if method != "null-exact":
-        grid = np.ascontiguousarray(np.asarray(h2_grid if h2_grid is not None else [i / 10.0 for i in range(10)], dtype=np.float64))
-        ngrid = grid.shape[0]
-    ncov = 0 if Covar is None else Covar.shape[0]
-    if Covar is None:
-        addIntercept = True
-    o = _opts(_METHODS[method], reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
-    st = L.blmm_status() if status else None
+    meth = _method(method)
+    grid, ngrid = _grid(meth, h2_grid)
+    ncov, addIntercept, st = _dev_args(Covar, addIntercept, status)
+    o = _opts(meth, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
     want = threshold is not None
-    r = L.blmm_reduced(None if max_out is None else max_out.data_ptr(), None if argmax_out is None else argmax_out.data_ptr(),
-                       1 if want else 0, float(threshold) if want else 0.0, int(trip_i.numel()) if want else 0,
-                       trip_i.data_ptr() if want else None, trip_j.data_ptr() if want else None,
+    r = L.blmm_reduced(_dptr(max_out), _dptr(argmax_out), 1 if want else 0, float(threshold) if want else 0.0,
+                       int(trip_i.numel()) if want else 0, trip_i.data_ptr() if want else None, trip_j.data_ptr() if want else None,
                        trip_lod.data_ptr() if want else None, trip_count.data_ptr() if want else None)
-    ctx.check(ctx.lib.blmm_bulkscan_reduced_dev(ctx.h, C.byref(o), Y.data_ptr(), n, m, G.data_ptr(), p,
-                                                None if Covar is None else Covar.data_ptr(), ncov, K.data_ptr(),
-                                                None if weights is None else weights.data_ptr(), _p(grid), ngrid, C.byref(r),
-                                                None if h2_out is None else h2_out.data_ptr(), C.byref(st) if status else None))
+    ctx.check(ctx.lib.blmm_bulkscan_reduced_dev(ctx.h, C.byref(o), Y.data_ptr(), n, m, G.data_ptr(), p, _dptr(Covar), ncov, K.data_ptr(),
+                                                _dptr(weights), _p(grid), ngrid, C.byref(r), _dptr(h2_out),
+                                                C.byref(st) if status else None))
     return st
 
 
@@ -1024,26 +985,19 @@ def bulkscan_reduced_async(ctx: Context, Y, G, K, max_out, argmax_out, h2_out, i
     stream.  Flagged traits are re-scanned on the device (route 3) instead of a second run; reduced_info() decodes info_out."""
     m, n = Y.shape
     p = G.shape[0]
-    grid, ngrid = None, 0
-    if method != "null-exact":
-        grid = np.ascontiguousarray(np.asarray(h2_grid if h2_grid is not None else [i / 10.0 for i in range(10)], dtype=np.float64))
-        ngrid = grid.shape[0]
-    ncov = 0 if Covar is None else Covar.shape[0]
-    if Covar is None:
-        addIntercept = True
+    meth = _method(method)
+    grid, ngrid = _grid(meth, h2_grid)
+    ncov, addIntercept, _ = _dev_args(Covar, addIntercept, False)
     if info_out is not None and info_out.numel() < L.BLMM_RINFO_LEN:
         raise BulkLMMError(f"info_out holds {info_out.numel()} entries, the info block {L.BLMM_RINFO_LEN}")
-    o = _opts(_METHODS[method], reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
+    o = _opts(meth, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
     want = threshold is not None
-    r = L.blmm_reduced(None if max_out is None else max_out.data_ptr(), None if argmax_out is None else argmax_out.data_ptr(),
-                       1 if want else 0, float(threshold) if want else 0.0, int(trip_i.numel()) if want else 0,
-                       trip_i.data_ptr() if want else None, trip_j.data_ptr() if want else None,
+    r = L.blmm_reduced(_dptr(max_out), _dptr(argmax_out), 1 if want else 0, float(threshold) if want else 0.0,
+                       int(trip_i.numel()) if want else 0, trip_i.data_ptr() if want else None, trip_j.data_ptr() if want else None,
                        trip_lod.data_ptr() if want else None, trip_count.data_ptr() if want else None)
-    ctx.check(ctx.lib.blmm_bulkscan_reduced_async(ctx.h, C.byref(o), Y.data_ptr(), n, m, G.data_ptr(), p,
-                                                  None if Covar is None else Covar.data_ptr(), ncov, K.data_ptr(),
-                                                  None if weights is None else weights.data_ptr(), _p(grid), ngrid, C.byref(r),
-                                                  None if h2_out is None else h2_out.data_ptr(),
-                                                  None if info_out is None else info_out.data_ptr()))
+    ctx.check(ctx.lib.blmm_bulkscan_reduced_async(ctx.h, C.byref(o), Y.data_ptr(), n, m, G.data_ptr(), p, _dptr(Covar), ncov,
+                                                  K.data_ptr(), _dptr(weights), _p(grid), ngrid, C.byref(r), _dptr(h2_out),
+                                                  _dptr(info_out)))
 
 
 def reduced_info(info) -> dict:
@@ -1061,13 +1015,10 @@ def prepare_dev(ctx: Context, K, *, Covar=None, weights=None, addIntercept: bool
     rotation matrix; the context then serves rotate_block_dev / bulkscan_prerotated_dev (one process per GPU: the marker
     rotation is sharded over the ranks, include/bulklmm_hip.h)."""
     n = K.shape[0]
-    ncov = 0 if Covar is None else Covar.shape[0]
-    if Covar is None:
-        addIntercept = True
+    ncov, addIntercept, st = _dev_args(Covar, addIntercept, status)
     o = _opts(L.BLMM_NULL_EXACT, False, addIntercept, decomp_scheme)
-    st = L.blmm_status() if status else None
-    ctx.check(ctx.lib.blmm_prepare_dev(ctx.h, C.byref(o), n, None if Covar is None else Covar.data_ptr(), ncov, K.data_ptr(),
-                                       None if weights is None else weights.data_ptr(), C.byref(st) if status else None))
+    ctx.check(ctx.lib.blmm_prepare_dev(ctx.h, C.byref(o), n, _dptr(Covar), ncov, K.data_ptr(), _dptr(weights),
+                                       C.byref(st) if status else None))
     return st
 
 
@@ -1087,11 +1038,9 @@ def bulkscan_prerotated_dev(ctx: Context, Y, Xt_blocks, p: int, block_cols: int,
     """blmm_bulkscan_prerotated_dev: Y (m, n); Xt_blocks (nblocks, rows, block_ld) contiguous -- the all-gathered output of
     rotate_block_dev, block b = markers [b block_cols, min(p, (b+1) block_cols)); L_out (m, p) [ld = stride(0)]."""
     m = Y.shape[0]
-    grid, ngrid = None, 0
-    if method != "null-exact":
-        grid = np.ascontiguousarray(np.asarray(h2_grid if h2_grid is not None else [i / 10.0 for i in range(10)], dtype=np.float64))
-        ngrid = grid.shape[0]
-    o = _opts(_METHODS[method], reml, True, "eigen", optim_interval, prior_variance, prior_sample_size)
+    meth = _method(method)
+    grid, ngrid = _grid(meth, h2_grid)
+    o = _opts(meth, reml, True, "eigen", optim_interval, prior_variance, prior_sample_size)
     st = L.blmm_status() if status else None
     nb, rows, bld = Xt_blocks.shape
     assert Xt_blocks.is_contiguous() and rows == rotated_rows(ctx)
@@ -1121,8 +1070,8 @@ def scan_perms_prerotated_dev(ctx: Context, y, Xt_blocks, p: int, block_cols: in
     assert Xt_blocks.is_contiguous() and rows == rotated_rows(ctx)
     f32 = Lperms_out is not None and Lperms_out.dtype == torch.float32
     ctx.check(ctx.lib.blmm_scan_perms_prerotated_dev(ctx.h, C.byref(o), y.data_ptr(), int(p), Xt_blocks.data_ptr(), nb, int(block_cols), bld,
-                                                     int(nperms), C.c_uint64(int(seed)), None if perm_idx is None else perm_idx.data_ptr(),
-                                                     scalars_out.data_ptr(), lod_out.data_ptr(),
+                                                     int(nperms), C.c_uint64(int(seed)), _dptr(perm_idx), scalars_out.data_ptr(),
+                                                     lod_out.data_ptr(),
                                                      None if (f32 or Lperms_out is None) else Lperms_out.data_ptr(),
                                                      Lperms_out.data_ptr() if f32 else None, C.byref(st) if status else None))
     return st
@@ -1137,20 +1086,14 @@ def scan_perms_dev(ctx: Context, y, G, K, scalars_out, lod_out, Lperms_out, *, n
     A float32 Lperms_out selects the fp32 permutation kernel (blmm_scan_perms_f32_dev)."""
     n = y.shape[0]
     p = G.shape[0]
-    ncov = 0 if Covar is None else Covar.shape[0]
-    if Covar is None:
-        addIntercept = True
+    ncov, addIntercept, st = _dev_args(Covar, addIntercept, status)
     o = _opts(L.BLMM_NULL_EXACT, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
-    st = L.blmm_status() if status else None
     import torch
     f32 = Lperms_out is not None and Lperms_out.dtype == torch.float32
     fn = ctx.lib.blmm_scan_perms_f32_dev if f32 else ctx.lib.blmm_scan_perms_dev
-    ctx.check(fn(ctx.h, C.byref(o), y.data_ptr(), n, G.data_ptr(), p,
-                                          None if Covar is None else Covar.data_ptr(), ncov, K.data_ptr(),
-                                          None if weights is None else weights.data_ptr(), int(nperms), C.c_uint64(int(seed)),
-                                          None if perm_idx is None else perm_idx.data_ptr(), scalars_out.data_ptr(),
-                                          lod_out.data_ptr(), None if Lperms_out is None else Lperms_out.data_ptr(),
-                                          C.byref(st) if status else None))
+    ctx.check(fn(ctx.h, C.byref(o), y.data_ptr(), n, G.data_ptr(), p, _dptr(Covar), ncov, K.data_ptr(), _dptr(weights), int(nperms),
+                 C.c_uint64(int(seed)), _dptr(perm_idx), scalars_out.data_ptr(), lod_out.data_ptr(), _dptr(Lperms_out),
+                 C.byref(st) if status else None))
     return st
 
 
@@ -1164,18 +1107,14 @@ def bulkscan_perms_dev(ctx: Context, Y, G, K, h2_out, sigma2_out, lod_max_out, l
     Enqueues on the context's stream (status=True synchronises it)."""
     m, n = Y.shape
     p = G.shape[0]
-    ncov = 0 if Covar is None else Covar.shape[0]
-    if Covar is None:
-        addIntercept = True
+    ncov, addIntercept, st = _dev_args(Covar, addIntercept, status)
     o = _opts(L.BLMM_NULL_EXACT, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
-    probs = np.ascontiguousarray(1.0 - np.atleast_1d(np.asarray(signif_level, dtype=np.float64)))
-    st = L.blmm_status() if status else None
-    dp = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-    ctx.check(ctx.lib.blmm_bulkscan_perms_dev(ctx.h, C.byref(o), Y.data_ptr(), n, m, G.data_ptr(), p, dp(Covar), ncov, K.data_ptr(),
-                                              dp(weights), int(nperms), C.c_uint64(int(seed)), dp(perm_idx), _p(probs),
-                                              probs.shape[0], h2_out.data_ptr(), sigma2_out.data_ptr(), lod_max_out.data_ptr(),
-                                              lod_argmax_out.data_ptr(), dp(max_perms_out), dp(thr_out), dp(pval_out),
-                                              C.byref(st) if status else None))
+    probs = _probs(signif_level)
+    ctx.check(ctx.lib.blmm_bulkscan_perms_dev(ctx.h, C.byref(o), Y.data_ptr(), n, m, G.data_ptr(), p, _dptr(Covar), ncov,
+                                              K.data_ptr(), _dptr(weights), int(nperms), C.c_uint64(int(seed)), _dptr(perm_idx),
+                                              _p(probs), probs.shape[0], h2_out.data_ptr(), sigma2_out.data_ptr(),
+                                              lod_max_out.data_ptr(), lod_argmax_out.data_ptr(), _dptr(max_perms_out), _dptr(thr_out),
+                                              _dptr(pval_out), C.byref(st) if status else None))
     return st
 
 
@@ -1230,7 +1169,7 @@ def calcKinship_loco(G, chrom, digits: Optional[int] = None, ctx: Optional[Conte
     nchr = cs.shape[0] - 1
     ctx = ctx or default_context()
     out = np.empty((nchr, n, n), dtype=np.float64)     # block c = matrix c, column-major
-    ctx.check(ctx.lib.blmm_kinship_loco(ctx.h, _p(Gf), n, p, _p(cs), nchr, -1 if digits is None else int(digits), _p(out)))
+    ctx.check(ctx.lib.blmm_kinship_loco(ctx.h, _p(Gf), n, p, _p(cs), nchr, _kdigits(digits), _p(out)))
     return out.transpose(0, 2, 1)
 
 
@@ -1245,43 +1184,20 @@ def bulkscan_loco(Y, G, chrom, Covar=None, *, method: str = "null-grid", h2_grid
     options)["L"] bit for bit.  `chrom`: a length-p sequence of labels in contiguous runs.  Returns {"L": p x m (or a DeviceLOD),
     "h2_null_list": nchr x m (null-* methods) or "h2_panel": p x m (alt-grid), "chromosomes": labels in run order,
     "chr_start": nchr + 1 offsets [, "log10Pvals_mat", "Chisq_df"] [, "status"]}."""
-    if h2_grid is None:
-        h2_grid = [i / 10.0 for i in range(10)]
-    if method not in _METHODS:
-        raise BulkLMMError("Unknown method `%s`; choose null-exact, null-grid or alt-grid." % method, -5)
-    meth = _METHODS[method]
-    Y = _F(Y)
-    G = _F(G)
-    n, m = Y.shape
-    p = G.shape[1]
-    if G.shape[0] != n:
-        raise BulkLMMError("Dimension mismatch.", -2)
+    meth = _method(method)
+    Y, G, _, n, m, p = _host_arrays(Y, G)
     runs, cs = chromosome_runs(chrom, p)
     nchr = cs.shape[0] - 1
     _check_n(n)
-    cov, ncov = None, 0
-    if Covar is not None:
-        cov = _F(Covar)
-        if cov.shape[0] != n:
-            raise BulkLMMError("Dimension mismatch.", -2)
-        ncov = cov.shape[1]
-    else:
-        addIntercept = True
-    w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).ravel())
-    if w is not None and w.shape[0] != n:
-        raise BulkLMMError("Dimension mismatch.", -2)
-    grid, ngrid = None, 0
-    if meth != L.BLMM_NULL_EXACT:
-        grid = np.ascontiguousarray(np.asarray(h2_grid, dtype=np.float64).ravel())
-        ngrid = grid.shape[0]
+    cov, ncov, w, addIntercept = _host_covariates(Covar, weights, n, addIntercept)
+    grid, ngrid = _grid(meth, h2_grid)
     o = _opts(meth, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
     ctx = ctx or default_context()  # after the argument checks: those must not need a GPU
     Lout = None if keep_on_device else np.empty((p, m), dtype=np.float64, order="F")
     h2 = np.empty((p, m), order="F") if meth == L.BLMM_ALT_GRID else np.empty((nchr, m))   # row c: chromosome c's h2 (C order)
     st = L.blmm_status()
-    ctx.check(ctx.lib.blmm_bulkscan_loco(ctx.h, C.byref(o), _p(Y), n, m, _p(G), p, _p(cs), nchr,
-                                         -1 if kinship_digits is None else int(kinship_digits), _p(cov), ncov, _p(w), _p(grid), ngrid,
-                                         _p(Lout), _p(h2), C.byref(st)))
+    ctx.check(ctx.lib.blmm_bulkscan_loco(ctx.h, C.byref(o), _p(Y), n, m, _p(G), p, _p(cs), nchr, _kdigits(kinship_digits), _p(cov),
+                                         ncov, _p(w), _p(grid), ngrid, _p(Lout), _p(h2), C.byref(st)))
     _raise_status(st)
     out = {"L": DeviceLOD(ctx, p, m) if keep_on_device else Lout, "chromosomes": runs, "chr_start": cs}
     out["h2_panel" if meth == L.BLMM_ALT_GRID else "h2_null_list"] = h2
@@ -1305,23 +1221,13 @@ def bulkscan_loco_dev(ctx: Context, Y, G, chr_start, L_out, h2_out, *, method: s
     cs = _check_chr_start(chr_start, p)
     nchr = cs.shape[0] - 1
     _check_n(n)
-    if method not in _METHODS:
-        raise BulkLMMError("Unknown method `%s`; choose null-exact, null-grid or alt-grid." % method, -5)
-    grid, ngrid = None, 0
-    if method != "null-exact":
-        grid = np.ascontiguousarray(np.asarray(h2_grid if h2_grid is not None else [i / 10.0 for i in range(10)], dtype=np.float64))
-        ngrid = grid.shape[0]
-    ncov = 0 if Covar is None else Covar.shape[0]
-    if Covar is None:
-        addIntercept = True
-    o = _opts(_METHODS[method], reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
-    st = L.blmm_status() if status else None
-    ctx.check(ctx.lib.blmm_bulkscan_loco_dev(ctx.h, C.byref(o), Y.data_ptr(), n, m, G.data_ptr(), p, _p(cs), nchr,
-                                             -1 if kinship_digits is None else int(kinship_digits),
-                                             None if Covar is None else Covar.data_ptr(), ncov,
-                                             None if weights is None else weights.data_ptr(), _p(grid), ngrid,
-                                             None if K_loco is None else K_loco.data_ptr(), L_out.data_ptr(), _ld(L_out, p),
-                                             None if h2_out is None else h2_out.data_ptr(), C.byref(st) if status else None))
+    meth = _method(method)
+    grid, ngrid = _grid(meth, h2_grid)
+    ncov, addIntercept, st = _dev_args(Covar, addIntercept, status)
+    o = _opts(meth, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
+    ctx.check(ctx.lib.blmm_bulkscan_loco_dev(ctx.h, C.byref(o), Y.data_ptr(), n, m, G.data_ptr(), p, _p(cs), nchr, _kdigits(kinship_digits),
+                                             _dptr(Covar), ncov, _dptr(weights), _p(grid), ngrid, _dptr(K_loco), L_out.data_ptr(),
+                                             _ld(L_out, p), _dptr(h2_out), C.byref(st) if status else None))
     return st
 
 
@@ -1336,68 +1242,26 @@ def bulkscan_loco_reduced(Y, G, chrom, Covar=None, *, method: str = "null-grid",
     -inf / -1 where every LOD is NaN), "h2_null_list": (nchr, m) (null-* methods), "chromosomes", "chr_start" [, "triplets": (i, j,
     lod) sorted by (trait, marker)], "route": 1 fused | 3 fused with on-device re-scans | 2 per-chromosome resident block
     [, "status"]}.  `cap` as bulkscan_reduced: more hits than that and the whole call runs again with the count it reported."""
-    if h2_grid is None:
-        h2_grid = [i / 10.0 for i in range(10)]
-    if method not in _METHODS:
-        raise BulkLMMError("Unknown method `%s`; choose null-exact, null-grid or alt-grid." % method, -5)
-    meth = _METHODS[method]
+    meth = _method(method)
     if int(cap) < 0:
         raise BulkLMMError("bulkscan_loco_reduced: triplet buffers (cap < 0)", -1)
-    Y = _F(Y)
-    G = _F(G)
-    n, m = Y.shape
-    p = G.shape[1]
-    if G.shape[0] != n:
-        raise BulkLMMError("Dimension mismatch.", -2)
+    Y, G, _, n, m, p = _host_arrays(Y, G)
     runs, cs = chromosome_runs(chrom, p)
     nchr = cs.shape[0] - 1
     _check_n(n)
-    cov, ncov = None, 0
-    if Covar is not None:
-        cov = _F(Covar)
-        if cov.shape[0] != n:
-            raise BulkLMMError("Dimension mismatch.", -2)
-        ncov = cov.shape[1]
-    else:
-        addIntercept = True
-    w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).ravel())
-    if w is not None and w.shape[0] != n:
-        raise BulkLMMError("Dimension mismatch.", -2)
-    grid, ngrid = None, 0
-    if meth != L.BLMM_NULL_EXACT:
-        grid = np.ascontiguousarray(np.asarray(h2_grid, dtype=np.float64).ravel())
-        ngrid = grid.shape[0]
+    cov, ncov, w, addIntercept = _host_covariates(Covar, weights, n, addIntercept)
+    grid, ngrid = _grid(meth, h2_grid)
     o = _opts(meth, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
     ctx = ctx or default_context()  # after the argument checks: those must not need a GPU
-    mx = np.empty(m); arg = np.empty(m, dtype=np.int64)
     cmx = np.empty((nchr, m)); carg = np.empty((nchr, m), dtype=np.int64)     # row c: chromosome c (C order = the library's blocks)
     h2 = np.empty((nchr, m))
-    st = L.blmm_status()
-    want = threshold is not None
-    cap = int(cap)
-    while True:
-        cnt = C.c_int64(0)
-        ii = np.empty(max(cap, 1), dtype=np.int32); jj = np.empty(max(cap, 1), dtype=np.int32); ll = np.empty(max(cap, 1))
-        r = L.blmm_reduced(mx.ctypes.data, arg.ctypes.data, 1 if want else 0, float(threshold) if want else 0.0, cap if want else 0,
-                           ii.ctypes.data, jj.ctypes.data, ll.ctypes.data, C.addressof(cnt))
-        ctx.check(ctx.lib.blmm_bulkscan_loco_reduced(ctx.h, C.byref(o), _p(Y), n, m, _p(G), p, _p(cs), nchr,
-                                                     -1 if kinship_digits is None else int(kinship_digits), _p(cov), ncov, _p(w),
-                                                     _p(grid), ngrid, C.byref(r), _p(cmx), _p(carg), _p(h2), C.byref(st)))
-        if not want or cnt.value <= cap:
-            break
-        cap = int(cnt.value)
-    _raise_status(st)
-    out = {"max_lod": mx, "argmax": arg, "chr_max_lod": cmx, "chr_argmax": carg, "chromosomes": runs, "chr_start": cs,
-           "route": int(ctx.lib.blmm_last_reduced_route(ctx.h))}
-    if meth != L.BLMM_ALT_GRID:
-        out["h2_null_list"] = h2
-    if want:
-        k = int(cnt.value)
-        order = np.lexsort((ii[:k], jj[:k]))
-        out["triplets"] = (ii[:k][order], jj[:k][order], ll[:k][order])
-    if return_status:
-        out["status"] = st
-    return out
+
+    def call(r, st):
+        return ctx.lib.blmm_bulkscan_loco_reduced(ctx.h, C.byref(o), _p(Y), n, m, _p(G), p, _p(cs), nchr, _kdigits(kinship_digits),
+                                                  _p(cov), ncov, _p(w), _p(grid), ngrid, r, _p(cmx), _p(carg), _p(h2), st)
+    return _reduced_host(ctx, m, threshold, int(cap), call,
+                         {"chr_max_lod": cmx, "chr_argmax": carg, "chromosomes": runs, "chr_start": cs},
+                         None if meth == L.BLMM_ALT_GRID else h2, return_status)
 
 
 def bulkscan_loco_reduced_dev(ctx: Context, Y, G, chr_start, max_out, argmax_out, chr_max_out, chr_argmax_out, h2_out, *,
@@ -1415,26 +1279,18 @@ def bulkscan_loco_reduced_dev(ctx: Context, Y, G, chr_start, max_out, argmax_out
     cs = _check_chr_start(chr_start, p)
     nchr = cs.shape[0] - 1
     _check_n(n)
-    if method not in _METHODS:
-        raise BulkLMMError("Unknown method `%s`; choose null-exact, null-grid or alt-grid." % method, -5)
-    grid, ngrid = None, 0
-    if method != "null-exact":
-        grid = np.ascontiguousarray(np.asarray(h2_grid if h2_grid is not None else [i / 10.0 for i in range(10)], dtype=np.float64))
-        ngrid = grid.shape[0]
-    ncov = 0 if Covar is None else Covar.shape[0]
-    if Covar is None:
-        addIntercept = True
-    o = _opts(_METHODS[method], reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
-    st = L.blmm_status() if status else None
+    meth = _method(method)
+    grid, ngrid = _grid(meth, h2_grid)
+    ncov, addIntercept, st = _dev_args(Covar, addIntercept, status)
+    o = _opts(meth, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
     want = threshold is not None
-    dp = lambda t: None if t is None else t.data_ptr()
-    r = L.blmm_reduced(dp(max_out), dp(argmax_out), 1 if want else 0, float(threshold) if want else 0.0,
-                       int(trip_i.numel()) if want else 0, dp(trip_i) if want else None, dp(trip_j) if want else None,
-                       dp(trip_lod) if want else None, dp(trip_count) if want else None)
+    r = L.blmm_reduced(_dptr(max_out), _dptr(argmax_out), 1 if want else 0, float(threshold) if want else 0.0,
+                       int(trip_i.numel()) if want else 0, _dptr(trip_i) if want else None, _dptr(trip_j) if want else None,
+                       _dptr(trip_lod) if want else None, _dptr(trip_count) if want else None)
     ctx.check(ctx.lib.blmm_bulkscan_loco_reduced_dev(ctx.h, C.byref(o), Y.data_ptr(), n, m, G.data_ptr(), p, _p(cs), nchr,
-                                                     -1 if kinship_digits is None else int(kinship_digits), dp(Covar), ncov, dp(weights),
-                                                     _p(grid), ngrid, dp(K_loco), C.byref(r), dp(chr_max_out), dp(chr_argmax_out),
-                                                     dp(h2_out), C.byref(st) if status else None))
+                                                     _kdigits(kinship_digits), _dptr(Covar), ncov, _dptr(weights), _p(grid), ngrid,
+                                                     _dptr(K_loco), C.byref(r), _dptr(chr_max_out), _dptr(chr_argmax_out),
+                                                     _dptr(h2_out), C.byref(st) if status else None))
     return st
 
 
@@ -1450,7 +1306,7 @@ def _loco_perms_checks(n: int, nperms: int, ncov: int, addIntercept: bool, nprob
         raise BulkLMMError("The required number of permutations must be a positive integer.", -9)
     if nperms > BPERM_MAX_NPERMS:
         raise BulkLMMError("bulkscan_loco_perms: more than 16384 permutations (the per-trait sort runs in LDS)", -10)
-    if (ncov + (1 if addIntercept else 0) if ncov > 0 else 1) > BPERM_MAX_COVARIATES:
+    if _null_covariates(ncov, addIntercept) > BPERM_MAX_COVARIATES:
         raise BulkLMMError("bulkscan_loco_perms: more than 8 null covariates (incl. intercept) are not supported", -10)
     if nprobs > 64:
         raise BulkLMMError("bulkscan_loco_perms: 0 .. 64 threshold levels", -1)
@@ -1473,35 +1329,16 @@ def bulkscan_loco_perms(Y, G, chrom, Covar=None, *, nperms: int = 1024, rndseed:
     "max_perms": (nperms, m); "thresholds": (len(signif_level), m); "chr_lod_max", "chr_lod_argmax", "chr_pvals_perm": (nchr, m);
     "chr_thresholds": (nchr, len(signif_level), m) [; "chr_max_perms": (nchr, nperms, m) when chr_max_perms]; "probs";
     "chromosomes"; "chr_start" [; "status"]}.  nperms = 0: thresholds and p-values NaN."""
-    Y = _F(Y)
-    G = _F(G)
-    n, m = Y.shape
-    p = G.shape[1]
-    if G.shape[0] != n:
-        raise BulkLMMError("Dimension mismatch.", -2)
+    Y, G, _, n, m, p = _host_arrays(Y, G)
     runs, cs = chromosome_runs(chrom, p)
     nchr = cs.shape[0] - 1
     nperms = int(nperms)
-    cov, ncov = None, 0
-    if Covar is not None:
-        cov = _F(Covar)
-        if cov.shape[0] != n:
-            raise BulkLMMError("Dimension mismatch.", -2)
-        ncov = cov.shape[1]
-    else:
-        addIntercept = True
-    w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).ravel())
-    if w is not None and w.shape[0] != n:
-        raise BulkLMMError("Dimension mismatch.", -2)
-    probs = np.ascontiguousarray(1.0 - np.atleast_1d(np.asarray(signif_level, dtype=np.float64)))
+    cov, ncov, w, addIntercept = _host_covariates(Covar, weights, n, addIntercept)
+    probs = _probs(signif_level)
     _loco_perms_checks(n, nperms, ncov, addIntercept, probs.shape[0])
-    pidx = None
-    if perm_idx is not None and nperms > 0:
-        pidx = np.asfortranarray(np.asarray(perm_idx, dtype=np.int32))
-        if pidx.shape != (n, nperms):
-            raise BulkLMMError("Dimension mismatch.", -2)
-        if pidx.size and (pidx.min() < 0 or pidx.max() >= n):
-            raise BulkLMMError("bulkscan_loco_perms: perm_idx entries must lie in 0 .. n - 1", -1)
+    pidx = _perm_idx(perm_idx, n, nperms)
+    if pidx is not None and pidx.size and (pidx.min() < 0 or pidx.max() >= n):
+        raise BulkLMMError("bulkscan_loco_perms: perm_idx entries must lie in 0 .. n - 1", -1)
     o = _opts(L.BLMM_NULL_EXACT, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
     ctx = ctx or default_context()  # after the argument checks: those must not need a GPU
     npr = probs.shape[0]
@@ -1516,7 +1353,7 @@ def bulkscan_loco_perms(Y, G, chrom, Covar=None, *, nperms: int = 1024, rndseed:
     cmp = np.empty((nchr, m, max(nperms, 1))) if chr_max_perms else None
     st = L.blmm_status()
     ctx.check(ctx.lib.blmm_bulkscan_loco_perms(ctx.h, C.byref(o), _p(Y), n, m, _p(G), p, _p(cs), nchr,
-                                               -1 if kinship_digits is None else int(kinship_digits), _p(cov), ncov, _p(w), nperms,
+                                               _kdigits(kinship_digits), _p(cov), ncov, _p(w), nperms,
                                                C.c_uint64(int(rndseed)), _p(pidx), _p(probs), npr, _p(h2), _p(s2), _p(mx), _p(arg),
                                                _p(mp), _p(thr), _p(pv), _p(cmx), _p(carg), _p(cmp), _p(cthr), _p(cpv), C.byref(st)))
     _raise_status(st)
@@ -1547,21 +1384,17 @@ def bulkscan_loco_perms_dev(ctx: Context, Y, G, chr_start, h2_out, sigma2_out, l
     p = G.shape[0]
     cs = _check_chr_start(chr_start, p)
     nchr = cs.shape[0] - 1
-    ncov = 0 if Covar is None else Covar.shape[0]
-    if Covar is None:
-        addIntercept = True
-    probs = np.ascontiguousarray(1.0 - np.atleast_1d(np.asarray(signif_level, dtype=np.float64)))
+    ncov, addIntercept, st = _dev_args(Covar, addIntercept, status)
+    probs = _probs(signif_level)
     _loco_perms_checks(n, int(nperms), ncov, addIntercept, probs.shape[0])
     o = _opts(L.BLMM_NULL_EXACT, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
-    st = L.blmm_status() if status else None
-    dp = lambda t: None if t is None else t.data_ptr()   # noqa: E731
     ctx.check(ctx.lib.blmm_bulkscan_loco_perms_dev(ctx.h, C.byref(o), Y.data_ptr(), n, m, G.data_ptr(), p, _p(cs), nchr,
-                                                   -1 if kinship_digits is None else int(kinship_digits), dp(Covar), ncov, dp(weights),
-                                                   int(nperms), C.c_uint64(int(seed)), dp(perm_idx), _p(probs), probs.shape[0],
-                                                   dp(K_loco), dp(h2_out), dp(sigma2_out), dp(lod_max_out), dp(lod_argmax_out),
-                                                   dp(max_perms_out), dp(thr_out), dp(pval_out), dp(chr_lod_max_out),
-                                                   dp(chr_lod_argmax_out), dp(chr_max_perms_out), dp(chr_thr_out), dp(chr_pval_out),
-                                                   C.byref(st) if status else None))
+                                                   _kdigits(kinship_digits), _dptr(Covar), ncov, _dptr(weights), int(nperms),
+                                                   C.c_uint64(int(seed)), _dptr(perm_idx), _p(probs), probs.shape[0], _dptr(K_loco),
+                                                   _dptr(h2_out), _dptr(sigma2_out), _dptr(lod_max_out), _dptr(lod_argmax_out),
+                                                   _dptr(max_perms_out), _dptr(thr_out), _dptr(pval_out), _dptr(chr_lod_max_out),
+                                                   _dptr(chr_lod_argmax_out), _dptr(chr_max_perms_out), _dptr(chr_thr_out),
+                                                   _dptr(chr_pval_out), C.byref(st) if status else None))
     return st
 
 
@@ -1580,7 +1413,7 @@ def _multidf_checks(method: str, n: int, p: int, k, ncov: int, addIntercept: boo
         raise BulkLMMError("bulkscan_multidf: alt-grid is not supported; use null-grid or null-exact", -10)
     if k > _MULTIDF_KMAX[method]:
         raise BulkLMMError("bulkscan_multidf: %s takes 1 <= k <= %d" % (method, _MULTIDF_KMAX[method]), -10)
-    if (ncov + (1 if addIntercept else 0) if ncov > 0 else 1) > L.BLMM_MULTIDF_MAX_COVARIATES:
+    if _null_covariates(ncov, addIntercept) > L.BLMM_MULTIDF_MAX_COVARIATES:
         raise BulkLMMError("bulkscan_multidf: more than 8 null covariates (incl. intercept) are not supported", -10)
     _check_n(n)
     return k
@@ -1597,49 +1430,23 @@ def bulkscan_multidf(Y, G, K, k: int, Covar=None, *, method: str = "null-grid", 
     1e-8 |x|^2: complements, duplicates, absent genotypes) are dropped.  Every other argument is bulkscan's; h2_null_list is
     bulkscan's, bit for bit.  `chisq_df` (output_pvals) defaults to k -- callers who pass complement columns choose k - 1.
     Returns {"L": P x m ndarray (DeviceLOD when keep_on_device), "h2_null_list": m [, "log10Pvals_mat", "Chisq_df"] [, "status"]}."""
-    if h2_grid is None:
-        h2_grid = [i / 10.0 for i in range(10)]  # collect(0.0:0.1:0.9)
-    Y = _F(Y)
-    G = _F(G)
-    K = _F(K)
-    n, m = Y.shape
-    p = G.shape[1]
-    if G.shape[0] != n or K.shape[0] != n or K.shape[1] != n:
-        raise BulkLMMError("Dimension mismatch.", -2)
-    cov, ncov = None, 0
-    if Covar is not None:
-        cov = _F(Covar)
-        if cov.shape[0] != n:
-            raise BulkLMMError("Dimension mismatch.", -2)
-        ncov = cov.shape[1]
-    else:
-        addIntercept = True
-    w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float64).ravel())
-    if w is not None and w.shape[0] != n:
-        raise BulkLMMError("Dimension mismatch.", -2)
+    Y, G, K, n, m, p = _host_arrays(Y, G, K)
+    cov, ncov, w, addIntercept = _host_covariates(Covar, weights, n, addIntercept)
     k = _multidf_checks(method, n, p, k, ncov, addIntercept)
     df = k if chisq_df is None else int(chisq_df)
     if output_pvals and not 1 <= df <= 1000000:
         raise BulkLMMError("chisq_df must lie in 1 .. 10^6", -1)
-    grid = None
-    ngrid = 0
-    if method != "null-exact":
-        grid = np.ascontiguousarray(np.asarray(h2_grid, dtype=np.float64).ravel())
-        ngrid = grid.shape[0]
-    o = _opts(_METHODS[method], reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
+    meth = _METHODS[method]
+    grid, ngrid = _grid(meth, h2_grid)
+    o = _opts(meth, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
     ctx = ctx or default_context()  # after the argument checks: those must not need a GPU
     P = p // k
     Lout = None if keep_on_device else np.empty((P, m), dtype=np.float64, order="F")
     h2 = np.empty(m, dtype=np.float64)
     st = L.blmm_status()
-    if output_pvals:
-        ctx.check(ctx.lib.blmm_set_log10p_output(ctx.h, None, 0, df))
-    try:
+    with _log10p_output(ctx, df if output_pvals else None):
         ctx.check(ctx.lib.blmm_bulkscan_multidf(ctx.h, C.byref(o), _p(Y), n, m, _p(G), p, k, _p(cov), ncov, _p(K), _p(w), _p(grid), ngrid,
                                                 _p(Lout), _p(h2), C.byref(st)))
-    finally:
-        if output_pvals:
-            ctx.lib.blmm_set_log10p_output(ctx.h, None, 0, 0)
     _raise_status(st)
     out = {"L": DeviceLOD(ctx, P, m) if keep_on_device else Lout, "h2_null_list": h2}
     if output_pvals:
@@ -1659,26 +1466,14 @@ def bulkscan_multidf_dev(ctx: Context, Y, G, K, k: int, L_out, h2_out, *, method
     the same call (blmm_set_log10p_output).  Enqueues on the context's stream; synchronises only for `status`."""
     m, n = Y.shape
     p = G.shape[0]
-    ncov = 0 if Covar is None else Covar.shape[0]
-    if Covar is None:
-        addIntercept = True
+    ncov, addIntercept, st = _dev_args(Covar, addIntercept, status)
     k = _multidf_checks(method, n, p, k, ncov, addIntercept)
     P = p // k
-    grid = None
-    ngrid = 0
-    if method != "null-exact":
-        grid = np.ascontiguousarray(np.asarray(h2_grid if h2_grid is not None else [i / 10.0 for i in range(10)], dtype=np.float64))
-        ngrid = grid.shape[0]
-    o = _opts(_METHODS[method], reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
-    st = L.blmm_status() if status else None
-    if log10p_out is not None:
-        ctx.check(ctx.lib.blmm_set_log10p_output(ctx.h, log10p_out.data_ptr(), _ld(log10p_out, P), k if chisq_df is None else int(chisq_df)))
-    try:
-        ctx.check(ctx.lib.blmm_bulkscan_multidf_dev(ctx.h, C.byref(o), Y.data_ptr(), n, m, G.data_ptr(), p, k,
-                                                    None if Covar is None else Covar.data_ptr(), ncov, K.data_ptr(),
-                                                    None if weights is None else weights.data_ptr(), _p(grid), ngrid,
-                                                    L_out.data_ptr(), _ld(L_out, P), h2_out.data_ptr(), C.byref(st) if status else None))
-    finally:
-        if log10p_out is not None:
-            ctx.lib.blmm_set_log10p_output(ctx.h, None, 0, 0)
+    meth = _METHODS[method]
+    grid, ngrid = _grid(meth, h2_grid)
+    o = _opts(meth, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
+    with _log10p_output(ctx, None if log10p_out is None else (k if chisq_df is None else chisq_df), log10p_out, P):
+        ctx.check(ctx.lib.blmm_bulkscan_multidf_dev(ctx.h, C.byref(o), Y.data_ptr(), n, m, G.data_ptr(), p, k, _dptr(Covar), ncov,
+                                                    K.data_ptr(), _dptr(weights), _p(grid), ngrid, L_out.data_ptr(), _ld(L_out, P),
+                                                    h2_out.data_ptr(), C.byref(st) if status else None))
     return st
