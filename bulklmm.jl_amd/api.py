@@ -1477,3 +1477,104 @@ def bulkscan_multidf_dev(ctx: Context, Y, G, K, k: int, L_out, h2_out, *, method
                                                     K.data_ptr(), _dptr(weights), _p(grid), ngrid, L_out.data_ptr(), _ld(L_out, P),
                                                     h2_out.data_ptr(), C.byref(st) if status else None))
     return st
+
+
+# ---- effects at chosen tests (blmm_bulkscan_effects) ---------------------------------------------------------------------------
+def _effects_checks(method: str, n: int, p: int, k, ncov: int, addIntercept: bool):
+    """The library's refusals of blmm_bulkscan_effects that need no data (blmm_api.hip: effects_check), before any context."""
+    if method not in _METHODS:
+        raise BulkLMMError("Unknown method; choose null-exact, null-grid or alt-grid.", -5)
+    k = int(k)
+    if k < 1 or p % k != 0:
+        raise BulkLMMError("bulkscan_effects: the number of columns of G must be a multiple of k >= 1", -2)
+    if method == "alt-grid":
+        raise BulkLMMError("bulkscan_effects: alt-grid is not supported; use null-grid or null-exact", -10)
+    if k > L.BLMM_EFFECTS_MAX_K:
+        raise BulkLMMError("bulkscan_effects: takes 1 <= k <= %d" % L.BLMM_EFFECTS_MAX_K, -10)
+    if _null_covariates(ncov, addIntercept) > L.BLMM_MULTIDF_MAX_COVARIATES:
+        raise BulkLMMError("bulkscan_effects: more than 8 null covariates (incl. intercept) are not supported", -10)
+    _check_n(n)
+    return k
+
+
+def _effects_tests(locus, trait, nloci: int, m: int):
+    """The test lists as flat int64 arrays of one length with every index in range (BLMM_ERR_INVALID otherwise)."""
+    loc = np.ascontiguousarray(np.asarray(locus, dtype=np.int64).ravel())
+    tr = np.ascontiguousarray(np.asarray(trait, dtype=np.int64).ravel())
+    if loc.shape[0] != tr.shape[0]:
+        raise BulkLMMError("bulkscan_effects: locus and trait must have the same length", -1)
+    if loc.size and (loc.min() < 0 or loc.max() >= nloci or tr.min() < 0 or tr.max() >= m):
+        raise BulkLMMError("bulkscan_effects: a locus or trait index is out of range", -1)
+    return loc, tr
+
+
+def bulkscan_effects(Y, G, K, Covar=None, *, k: int = 1, locus=None, trait=None, method: str = "null-grid", h2_grid=None,
+                     addIntercept: bool = True, weights=None, prior_variance: float = 1.0, prior_sample_size: float = 0.0,
+                     reml: bool = False, optim_interval: int = 1, decomp_scheme: str = "eigen", ctx: Optional[Context] = None,
+                     return_status: bool = False) -> dict:
+    """Coefficients and standard errors at chosen tests (blmm_bulkscan_effects; the reference's scan_null fits them per marker and
+    keeps only the rss).  G is n x (P k), locus l the columns l k .. l k + k - 1 (k = 1: the ordinary marker test); test t is
+    (locus[t], trait[t]), 0-based, in any order, repeats allowed.  Per test: `beta` and `se` (T x k) of the locus columns in the
+    weighted least-squares fit wls(y0_j, [Z0 X0_l], w) under the trait's null h2 (a column the rank rule of bulkscan_multidf drops has
+    beta = se = 0), `sigma2` (wls's sigma2_e of that fit: (rss1 + prior) / (n + prior_df), n - (c + accepted columns) under reml),
+    `lod` (what bulkscan / bulkscan_multidf writes at L[locus, trait]) and `accepted` (int32 bit mask of the columns kept).
+    `h2_null_list` is bulkscan's, bit for bit.  Every other argument is bulkscan's; alt-grid is refused, k <= 8, at most 8 null
+    covariates.  With locus and trait both omitted (k = 1 only) the matching bulkscan_reduced runs first and the tests are every
+    trait's peak: locus = its argmax, trait = 0 .. m - 1 (both are returned).  LOCO: call once per chromosome with calcKinship_loco's
+    kinship of that chromosome and its tests.
+    Returns {"beta", "se", "sigma2", "lod", "accepted", "h2_null_list", "locus", "trait" [, "status"]}."""
+    Y, G, K, n, m, p = _host_arrays(Y, G, K)
+    cov, ncov, w, addIntercept = _host_covariates(Covar, weights, n, addIntercept)
+    k = _effects_checks(method, n, p, k, ncov, addIntercept)
+    if (locus is None) != (trait is None):
+        raise BulkLMMError("bulkscan_effects: give both locus and trait, or neither (every trait's peak, k = 1)", -1)
+    if locus is None:
+        if k != 1:
+            raise BulkLMMError("bulkscan_effects: locus and trait are required for k > 1 (there is no reduced k-df scan)", -1)
+        peaks = bulkscan_reduced(Y, G, K, Covar, method=method, h2_grid=h2_grid, addIntercept=addIntercept, weights=weights,
+                                 prior_variance=prior_variance, prior_sample_size=prior_sample_size, reml=reml,
+                                 optim_interval=optim_interval, decomp_scheme=decomp_scheme, ctx=ctx)
+        locus, trait = np.maximum(peaks["argmax"], 0), np.arange(m)   # (-1: a trait without a finite LOD -- its marker 0 then)
+    loc, tr = _effects_tests(locus, trait, p // k, m)
+    T = loc.shape[0]
+    meth = _METHODS[method]
+    grid, ngrid = _grid(meth, h2_grid)
+    o = _opts(meth, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
+    ctx = ctx or default_context()  # after the argument checks: those must not need a GPU
+    beta, se = np.empty((T, k)), np.empty((T, k))
+    sigma2, lod, acc, h2 = np.empty(T), np.empty(T), np.empty(T, dtype=np.int32), np.empty(m)
+    st = L.blmm_status()
+    ctx.check(ctx.lib.blmm_bulkscan_effects(ctx.h, C.byref(o), _p(Y), n, m, _p(G), p, k, _p(cov), ncov, _p(K), _p(w), _p(grid), ngrid,
+                                            _p(loc), _p(tr), T, _p(beta), _p(se), _p(sigma2), _p(lod), _p(acc), _p(h2), C.byref(st)))
+    _raise_status(st)
+    out = {"beta": beta, "se": se, "sigma2": sigma2, "lod": lod, "accepted": acc, "h2_null_list": h2, "locus": loc, "trait": tr}
+    if return_status:
+        out["status"] = st
+    return out
+
+
+def bulkscan_effects_dev(ctx: Context, Y, G, K, k: int, locus, trait, beta_out, se_out, sigma2_out, lod_out, accepted_out, h2_out, *,
+                         method: str = "null-grid", h2_grid=None, Covar=None, weights=None, addIntercept: bool = True,
+                         prior_variance: float = 1.0, prior_sample_size: float = 0.0, reml: bool = False, optim_interval: int = 1,
+                         decomp_scheme: str = "eigen", status: bool = False):
+    """blmm_bulkscan_effects_dev on torch tensors in bulkscan_dev's layout: Y (m, n), G (p, n) with p = P k, K (n, n); locus, trait
+    (T,) int64; beta_out, se_out (T, k) contiguous float64; sigma2_out, lod_out (T,) float64; accepted_out (T,) int32; h2_out (m).
+    Enqueues on the context's stream; synchronises only for `status`.  The indices are on the device and not inspected here: a test
+    out of range gets NaN / accepted = -1 and, with `status`, the call raises."""
+    m, n = Y.shape
+    p = G.shape[0]
+    ncov, addIntercept, st = _dev_args(Covar, addIntercept, status)
+    k = _effects_checks(method, n, p, k, ncov, addIntercept)
+    T = locus.shape[0]
+    if trait.shape[0] != T:
+        raise BulkLMMError("bulkscan_effects: locus and trait must have the same length", -1)
+    if tuple(beta_out.shape) != (T, k) or tuple(se_out.shape) != (T, k) or not beta_out.is_contiguous() or not se_out.is_contiguous():
+        raise ValueError("beta_out and se_out must be contiguous (T, k) tensors")
+    meth = _METHODS[method]
+    grid, ngrid = _grid(meth, h2_grid)
+    o = _opts(meth, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
+    ctx.check(ctx.lib.blmm_bulkscan_effects_dev(ctx.h, C.byref(o), Y.data_ptr(), n, m, G.data_ptr(), p, k, _dptr(Covar), ncov,
+                                                K.data_ptr(), _dptr(weights), _p(grid), ngrid, locus.data_ptr(), trait.data_ptr(), T,
+                                                beta_out.data_ptr(), se_out.data_ptr(), sigma2_out.data_ptr(), lod_out.data_ptr(),
+                                                accepted_out.data_ptr(), h2_out.data_ptr(), C.byref(st) if status else None))
+    return st

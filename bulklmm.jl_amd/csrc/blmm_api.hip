@@ -857,7 +857,8 @@ void blmm_destroy(blmm_ctx* ctx) {
                     &ctx->tmpA, &ctx->tmpB, &ctx->tmpC, &ctx->perm, &ctx->r0, &ctx->altbuf, &ctx->logtab, &ctx->lraw,
                     &ctx->wbQ, &ctx->wbW, &ctx->wbRk, &ctx->lrT, &ctx->lrC, &ctx->lrL, &ctx->lrFlag, &ctx->lrPart, &ctx->lrPerm, &ctx->lrDen0, &ctx->eigW, &ctx->xf32, &ctx->pf32, &ctx->brSt, &ctx->brList, &ctx->illList, &ctx->qrSlab, &ctx->lodtab, &ctx->dynFac, &ctx->pvtab, &ctx->outP, &ctx->redbuf, &ctx->redtrip, &ctx->altC, &ctx->rf32, &ctx->btG, &ctx->redflag, &ctx->bperm,
                     &ctx->locoK, &ctx->locoPart, &ctx->locoChr, &ctx->locoStat, &ctx->locoKs, &ctx->locoV, &ctx->locoLraw,
-                    &ctx->locoCmx, &ctx->locoCarg, &ctx->locoPerm, &ctx->mdfR, &ctx->mdfT};
+                    &ctx->locoCmx, &ctx->locoCarg, &ctx->locoPerm, &ctx->mdfR, &ctx->mdfT,
+                    &ctx->effX, &ctx->effIdx, &ctx->effWork, &ctx->effOut, &ctx->effSlab};
   for (DevBuf* b : bufs) if (b->p) hipFree(b->p);
   for (auto& s : ctx->evsets) for (auto& e : s.e) (void)hipEventDestroy(e);
   if (ctx->side) { (void)hipStreamSynchronize(ctx->side); (void)hipStreamDestroy(ctx->side); }
@@ -3016,6 +3017,145 @@ int blmm_bulkscan_multidf(blmm_ctx* ctx, const blmm_opts* opts, const double* Y,
                              nloci > 0 ? nloci : 1, ptr<double>(ctx->outH2), status, pvreq))) return rc;
   set_last(ctx, ptr<double>(ctx->outL), nloci, m);
   if (L_out && (size_t)nloci * m > 0 && (rc = copy_to_host(ctx, L_out, ctx->outL.p, sizeof(double) * (size_t)nloci * m))) return rc;
+  if (m > 0 && (rc = copy_to_host(ctx, h2_out, ctx->outH2.p, sizeof(double) * (size_t)m))) return rc;
+  if ((rc = hc.finish())) return rc;
+  return check_sticky(ctx);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Coefficients and standard errors at a list of tests (include/bulklmm_hip.h: blmm_bulkscan_effects; kernels_effects.hip).  The
+// refusals that need no device come first, in the same order in the host and the device forms (multidf_check's, with k up to
+// BLMM_EFFECTS_MAX_K for both methods).
+static int effects_check(blmm_ctx* ctx, const blmm_opts* opts, int64_t n, int64_t m, int64_t p, int64_t k, const double* Covar,
+                         int64_t ncov, int64_t T) {
+  int rc = check_opts(ctx, opts);
+  if (rc) return rc;
+  if (n < 1 || m < 0 || p < 0 || ncov < 0 || T < 0 || p > 0x7fffffffLL || m > 0x7ffffff0LL || T > 0x7fffffffLL)
+    return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
+  if (k < 1 || p % k != 0) return fail(ctx, BLMM_ERR_DIM, "bulkscan_effects: the number of columns of G must be a multiple of k >= 1");
+  if ((rc = check_method(ctx, opts))) return rc;
+  if (opts->method == BLMM_ALT_GRID) return fail(ctx, BLMM_ERR_UNSUPPORTED, "bulkscan_effects: alt-grid is not supported; use null-grid or null-exact");
+  if (k > BLMM_EFFECTS_MAX_K) return fail(ctx, BLMM_ERR_UNSUPPORTED, "bulkscan_effects: takes 1 <= k <= " + std::to_string(BLMM_EFFECTS_MAX_K));
+  if (null_cov(opts, Covar, ncov).c > BLMM_MULTIDF_MAX_COVARIATES)
+    return fail(ctx, BLMM_ERR_UNSUPPORTED, "bulkscan_effects: more than 8 null covariates (incl. intercept) are not supported");
+  if (n > 2048) return fail(ctx, BLMM_ERR_UNSUPPORTED, "more than 2048 individuals: the device eigensolver (tridiagonalisation + divide and conquer) stops at n = 2048");
+  return BLMM_OK;
+}
+
+static int effects_dev_impl(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG, int64_t p,
+                            int64_t k, const double* dCovar, int64_t ncov, const double* dK, const double* dweights,
+                            const double* h2_grid_host, int64_t ngrid, const int64_t* dlocus, const int64_t* dtrait, int64_t T,
+                            double* dbeta, double* dse, double* dsigma2, double* dlod, int32_t* dacc, double* dh2_out,
+                            blmm_status* status) {
+  int rc = effects_check(ctx, opts, n, m, p, k, dCovar, ncov, T);
+  if (rc) return rc;
+  const int64_t nloci = p / k;
+  if (!dY || !dG || !dK || !dh2_out || (T > 0 && (!dlocus || !dtrait || !dbeta || !dse || !dsigma2 || !dlod || !dacc)))
+    return fail(ctx, BLMM_ERR_INVALID, "bulkscan_effects: NULL buffer");
+  const bool exact = opts->method == BLMM_NULL_EXACT;
+  if ((rc = enter_device(ctx))) return rc;
+  Timer tm(ctx);
+  Pipe P;
+  double* dgrid = nullptr;
+  if (!exact && (rc = grid_to_device(ctx, h2_grid_host, ngrid, &dgrid))) return rc;
+  // blmm_bulkscan's design, eigen phase and trait rotation (the null model is its own, bit for bit), as blmm_bulkscan_multidf
+  const bool g_in_flight = ctx->up_pending || ctx->in_wait;
+  if ((rc = prepare(ctx, opts, dY, n, m, dG, p, dCovar, ncov, dK, dweights, 1, P, tm, false, false, /*skip_markers*/ true))) return rc;
+  if (g_in_flight) BLMM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_in, 0));
+  const NullModel nm = null_model(P, opts);
+  if (m == 0) { tm.mark(); tm.mark(); tm.mark(); return end_call(ctx, P, status, &tm); }
+  if (exact) {
+    if ((rc = launch_brent(ctx, nm, P.Yt, P.ldy, m, P.Z0, P.lam, dh2_out, nullptr, nullptr, P.stat))) return rc;
+  } else {
+    if ((rc = ensure(ctx, ctx->h2idx, sizeof(int) * (size_t)m))) return rc;
+    if ((rc = launch_loglik_grid(ctx, nm, P.Yt, P.ldy, m, P.Z0, P.lam, dgrid, (int)ngrid, nullptr, ptr<int>(ctx->h2idx), dh2_out, P.stat))) return rc;
+  }
+  tm.mark();
+  if (T == 0 || nloci == 0) {   // (nloci == 0 with T > 0: every index is out of range; the host form has refused it)
+    tm.mark(); tm.mark();
+    if (T > 0) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_effects: a locus index is out of range (G has no columns)");
+    return end_call(ctx, P, status, &tm);
+  }
+  // the uncentred rotation of every marker (blmm_bulkscan_multidf's), then column-major: a test's k columns are k n contiguous doubles
+  if ((rc = ensure(ctx, ctx->mdfR, sizeof(double) * (size_t)P.npad * P.ldr)) ||
+      (rc = ensure(ctx, ctx->Xt, sizeof(double) * (size_t)P.npad * P.ldx)) ||
+      (rc = ensure(ctx, ctx->effX, sizeof(double) * (size_t)P.n * (size_t)p)) ||
+      (rc = ensure(ctx, ctx->effWork, sizeof(int) * (size_t)(m + 2 + T)))) return rc;
+  if ((rc = launch_mdf_rawrot(ctx, ptr<double>(ctx->U), dweights, P.n, P.npad, P.ldr, ptr<double>(ctx->mdfR)))) return rc;
+  P.Xt = ptr<double>(ctx->Xt);
+  if ((rc = launch_rotate(ctx, ptr<double>(ctx->mdfR), P.ldr, P.n, P.npad, dG, p, P.Xt, P.ldx, P.ldx))) return rc;
+  if ((rc = launch_untranspose(ctx, P.Xt, P.ldx, P.n, p, ptr<double>(ctx->effX)))) return rc;
+  EffArgs a;
+  a.n = P.n; a.c = P.c; a.k = (int)k; a.m = m; a.nloci = nloci; a.T = T;
+  a.Xc = ptr<double>(ctx->effX); a.Yt = P.Yt; a.ldy = P.ldy; a.Z0 = P.Z0; a.lam = P.lam; a.h2 = dh2_out;
+  a.locus = dlocus; a.trait = dtrait; a.cnt = ptr<int>(ctx->effWork); a.order = a.cnt + (m + 2);
+  a.reml = nm.reml; a.prior_a = nm.prior_a; a.prior_b = nm.prior_b;
+  a.beta = dbeta; a.se = dse; a.sigma2 = dsigma2; a.lod = dlod; a.accepted = dacc; a.stat = P.stat;
+  a.slab = nullptr; a.chunk = 1;
+  if ((rc = launch_effects_sort(ctx, a))) return rc;
+  tm.mark();
+  if ((rc = launch_effects(ctx, a))) return rc;
+  tm.mark();
+  if ((rc = end_call(ctx, P, status, &tm))) return rc;
+  if (status) {   // the stream has been synchronised: tests out of range (their outputs are NaN / accepted = -1) are an error
+    int bad = 0;
+    BLMM_HIP(hipMemcpy(&bad, a.cnt + m + 1, sizeof(int), hipMemcpyDeviceToHost));
+    if (bad) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_effects: " + std::to_string(bad) + " test(s) with a locus or trait index out of range");
+  }
+  return BLMM_OK;
+}
+
+int blmm_bulkscan_effects_dev(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG,
+                              int64_t p, int64_t k, const double* dCovar, int64_t ncov, const double* dK, const double* dweights,
+                              const double* h2_grid, int64_t ngrid, const int64_t* dlocus, const int64_t* dtrait, int64_t ntests,
+                              double* dbeta_out, double* dse_out, double* dsigma2_out, double* dlod_out, int32_t* daccepted_out,
+                              double* dh2_out, blmm_status* status) {
+  if (!ctx) return BLMM_ERR_INVALID;
+  (void)pv_take(ctx);   // a pending -log10 p request does not apply to this call: disarmed, as by every entry point
+  ctx->red_cur = RedArgs();
+  return effects_dev_impl(ctx, opts, dY, n, m, dG, p, k, dCovar, ncov, dK, dweights, h2_grid, ngrid, dlocus, dtrait, ntests, dbeta_out,
+                          dse_out, dsigma2_out, dlod_out, daccepted_out, dh2_out, status);
+}
+
+int blmm_bulkscan_effects(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, int64_t n, int64_t m, const double* G, int64_t p,
+                          int64_t k, const double* Covar, int64_t ncov, const double* K, const double* weights,
+                          const double* h2_grid, int64_t ngrid, const int64_t* locus, const int64_t* trait, int64_t ntests,
+                          double* beta_out, double* se_out, double* sigma2_out, double* lod_out, int32_t* accepted_out,
+                          double* h2_out, blmm_status* status) {
+  if (!ctx) return BLMM_ERR_INVALID;
+  (void)pv_take(ctx);
+  const int64_t T = ntests;
+  int rc = effects_check(ctx, opts, n, m, p, k, Covar, ncov, T);
+  if (rc) return rc;
+  if (!Y || !G || !K || !h2_out || (T > 0 && (!locus || !trait || !beta_out || !se_out || !sigma2_out || !lod_out || !accepted_out)))
+    return fail(ctx, BLMM_ERR_INVALID, "bulkscan_effects: NULL buffer");
+  const int64_t nloci = p / k;
+  for (int64_t t = 0; t < T; ++t)
+    if (locus[t] < 0 || locus[t] >= nloci || trait[t] < 0 || trait[t] >= m)
+      return fail(ctx, BLMM_ERR_INVALID, "bulkscan_effects: test " + std::to_string((long long)t) + " has a locus or trait index out of range");
+  HostCall hc(ctx);
+  const size_t Tn = (size_t)(T > 0 ? T : 1);
+  // outputs in one block: beta, se (T k each), sigma2, lod (T each), accepted (T int32)
+  if ((rc = hc.begin()) || (rc = ensure(ctx, ctx->effOut, sizeof(double) * Tn * (size_t)(2 * k + 2) + sizeof(int32_t) * Tn)) ||
+      (rc = ensure(ctx, ctx->effIdx, sizeof(int64_t) * 2 * Tn)) || (rc = ensure(ctx, ctx->outH2, sizeof(double) * (size_t)(m > 0 ? m : 1))))
+    return rc;
+  int64_t* dloc = ptr<int64_t>(ctx->effIdx);
+  int64_t* dtr = dloc + Tn;
+  if (T > 0 && ((rc = hc.up(dloc, locus, sizeof(int64_t) * (size_t)T)) || (rc = hc.up(dtr, trait, sizeof(int64_t) * (size_t)T)))) return rc;
+  HostCall::In d;
+  if ((rc = hc.inputs(Y, n, m, G, p, K, Covar, ncov, weights, /*defer*/ true, &d))) return rc;
+  ctx->red_cur = RedArgs();
+  double* dbeta = ptr<double>(ctx->effOut);
+  double* dse = dbeta + Tn * (size_t)k;
+  double* dsig = dse + Tn * (size_t)k;
+  double* dlod = dsig + Tn;
+  int32_t* dacc = reinterpret_cast<int32_t*>(dlod + Tn);
+  if ((rc = effects_dev_impl(ctx, opts, d.Y, n, m, d.G, p, k, d.Cov, d.ncov, d.K, d.W, h2_grid, ngrid, dloc, dtr, T, dbeta, dse, dsig, dlod,
+                             dacc, ptr<double>(ctx->outH2), status))) return rc;
+  if (T > 0 && m > 0 &&
+      ((rc = copy_to_host(ctx, beta_out, dbeta, sizeof(double) * (size_t)T * k)) || (rc = copy_to_host(ctx, se_out, dse, sizeof(double) * (size_t)T * k)) ||
+       (rc = copy_to_host(ctx, sigma2_out, dsig, sizeof(double) * (size_t)T)) || (rc = copy_to_host(ctx, lod_out, dlod, sizeof(double) * (size_t)T)) ||
+       (rc = copy_to_host(ctx, accepted_out, dacc, sizeof(int32_t) * (size_t)T)))) return rc;
   if (m > 0 && (rc = copy_to_host(ctx, h2_out, ctx->outH2.p, sizeof(double) * (size_t)m))) return rc;
   if ((rc = hc.finish())) return rc;
   return check_sticky(ctx);

@@ -111,7 +111,9 @@ struct blmm_ctx {
       locoK, locoPart, locoChr, locoStat, locoKs, locoV, locoLraw,   // blmm_kinship_loco / blmm_bulkscan_loco (kernels_loco.hip)
       locoCmx, locoCarg,   // blmm_bulkscan_loco_reduced: the per-chromosome maxima / arg-maxima when the caller's tables are not on the device
       locoPerm,            // blmm_bulkscan_loco_perms: the genome-wide (nperms + 1) x m column maxima and their global markers
-      mdfR, mdfT;          // blmm_bulkscan_multidf: the uncentred rotation and the null-grid factor table (kernels_mdf.hip)
+      mdfR, mdfT,          // blmm_bulkscan_multidf: the uncentred rotation and the null-grid factor table (kernels_mdf.hip)
+      effX, effIdx, effWork, effOut, effSlab;   // blmm_bulkscan_effects (kernels_effects.hip): the rotated markers column-major, the host form's
+                                                // test lists, the sort's counters + permutation, the host form's outputs, the waves' slab
   // event sets: one per timed call since the last blmm_read_timings (grown on demand, reused afterwards)
   struct EvSet { hipEvent_t e[8]; int n; };
   std::vector<EvSet> evsets;
@@ -505,6 +507,22 @@ int launch_mdf_scan(blmm_ctx* ctx, const MdfArgs& a, bool exact);
 int launch_mdf_qr(blmm_ctx* ctx, const NullModel& nm, const double* Yt, int64_t ldy, const double* Xt, int64_t ldx, int64_t nloci, int k,
                   const double* Z0, const double* lam, const double* h2, const int* list, double* L, int64_t ldL, int64_t* stat);
    // k_bperm_summary sorts a trait's maxima in LDS (128 KB)
+
+// kernels_effects.hip: blmm_bulkscan_effects, coefficients and standard errors at a list of (locus, trait) tests
+struct EffArgs {
+  int n, c, k; int64_t m, nloci, T;
+  const double* Xc;                    // rotated markers (uncentred), COLUMN-major: column i of G at Xc + i n
+  const double* Yt; int64_t ldy;       // rotated traits, row-major
+  const double *Z0, *lam, *h2;         // rotated covariates (column-major n x c), eigenvalues, each trait's null h2
+  const int64_t *locus, *trait;        // the T tests
+  int* cnt; int* order;                // the sort: m + 2 counters (offsets; [m] valid tests, [m + 1] tests out of range), sorted position -> test
+  int reml; double prior_a, prior_b;
+  double *beta, *se, *sigma2, *lod; int32_t* accepted;
+  int64_t* stat;
+  double* slab; int chunk;             // set by launch_effects
+};
+int launch_effects_sort(blmm_ctx* ctx, const EffArgs& a);
+int launch_effects(blmm_ctx* ctx, EffArgs a);
 
 }  // namespace blmm
 

@@ -11,7 +11,7 @@
 # every `ccall`'s symbol, return type and argument tuple (arity and types) against the prototype in include/bulklmm_hip.h.
 module BulkLMMHIP
 
-export bulkscan_multidf, calcKinship_loco, bulkscan_loco, bulkscan_loco_reduced, bulkscan_loco_perms, bulkscan_perms, bulkscan_reduced, bulkscan_reduced_async!, synchronize, DeviceLOD, lod_columns, set_tuning, calcKinship, bulkscan, bulkscan_null, bulkscan_null_grid, bulkscan_alt_grid, bulkscan_alt_exact, scan, bulkscan_multi, lod2log10p, get_thresholds,
+export bulkscan_effects, bulkscan_multidf, calcKinship_loco, bulkscan_loco, bulkscan_loco_reduced, bulkscan_loco_perms, bulkscan_perms, bulkscan_reduced, bulkscan_reduced_async!, synchronize, DeviceLOD, lod_columns, set_tuning, calcKinship, bulkscan, bulkscan_null, bulkscan_null_grid, bulkscan_alt_grid, bulkscan_alt_exact, scan, bulkscan_multi, lod2log10p, get_thresholds,
        lod_threshold, lod_colmax, pinned_matrix, host_register, host_unregister
 
 const libblmm = get(ENV, "BULKLMM_HIP_LIB", joinpath(@__DIR__, "..", "csrc", "libbulklmm_hip.so"))
@@ -401,6 +401,49 @@ function bulkscan_multidf(Y::Array{Float64, 2}, G::Array{Float64, 2}, Covar::Arr
         return merge(res, (log10Pvals_mat = _last_log10p((P, m), chisq_df), Chisq_df = chisq_df))
     end
     return res
+end
+
+# ---- effects at chosen tests (blmm_bulkscan_effects): coefficients and standard errors of the locus columns in the weighted
+# least-squares fit wls(y0_j, [Z0 X0_l], w) under trait j's null h2, for tests (locus[t], trait[t]) -- 1-based here -- in any order.
+# beta, se: k x T (column t = test t; a column the rank rule drops has 0 in both); sigma2 (wls's sigma2_e of the fit), lod (what
+# bulkscan / bulkscan_multidf has at L[locus, trait]), accepted (bit mask of the columns kept): T.  k <= 8 for both methods, at most
+# 8 null covariates, alt-grid is refused.  LOCO: call once per chromosome with calcKinship_loco's kinship of it and its tests.
+function bulkscan_effects(Y::Array{Float64, 2}, G::Array{Float64, 2}, K::Array{Float64, 2}, k::Integer, locus::Array{Int64, 1},
+                          trait::Array{Int64, 1}; kwargs...)
+    return bulkscan_effects(Y, G, ones(size(Y, 1), 1), K, k, locus, trait; kwargs..., addIntercept = false)
+end
+function bulkscan_effects(Y::Array{Float64, 2}, G::Array{Float64, 2}, Covar::Array{Float64, 2}, K::Array{Float64, 2}, k::Integer,
+                          locus::Array{Int64, 1}, trait::Array{Int64, 1};
+                          method::String = "null-grid", h2_grid::Array{Float64, 1} = collect(0.0:0.1:0.9), addIntercept::Bool = true,
+                          weights::Union{Missing, Array{Float64, 1}} = missing, prior_variance::Float64 = 1.0,
+                          prior_sample_size::Float64 = 0.0, reml::Bool = false, optim_interval::Int64 = 1,
+                          decomp_scheme::String = "eigen")
+    (n, m) = size(Y); p = size(G, 2)
+    (size(G, 1) != n || size(K, 1) != n || size(K, 2) != n || size(Covar, 1) != n) && error("Dimension mismatch.")
+    (weights !== missing && length(weights) != n) && error("Dimension mismatch.")
+    method in ("null-grid", "null-exact", "alt-grid") || error("Unknown method `$method`; choose null-exact, null-grid or alt-grid.")
+    (k < 1 || p % k != 0) && error("bulkscan_effects: the number of columns of G must be a multiple of k >= 1")
+    check_n(n)
+    T = length(locus)
+    length(trait) == T || error("bulkscan_effects: locus and trait must have the same length")
+    (all(1 .<= locus .<= div(p, k)) && all(1 .<= trait .<= m)) || error("bulkscan_effects: a locus or trait index is out of range")
+    meth = method == "null-exact" ? NULL_EXACT : method == "null-grid" ? NULL_GRID : ALT_GRID
+    o = BlmmOpts(meth, reml, addIntercept, decomp(decomp_scheme), optim_interval, 0, prior_variance, prior_sample_size)
+    loc0 = locus .- 1; tr0 = trait .- 1
+    beta = Array{Float64, 2}(undef, k, T); se = Array{Float64, 2}(undef, k, T)
+    sigma2 = Array{Float64, 1}(undef, T); lod = Array{Float64, 1}(undef, T); accepted = Array{Int32, 1}(undef, T)
+    h2 = Array{Float64, 1}(undef, m)
+    st = BlmmStatus()
+    GC.@preserve Y G Covar K weights h2_grid loc0 tr0 beta se sigma2 lod accepted h2 begin
+        check(ccall((:blmm_bulkscan_effects, libblmm), Cint,
+                    (Ptr{Cvoid}, Ref{BlmmOpts}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64,
+                     Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Float64}, Ptr{Float64},
+                     Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ref{BlmmStatus}),
+                    context(), o, Y, n, m, G, p, Int64(k), Covar, size(Covar, 2), K, ptr_or_null(weights), h2_grid,
+                    length(h2_grid), loc0, tr0, Int64(T), beta, se, sigma2, lod, accepted, h2, st))
+    end
+    raise_status(st)
+    return (beta = beta, se = se, sigma2 = sigma2, lod = lod, accepted = accepted, h2_null_list = h2)
 end
 
 # ---- the bulk form of scan(...; assumption = "alt") (scan_alt, src/scan.jl:397-453; not in the reference, which has the

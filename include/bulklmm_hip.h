@@ -562,6 +562,51 @@ int blmm_bulkscan_multidf_dev(blmm_ctx* ctx, const blmm_opts* opts, const double
                               const double* h2_grid, int64_t ngrid, double* dL_out, int64_t ldL, double* dh2_out,
                               blmm_status* status);
 
+/* ---- effects at chosen tests: coefficients and standard errors where a scan found something ------------------------------------
+ * Takes what blmm_bulkscan_multidf takes (opts: null-grid or null-exact, reml, the prior, add_intercept, optim_interval,
+ * decomp_scheme; Y n x m; G n x p with p = P k, locus l = columns l k .. l k + k - 1, k = 1: the ordinary marker test; Covar, K,
+ * weights, h2_grid) plus ntests tests as two int64 arrays, locus[t] (0-based, < P) and trait[t] (0-based, < m), in any order,
+ * repeats allowed.  The null model is blmm_bulkscan's: h2_out (m) is its h2_null_list for the same method and options, bit for bit.
+ * For test t = (l, j), with s = sqrt(|makeweights(h2_j, lambda)|), Z~ = s .* Z0, x~_a = s .* (rotated column a of locus l),
+ * y~ = s .* y0_j in the rotated space of transform_rotation, and D~ = [Z~, the ACCEPTED x~_a] -- accepted by blmm_bulkscan_multidf's
+ * rank rule (BLMM_MULTIDF_TAU, in column order):
+ *   beta_out[t k + a]   the coefficient of column a in the weighted least-squares fit of y~ on D~, i.e. wls(y0_j, [Z0 X0_l], w).b
+ *                       (src/wls.jl) restricted to the locus columns; a dropped column has beta = 0 and se = 0
+ *   se_out[t k + a]     sqrt(sigma2[t] [(D~'D~)^-1]_aa)
+ *   sigma2_out[t]       wls's sigma2_e of that fit: (rss1 + prior_variance prior_sample_size) / (n + prior_df), or
+ *                       / (n - (c + r) + prior_df) under REML, with rss1 = |y~ - D~ b|^2, c the null covariates incl. the intercept,
+ *                       r the accepted columns and prior_df = prior_sample_size + 2 when prior_sample_size > 0, else prior_sample_size
+ *                       (src/wls.jl:72-77).  A caller who wants the unbiased rss1 / (n - c - r) rescales: without a prior,
+ *                       rss1 = sigma2 n under ML, and se scales with sqrt(sigma2).
+ *   lod_out[t]          -(n/2) log10(rss1 / rss0), rss0 the null fit's: the number blmm_bulkscan (k = 1) or blmm_bulkscan_multidf
+ *                       writes at L[l, j] (rss1 = 0: +Inf; NaN is counted in n_nan_lod)
+ *   accepted_out[t]     int32 bit mask of the accepted columns (bit a = column a)
+ * Limits: 1 <= k <= BLMM_EFFECTS_MAX_K for BOTH methods (null-exact too: blmm_bulkscan_multidf's BLMM_MULTIDF_MAX_K_EXACT is not
+ * this call's), at most BLMM_MULTIDF_MAX_COVARIATES null covariates (incl. the intercept) for every k -- k = 1 included, where
+ * blmm_bulkscan itself takes 32 --, n <= 2048, ntests < 2^31.  Refused before anything is uploaded: k < 1 or p not a multiple of k
+ * (BLMM_ERR_DIM); k above the limit, more covariates, alt-grid, n > 2048 (BLMM_ERR_UNSUPPORTED); an unknown method
+ * (BLMM_ERR_METHOD); a locus or trait index out of range (BLMM_ERR_INVALID).  A pending blmm_set_log10p_output request is dropped.
+ * LOCO: there is no leave-one-chromosome-out form; call once per chromosome with that chromosome's kinship (blmm_kinship_loco)
+ * and its tests.
+ * Kernels (kernels_effects.hip): the tests are ordered by trait on the device (counting sort); one wave takes a chunk of the
+ * sorted list, builds what depends on the trait only (s, an orthonormal basis of span(Z~) by Gram-Schmidt with
+ * re-orthogonalisation, the null residual) once per run, and for each test orthogonalises the locus's k weighted columns
+ * explicitly (no normal equations) and back-substitutes.
+ * The _dev form: device Y / G / Covar / weights / locus / trait and outputs; it enqueues on the context's stream and waits only for
+ * a status or to copy the host h2_grid.  It cannot refuse an index it has not seen: a test out of range gets NaN in beta, se,
+ * sigma2, lod and accepted = -1, touches no memory, and makes the call return BLMM_ERR_INVALID when a status is asked for. */
+#define BLMM_EFFECTS_MAX_K 8
+int blmm_bulkscan_effects(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, int64_t n, int64_t m, const double* G, int64_t p,
+                          int64_t k, const double* Covar, int64_t ncov, const double* K, const double* weights,
+                          const double* h2_grid, int64_t ngrid, const int64_t* locus, const int64_t* trait, int64_t ntests,
+                          double* beta_out, double* se_out, double* sigma2_out, double* lod_out, int32_t* accepted_out,
+                          double* h2_out, blmm_status* status);
+int blmm_bulkscan_effects_dev(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG,
+                              int64_t p, int64_t k, const double* dCovar, int64_t ncov, const double* dK, const double* dweights,
+                              const double* h2_grid, int64_t ngrid, const int64_t* dlocus, const int64_t* dtrait, int64_t ntests,
+                              double* dbeta_out, double* dse_out, double* dsigma2_out, double* dlod_out, int32_t* daccepted_out,
+                              double* dh2_out, blmm_status* status);
+
 /* ---- scan(y, G, [Z], K; assumption = "alt") -> scan_alt (src/scan.jl:397-453): the variance components are re-estimated for
  * every marker (fitlmm on [Z g_i], src/lmm.jl:56-86, one Brent search per marker on the device).
  * scalars_out = [sigma2_e, h2_null]; lod_out p; h2_each_out p (`h2_each_marker`).  opts->compat_flags:
