@@ -1578,3 +1578,114 @@ def bulkscan_effects_dev(ctx: Context, Y, G, K, k: int, locus, trait, beta_out, 
                                                 beta_out.data_ptr(), se_out.data_ptr(), sigma2_out.data_ptr(), lod_out.data_ptr(),
                                                 accepted_out.data_ptr(), h2_out.data_ptr(), C.byref(st) if status else None))
     return st
+
+
+# ---- the conditional scan (blmm_bulkscan_cond) -----------------------------------------------------------------------------------
+def _cond_table(cond, m: int, p: int):
+    """cond as the library takes it: (m, s) int64, C order (entry [j, a] at j s + a); indices in [-1, p)."""
+    c = np.asarray(cond)
+    if c.dtype.kind not in "iu":
+        raise BulkLMMError("bulkscan_cond: cond must hold integer column indices of G (or -1), or be \"peak\"", -1)
+    if c.ndim == 1:
+        c = c.reshape(-1, 1)
+    if c.ndim != 2 or c.shape[0] != m:
+        raise BulkLMMError("bulkscan_cond: cond must have shape (m,) or (m, s)", -2)
+    return np.ascontiguousarray(c, dtype=np.int64)
+
+
+def _cond_checks(method: str, n: int, s: int, ncov: int, addIntercept: bool):
+    """The library's refusals of blmm_bulkscan_cond that need no data (blmm_api.hip: cond_check), before any context."""
+    if method not in _METHODS:
+        raise BulkLMMError("Unknown method; choose null-exact, null-grid or alt-grid.", -5)
+    if method == "alt-grid":
+        raise BulkLMMError("bulkscan_cond: alt-grid is not supported; use null-grid or null-exact", -10)
+    if s > L.BLMM_COND_MAX_LOCI:
+        raise BulkLMMError("bulkscan_cond: at most 4 conditioning loci per trait", -10)
+    c = _null_covariates(ncov, addIntercept)
+    if c + s > L.BLMM_MULTIDF_MAX_COVARIATES:
+        raise BulkLMMError("bulkscan_cond: more than 8 null-design columns (covariates incl. intercept + conditioning loci) are not supported", -10)
+    _check_n(n)
+    if c + s >= n:
+        raise BulkLMMError("Dimension mismatch.", -2)
+
+
+def _cond_indices(c: np.ndarray, p: int):
+    bad = np.nonzero(((c < -1) | (c >= p)).any(axis=1))[0]
+    if bad.size:
+        raise BulkLMMError("bulkscan_cond: trait %d has a conditioning index outside [-1, p)" % int(bad[0]), -1)
+
+
+def bulkscan_cond(Y, G, K, cond, Covar=None, *, method: str = "null-grid", h2_grid=None, addIntercept: bool = True, weights=None,
+                  prior_variance: float = 1.0, prior_sample_size: float = 0.0, reml: bool = False, optim_interval: int = 1,
+                  decomp_scheme: str = "eigen", output_pvals: bool = False, chisq_df: int = 1, keep_on_device: bool = False,
+                  return_status: bool = False, ctx: Optional[Context] = None) -> dict:
+    """bulkscan of every trait CONDITIONAL on its own loci (blmm_bulkscan_cond): column j of L is the scan of trait j with the null
+    design [Covar, G[:, cond[j]]] -- secondary QTL given the peak, forward selection.  `cond`: (m,) or (m, s) integer column indices
+    of G (0-based), -1 for none, s <= 4; or the string "peak": bulkscan_reduced runs first with the same method and options and
+    every trait is conditioned on its arg-max marker.  Conditioning columns that add nothing beyond the covariates and the trait's
+    earlier ones (repeats, constants) are dropped; markers collinear with a trait's design (the conditioning marker itself, its
+    duplicates) get LOD +0.0.  h2_null_list is the null model WITH the conditioning loci.
+    Returns {"L": p x m (DeviceLOD when keep_on_device), "h2_null_list": m, "cond": (m, s) as used, "n_rule_zero", "n_cond_dropped",
+    "n_cond_traits" [, "log10Pvals_mat", "Chisq_df"] [, "status"]}."""
+    Y, G, K, n, m, p = _host_arrays(Y, G, K)
+    cov, ncov, w, addIntercept = _host_covariates(Covar, weights, n, addIntercept)
+    peak = isinstance(cond, str)
+    if peak and cond != "peak":
+        raise BulkLMMError("bulkscan_cond: cond is an index array or the string \"peak\"", -1)
+    ctab = None if peak else _cond_table(cond, m, p)
+    s = 1 if peak else ctab.shape[1]
+    _cond_checks(method, n, s, ncov, addIntercept)
+    if not peak:
+        _cond_indices(ctab, p)
+    if output_pvals and not 1 <= int(chisq_df) <= 1000000:
+        raise BulkLMMError("chisq_df must lie in 1 .. 10^6", -1)
+    meth = _METHODS[method]
+    grid, ngrid = _grid(meth, h2_grid)
+    o = _opts(meth, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
+    ctx = ctx or default_context()  # after the argument checks: those must not need a GPU
+    if peak:
+        red = bulkscan_reduced(Y, G, K, Covar, method=method, h2_grid=h2_grid, addIntercept=addIntercept, weights=weights,
+                               prior_variance=prior_variance, prior_sample_size=prior_sample_size, reml=reml,
+                               optim_interval=optim_interval, decomp_scheme=decomp_scheme, ctx=ctx)
+        ctab = np.ascontiguousarray(np.asarray(red["argmax"], dtype=np.int64).reshape(m, 1))
+    Lout = None if keep_on_device else np.empty((p, m), dtype=np.float64, order="F")
+    h2 = np.empty(m, dtype=np.float64)
+    info = np.zeros(L.BLMM_COND_INFO_LEN, dtype=np.int64)
+    st = L.blmm_status()
+    with _log10p_output(ctx, int(chisq_df) if output_pvals else None):
+        ctx.check(ctx.lib.blmm_bulkscan_cond(ctx.h, C.byref(o), _p(Y), n, m, _p(G), p, _p(cov), ncov, _p(K), _p(w), _p(grid), ngrid,
+                                             _p(ctab) if s > 0 else None, s, _p(Lout), _p(h2), _p(info), C.byref(st)))
+    _raise_status(st)
+    out = {"L": DeviceLOD(ctx, p, m) if keep_on_device else Lout, "h2_null_list": h2, "cond": ctab,
+           "n_rule_zero": int(info[0]), "n_cond_dropped": int(info[1]), "n_cond_traits": int(info[2])}
+    if output_pvals:
+        out["log10Pvals_mat"] = _last_log10p(ctx, (p, m), int(chisq_df))
+        out["Chisq_df"] = int(chisq_df)
+    if return_status:
+        out["status"] = st
+    return out
+
+
+def bulkscan_cond_dev(ctx: Context, Y, G, K, cond, L_out, h2_out, *, cinfo_out=None, method: str = "null-grid", h2_grid=None,
+                      Covar=None, weights=None, addIntercept: bool = True, prior_variance: float = 1.0,
+                      prior_sample_size: float = 0.0, reml: bool = False, optim_interval: int = 1, decomp_scheme: str = "eigen",
+                      status: bool = False, log10p_out=None, chisq_df: int = 1):
+    """blmm_bulkscan_cond_dev on torch tensors in bulkscan_dev's layout: Y (m, n), G (p, n), K (n, n), cond (m, s) int64 contiguous (or
+    None), L_out (m, p) (= p x m column-major; rows may be padded), h2_out (m), cinfo_out (4) int64 or None.  The indices are not
+    looked at on the host: a trait with one outside [-1, p) gets NaNs, and the call raises when `status` is asked for.  Enqueues on
+    the context's stream; synchronises only for `status`."""
+    m, n = Y.shape
+    p = G.shape[0]
+    ncov, addIntercept, st = _dev_args(Covar, addIntercept, status)
+    s = 0 if cond is None else int(cond.shape[1])
+    if cond is not None and (cond.dim() != 2 or cond.shape[0] != m or not cond.is_contiguous() or cond.element_size() != 8):
+        raise BulkLMMError("bulkscan_cond: cond must be a contiguous (m, s) int64 tensor", -2)
+    _cond_checks(method, n, s, ncov, addIntercept)
+    meth = _METHODS[method]
+    grid, ngrid = _grid(meth, h2_grid)
+    o = _opts(meth, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
+    with _log10p_output(ctx, None if log10p_out is None else chisq_df, log10p_out, p):
+        ctx.check(ctx.lib.blmm_bulkscan_cond_dev(ctx.h, C.byref(o), Y.data_ptr(), n, m, G.data_ptr(), p, _dptr(Covar), ncov, K.data_ptr(),
+                                                 _dptr(weights), _p(grid), ngrid, _dptr(cond) if s > 0 else None, s, L_out.data_ptr(),
+                                                 _ld(L_out, p), h2_out.data_ptr(), _dptr(cinfo_out), C.byref(st) if status else None))
+    return st

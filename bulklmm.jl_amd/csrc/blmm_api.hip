@@ -858,7 +858,7 @@ void blmm_destroy(blmm_ctx* ctx) {
                     &ctx->wbQ, &ctx->wbW, &ctx->wbRk, &ctx->lrT, &ctx->lrC, &ctx->lrL, &ctx->lrFlag, &ctx->lrPart, &ctx->lrPerm, &ctx->lrDen0, &ctx->eigW, &ctx->xf32, &ctx->pf32, &ctx->brSt, &ctx->brList, &ctx->illList, &ctx->qrSlab, &ctx->lodtab, &ctx->dynFac, &ctx->pvtab, &ctx->outP, &ctx->redbuf, &ctx->redtrip, &ctx->altC, &ctx->rf32, &ctx->btG, &ctx->redflag, &ctx->bperm,
                     &ctx->locoK, &ctx->locoPart, &ctx->locoChr, &ctx->locoStat, &ctx->locoKs, &ctx->locoV, &ctx->locoLraw,
                     &ctx->locoCmx, &ctx->locoCarg, &ctx->locoPerm, &ctx->mdfR, &ctx->mdfT,
-                    &ctx->effX, &ctx->effIdx, &ctx->effWork, &ctx->effOut, &ctx->effSlab};
+                    &ctx->effX, &ctx->effIdx, &ctx->effWork, &ctx->effOut, &ctx->effSlab, &ctx->condIdx, &ctx->condWork};
   for (DevBuf* b : bufs) if (b->p) hipFree(b->p);
   for (auto& s : ctx->evsets) for (auto& e : s.e) (void)hipEventDestroy(e);
   if (ctx->side) { (void)hipStreamSynchronize(ctx->side); (void)hipStreamDestroy(ctx->side); }
@@ -3018,6 +3018,141 @@ int blmm_bulkscan_multidf(blmm_ctx* ctx, const blmm_opts* opts, const double* Y,
   set_last(ctx, ptr<double>(ctx->outL), nloci, m);
   if (L_out && (size_t)nloci * m > 0 && (rc = copy_to_host(ctx, L_out, ctx->outL.p, sizeof(double) * (size_t)nloci * m))) return rc;
   if (m > 0 && (rc = copy_to_host(ctx, h2_out, ctx->outH2.p, sizeof(double) * (size_t)m))) return rc;
+  if ((rc = hc.finish())) return rc;
+  return check_sticky(ctx);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The conditional scan (include/bulklmm_hip.h: blmm_bulkscan_cond; kernels_cond.hip).  Every refusal that needs no device comes
+// first, in the same order in the host and the device forms.
+static int cond_check(blmm_ctx* ctx, const blmm_opts* opts, int64_t n, int64_t m, int64_t p, int64_t s, const double* Covar, int64_t ncov) {
+  int rc = check_opts(ctx, opts);
+  if (rc) return rc;
+  if (n < 1 || m < 0 || p < 0 || ncov < 0 || s < 0 || p > 0x7fffffffLL || m > 0x7fffffffLL) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
+  if ((rc = check_method(ctx, opts))) return rc;
+  if (opts->method == BLMM_ALT_GRID) return fail(ctx, BLMM_ERR_UNSUPPORTED, "bulkscan_cond: alt-grid is not supported; use null-grid or null-exact");
+  if (s > BLMM_COND_MAX_LOCI) return fail(ctx, BLMM_ERR_UNSUPPORTED, "bulkscan_cond: at most 4 conditioning loci per trait");
+  const int64_t c = null_cov(opts, Covar, ncov).c;
+  if (c + s > BLMM_MULTIDF_MAX_COVARIATES)
+    return fail(ctx, BLMM_ERR_UNSUPPORTED, "bulkscan_cond: more than 8 null-design columns (covariates incl. intercept + conditioning loci) are not supported");
+  if (n > 2048) return fail(ctx, BLMM_ERR_UNSUPPORTED, "more than 2048 individuals: the device eigensolver (tridiagonalisation + divide and conquer) stops at n = 2048");
+  if (c + s >= n) return fail(ctx, BLMM_ERR_DIM, "Dimension mismatch.");
+  return BLMM_OK;
+}
+
+static int cond_dev_impl(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG, int64_t p,
+                         const double* dCovar, int64_t ncov, const double* dK, const double* dweights, const double* h2_grid_host,
+                         int64_t ngrid, const int64_t* dcond, int64_t s, double* dL_out, int64_t ldL, double* dh2_out,
+                         int64_t* dcinfo_out, blmm_status* status, const PvReq& pvreq) {
+  if (!dcond) s = 0;
+  int rc = cond_check(ctx, opts, n, m, p, s, dCovar, ncov);
+  if (rc) return rc;
+  if (!dY || !dG || !dK || !dL_out || !dh2_out) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_cond: NULL buffer");
+  if (ldL < p) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_cond: ldL < p");
+  const bool exact = opts->method == BLMM_NULL_EXACT;
+  if ((rc = enter_device(ctx))) return rc;
+  Timer tm(ctx);
+  Pipe P;
+  double* dgrid = nullptr;
+  if (!exact && (rc = grid_to_device(ctx, h2_grid_host, ngrid, &dgrid))) return rc;
+  // blmm_bulkscan's design, eigen phase and trait rotation; the markers are rotated below without the centring projection (the
+  // rank rule compares against the norm of the rotated column itself), as blmm_bulkscan_multidf does
+  const bool g_in_flight = ctx->up_pending || ctx->in_wait;
+  if ((rc = prepare(ctx, opts, dY, n, m, dG, p, dCovar, ncov, dK, dweights, 1, P, tm, false, false, /*skip_markers*/ true))) return rc;
+  if (g_in_flight) BLMM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_in, 0));
+  const NullModel nm = null_model(P, opts);
+  PvCall pvc(ctx, pvreq);
+  if ((rc = pvc.resolve(p, m))) return rc;
+  // work area: the info counters, then per trait the kept columns (s), r_j and the guard's flag
+  const size_t mm = (size_t)(m > 0 ? m : 1);
+  if ((rc = ensure(ctx, ctx->condWork, sizeof(int64_t) * COND_NINFO + sizeof(int) * mm * (size_t)(s + 2)))) return rc;
+  int64_t* info = ptr<int64_t>(ctx->condWork);
+  BLMM_HIP(hipMemsetAsync(info, 0, sizeof(int64_t) * COND_NINFO, ctx->stream));
+  auto finish = [&]() -> int {
+    if (dcinfo_out) BLMM_HIP(hipMemcpyAsync(dcinfo_out, info, sizeof(int64_t) * BLMM_COND_INFO_LEN, hipMemcpyDeviceToDevice, ctx->stream));
+    int rc2 = end_call(ctx, P, status, &tm);
+    if (rc2 || !status) return rc2;
+    int64_t bad = 0;   // the stream has been synchronised
+    BLMM_HIP(hipMemcpy(&bad, info + 4, sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (bad) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_cond: " + std::to_string((long long)bad) + " trait(s) with a conditioning index outside [-1, p)");
+    return BLMM_OK;
+  };
+  if (m == 0) { tm.mark(); tm.mark(); tm.mark(); return finish(); }
+  CondArgs a;
+  a.n = P.n; a.c = P.c; a.s = (int)s; a.npad = P.npad; a.m = m; a.p = p;
+  a.Xt = nullptr; a.ldx = P.ldx; a.Yt = P.Yt; a.ldy = P.ldy; a.Z0 = P.Z0; a.lam = P.lam; a.cond = dcond;
+  a.kept = reinterpret_cast<int*>(info + COND_NINFO); a.nk = a.kept + mm * (size_t)s; a.flag = a.nk + mm;
+  a.info = info; a.h2 = dh2_out; a.stat = P.stat;
+  if (p > 0) {
+    if ((rc = ensure(ctx, ctx->mdfR, sizeof(double) * (size_t)P.npad * P.ldr)) ||
+        (rc = ensure(ctx, ctx->Xt, sizeof(double) * (size_t)P.npad * P.ldx))) return rc;
+    if ((rc = launch_mdf_rawrot(ctx, ptr<double>(ctx->U), dweights, P.n, P.npad, P.ldr, ptr<double>(ctx->mdfR)))) return rc;
+    P.Xt = ptr<double>(ctx->Xt);
+    if ((rc = launch_rotate(ctx, ptr<double>(ctx->mdfR), P.ldr, P.n, P.npad, dG, p, P.Xt, P.ldx, P.ldx))) return rc;
+    a.Xt = P.Xt;
+  }
+  if ((rc = launch_cond_null(ctx, nm, a, exact ? nullptr : dgrid, (int)ngrid))) return rc;
+  tm.mark();
+  if (p == 0) { tm.mark(); tm.mark(); return finish(); }
+  const int ct = P.c + (int)s;
+  const int64_t ldp = P.ldy;
+  if ((rc = ensure(ctx, ctx->panels, sizeof(double) * (size_t)(2 + ct) * P.npad * ldp)) ||
+      (rc = ensure(ctx, ctx->illList, sizeof(int) * mm))) return rc;
+  if ((rc = launch_cond_panels(ctx, nm, a, ptr<double>(ctx->panels), ldp, ctx->tune.illcond_rho, ptr<int>(ctx->illList)))) return rc;
+  tm.mark();
+  ScanArgs sa = scan_args(ctx, P, ptr<double>(ctx->panels), ldp, dL_out, ldL, m);
+  sa.c = ct; sa.Pv = nullptr; sa.red = RedArgs(); sa.cflag = a.flag; sa.cinfo = info;
+  if ((rc = launch_scan_cond(ctx, sa, ct))) return rc;
+  if ((rc = launch_cond_qr(ctx, nm, a, ptr<int>(ctx->illList), dL_out, ldL))) return rc;
+  tm.mark();
+  if ((rc = pvc.finish(p, m, dL_out, ldL))) return rc;
+  return finish();
+}
+
+int blmm_bulkscan_cond_dev(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG, int64_t p,
+                           const double* dCovar, int64_t ncov, const double* dK, const double* dweights, const double* h2_grid,
+                           int64_t ngrid, const int64_t* dcond, int64_t s, double* dL_out, int64_t ldL, double* dh2_out,
+                           int64_t* dcinfo_out, blmm_status* status) {
+  if (!ctx) return BLMM_ERR_INVALID;
+  const PvReq pvreq = pv_take(ctx);
+  ctx->red_cur = RedArgs();
+  return cond_dev_impl(ctx, opts, dY, n, m, dG, p, dCovar, ncov, dK, dweights, h2_grid, ngrid, dcond, s, dL_out, ldL, dh2_out, dcinfo_out,
+                       status, pvreq);
+}
+
+// L_out == NULL: L (p x m) stays resident for the blmm_last_* consumers, as blmm_bulkscan
+int blmm_bulkscan_cond(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, int64_t n, int64_t m, const double* G, int64_t p,
+                       const double* Covar, int64_t ncov, const double* K, const double* weights, const double* h2_grid,
+                       int64_t ngrid, const int64_t* cond, int64_t s, double* L_out, double* h2_out, int64_t* cinfo_out,
+                       blmm_status* status) {
+  if (!ctx) return BLMM_ERR_INVALID;
+  const PvReq pvreq = pv_take(ctx);
+  if (!cond) s = 0;
+  int rc = cond_check(ctx, opts, n, m, p, s, Covar, ncov);
+  if (rc) return rc;
+  if (!Y || !G || !K || !h2_out) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_cond: NULL buffer");
+  for (int64_t e = 0; e < s * m; ++e)
+    if (cond[e] < -1 || cond[e] >= p)
+      return fail(ctx, BLMM_ERR_INVALID, "bulkscan_cond: trait " + std::to_string((long long)(e / s)) + " has a conditioning index outside [-1, p)");
+  HostCall hc(ctx);
+  const size_t mm = (size_t)(m > 0 ? m : 1);
+  if ((rc = hc.begin()) || (rc = ensure(ctx, ctx->outL, sizeof(double) * (size_t)(p > 0 ? p : 1) * mm)) ||
+      (rc = ensure(ctx, ctx->outH2, sizeof(double) * mm)))
+    return rc;
+  const int64_t* dcond = nullptr;
+  if (s > 0 && m > 0) {
+    if ((rc = hc.up(ctx->condIdx, cond, sizeof(int64_t) * (size_t)s * (size_t)m))) return rc;
+    dcond = ptr<int64_t>(ctx->condIdx);
+  } else s = 0;
+  HostCall::In d;
+  if ((rc = hc.inputs(Y, n, m, G, p, K, Covar, ncov, weights, /*defer*/ true, &d))) return rc;
+  ctx->red_cur = RedArgs();
+  if ((rc = cond_dev_impl(ctx, opts, d.Y, n, m, d.G, p, d.Cov, d.ncov, d.K, d.W, h2_grid, ngrid, dcond, s, ptr<double>(ctx->outL),
+                          p > 0 ? p : 1, ptr<double>(ctx->outH2), nullptr, status, pvreq))) return rc;
+  set_last(ctx, ptr<double>(ctx->outL), p, m);
+  if (L_out && (size_t)p * m > 0 && (rc = copy_to_host(ctx, L_out, ctx->outL.p, sizeof(double) * (size_t)p * m))) return rc;
+  if (m > 0 && (rc = copy_to_host(ctx, h2_out, ctx->outH2.p, sizeof(double) * (size_t)m))) return rc;
+  if ((rc = hc.down(cinfo_out, ctx->condWork.p, sizeof(int64_t) * BLMM_COND_INFO_LEN))) return rc;
   if ((rc = hc.finish())) return rc;
   return check_sticky(ctx);
 }

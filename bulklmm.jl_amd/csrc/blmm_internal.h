@@ -112,6 +112,7 @@ struct blmm_ctx {
       locoCmx, locoCarg,   // blmm_bulkscan_loco_reduced: the per-chromosome maxima / arg-maxima when the caller's tables are not on the device
       locoPerm,            // blmm_bulkscan_loco_perms: the genome-wide (nperms + 1) x m column maxima and their global markers
       mdfR, mdfT,          // blmm_bulkscan_multidf: the uncentred rotation and the null-grid factor table (kernels_mdf.hip)
+      condIdx, condWork,   // blmm_bulkscan_cond (kernels_cond.hip): the host form's index table; kept columns, counts, guard flags, info counters
       effX, effIdx, effWork, effOut, effSlab;   // blmm_bulkscan_effects (kernels_effects.hip): the rotated markers column-major, the host form's
                                                 // test lists, the sort's counters + permutation, the host form's outputs, the waves' slab
   // event sets: one per timed call since the last blmm_read_timings (grown on demand, reused afterwards)
@@ -348,6 +349,9 @@ struct ScanArgs {
   // column pass over the finished L (launch_lod2log10p / launch_pv_list).
   double* Pv = nullptr; int64_t ldPv = 0; const double* pvtab = nullptr;
   RedArgs red;                             // red.pmax != nullptr: the reduce-in-epilogue instantiation runs and L is not touched
+  // launch_scan_cond (blmm_bulkscan_cond): per-trait flag (1: the conditioning guard re-scans the trait, its NaNs and rule hits are
+  // counted there) and the call's info counters ([0]: entries the rank rule set to 0)
+  const int* cflag = nullptr; int64_t* cinfo = nullptr;
 };
 // kernels_post.hip: threshold triplets of a resident L; the second pass of the reduce-in-epilogue scan (RedArgs partials -> per trait)
 int launch_threshold(blmm_ctx* ctx, const double* dL, int64_t p, int64_t m, int64_t ldL, double thr, int64_t cap,
@@ -366,6 +370,7 @@ int launch_red_final_loco(blmm_ctx* ctx, const double* pmax, const int* parg, in
 // flagged a trait, else 1.  Also raises the context's sticky word on a device-side failure (as k_sticky).
 int launch_red_info(blmm_ctx* ctx, const int64_t* stat, int route, const int64_t* count, int64_t* info);
 int launch_scan_exact(blmm_ctx* ctx, const ScanArgs& a, int c);
+int launch_scan_cond(blmm_ctx* ctx, const ScanArgs& a, int ct);   // a.c = ct = covariates + conditioning loci, uncentred markers
 // A region of the panel arrays of the low-rank form: columns [col0, col0 + ncol), the shared-weights class at its front
 // (counts[0] traits) and the other class at its back (counts[1]); counts live on the device.
 constexpr int LR_TILE = 64;   // a multiple of every trait-tile width of k_scan_lr (32 * MB); regions are multiples of it
@@ -507,6 +512,27 @@ int launch_mdf_scan(blmm_ctx* ctx, const MdfArgs& a, bool exact);
 int launch_mdf_qr(blmm_ctx* ctx, const NullModel& nm, const double* Yt, int64_t ldy, const double* Xt, int64_t ldx, int64_t nloci, int k,
                   const double* Z0, const double* lam, const double* h2, const int* list, double* L, int64_t ldL, int64_t* stat);
    // k_bperm_summary sorts a trait's maxima in LDS (128 KB)
+
+// kernels_cond.hip: blmm_bulkscan_cond, every trait scanned with its own conditioning loci in the null design
+constexpr int COND_NINFO = 8;          // device counters: [0 .. BLMM_COND_INFO_LEN) the caller's info block, [4] traits with an index out of range
+struct CondArgs {
+  int n, c, s, npad; int64_t m, p;
+  const double* Xt; int64_t ldx;       // rotated markers (uncentred: k_mdf_rawrot), npad x ldx row-major
+  const double* Yt; int64_t ldy;       // rotated traits, row-major
+  const double *Z0, *lam;
+  const int64_t* cond;                 // s x m: cond[j s + a] = trait j's a-th conditioning column of G, -1: none
+  int* kept;                           // [m][s]: the columns step 1 keeps, in order (-1 beyond r_j)
+  int* nk;                             // r_j; -1: an index outside [-1, p) (NaN column, NaN h2)
+  int* flag;                           // 1: listed for k_cond_qr
+  int64_t* info;                       // COND_NINFO counters
+  double* h2;
+  int64_t* stat;
+};
+// step 1 and the null model on D_j = [Z0, kept columns]: fitlmm (grid_dev == nullptr) or the first arg-max over the grid
+int launch_cond_null(blmm_ctx* ctx, const NullModel& nm, const CondArgs& a, const double* grid_dev, int ngrid);
+// k_panels' layout with 2 + c + s panels per trait (zero panels beyond 1 + c + r_j); flags the traits of the conditioning guard
+int launch_cond_panels(blmm_ctx* ctx, const NullModel& nm, const CondArgs& a, double* panels, int64_t ldp, double rho_min, int* list);
+int launch_cond_qr(blmm_ctx* ctx, const NullModel& nm, const CondArgs& a, const int* list, double* L, int64_t ldL);
 
 // kernels_effects.hip: blmm_bulkscan_effects, coefficients and standard errors at a list of (locus, trait) tests
 struct EffArgs {

@@ -1,0 +1,540 @@
+// kernels_cond.hip -- blmm_bulkscan_cond: every trait scanned with its OWN conditioning loci in the null design.
+//
+// Trait j's null design is D_j = [Z0, the kept columns among x0_{cond[j, 0]}, .., x0_{cond[j, s - 1]}] (rotated, uncentred: k_mdf_rawrot),
+// c + r_j <= CT = c + s <= 8 columns.  The kernels are templates over CT; a trait with fewer columns runs them with `ct` live columns,
+// the dead ones being zero columns whose Cholesky pivot is replaced by 1 (they then contribute nothing anywhere).
+//
+//   k_cond_null    one wave per trait.  Step 1: the unweighted Gram of [Z0, the trait's valid columns] factored with multidf's rank
+//                  rule (column a kept iff its pivot, the squared norm of the part orthogonal to Z0 and the kept columns before it,
+//                  exceeds MDF_TAU |x0_a|^2) -> kept[], r_j.  Then the null model on D_j: fitlmm (the scalar Brent of brent_scalar.h
+//                  on -ell, src/lmm.jl:56-86) or the first arg-max of ell over the grid (src/wls.jl:27-97 per point); the 64 lanes
+//                  split the individuals, the (c + r_j)(c + r_j + 1)/2 + c + r_j + 2 sums are wave reductions, the factorisation
+//                  is closed form in registers.  A trait with r_j = 0 gets bulkscan's null model through the same code.
+//   k_cond_panels  one thread per trait (coalesced panel rows, as k_panels): panel 0 = w .* residual / |.|, panel 1 = w,
+//                  panels 2 .. 1 + ct = w .* (D_j L^-T)_q, zero panels up to 1 + CT.  Also the conditioning guard's criterion
+//                  (k_illcond_flag's: the smallest pivot share of D_j'WD_j below rho_min) -> flag[], list, stat[ST_ILLCOND].
+//   the scan       k_scan<.., COND> (kernels_scan.hip): the f64-MFMA contraction with 2 + CT accumulators and the rank-rule epilogue.
+//   k_cond_qr      the listed traits again with an orthonormal basis of span(sqrt(W) D_j) (Gram-Schmidt twice) and explicit
+//                  residuals, the rank rule on the explicit norms (k_scan_qr's / k_mdf_qr's method).
+#include "blmm_internal.h"
+#include "fastmath.h"
+#include "brent_scalar.h"
+#include <cmath>
+
+namespace blmm {
+
+#define KCHECK()                                                                                      \
+  do {                                                                                                \
+    hipError_t e__ = hipGetLastError();                                                               \
+    if (e__ != hipSuccess) return fail(ctx, BLMM_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e__)); \
+  } while (0)
+
+// ---- the sums of one evaluation, wave-wide: A = D'WD (packed lower), v = D'Wy, y'Wy, sum ln(delta lambda + 1) ---------------------
+template <int CT>
+struct CondSums { double A[CT * (CT + 1) / 2], v[CT], syy, logsum; int bad; };
+
+// column q of the design at individual k: Z0's for q < c, the trait's staged conditioning column q - c for q < ct, else 0
+template <int CT>
+__device__ __forceinline__ void cond_row(double (&z)[CT], int k, int n, int c, int ct, const double* __restrict__ Z0, const double* sX) {
+#pragma unroll
+  for (int q = 0; q < CT; ++q) z[q] = (q < c) ? Z0[(size_t)q * n + k] : (q < ct ? sX[(size_t)(q - c) * n + k] : 0.0);
+}
+
+// unit: weights 1 (step 1's Gram); otherwise w = 1 / (delta lambda + 1) as the likelihood uses it (src/wls.jl:40)
+template <int CT>
+__device__ __forceinline__ void cond_sums(CondSums<CT>& S, bool unit, double h2, int n, int c, int ct, const double* __restrict__ Z0,
+                                          const double* __restrict__ lam, const double* sY, const double* sX) {
+  constexpr int NA = CT * (CT + 1) / 2;
+  const int lane = threadIdx.x & 63;
+  const double delta = h2 / (1.0 - h2);
+#pragma unroll
+  for (int a = 0; a < NA; ++a) S.A[a] = 0.0;
+#pragma unroll
+  for (int q = 0; q < CT; ++q) S.v[q] = 0.0;
+  S.syy = 0.0; S.logsum = 0.0; S.bad = 0;
+  for (int k = lane; k < n; k += 64) {
+    double w = 1.0;
+    if (!unit) {
+      const double t = fma(delta, lam[k], 1.0);
+      w = 1.0 / t;
+      S.bad |= !(w > 0.0);
+      S.logsum += log(t);
+    }
+    double z[CT];
+    cond_row<CT>(z, k, n, c, ct, Z0, sX);
+    const double y = sY[k], wy = w * y;
+    S.syy = fma(wy, y, S.syy);
+#pragma unroll
+    for (int q = 0; q < CT; ++q) {
+      S.v[q] = fma(wy, z[q], S.v[q]);
+      const double wz = w * z[q];
+#pragma unroll
+      for (int r = 0; r <= q; ++r) S.A[q * (q + 1) / 2 + r] = fma(wz, z[r], S.A[q * (q + 1) / 2 + r]);
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < NA; ++a) S.A[a] = group_sum<64>(S.A[a]);
+#pragma unroll
+  for (int q = 0; q < CT; ++q) S.v[q] = group_sum<64>(S.v[q]);
+  S.syy = group_sum<64>(S.syy); S.logsum = group_sum<64>(S.logsum);
+  S.bad = __any(S.bad) ? 1 : 0;
+}
+
+// ell of wls(y0_j, D_j, w, prior; reml) from the sums (null_ell's formula, kernels_prep.hip; REML's p is ct)
+template <int CT>
+__device__ __forceinline__ double cond_ell(const CondSums<CT>& S, int n, int ct, double prior_a, double prior_b, int reml) {
+  constexpr int NA = CT * (CT + 1) / 2;
+  double L[NA], t[CT], logdet = 0.0, tt = 0.0;
+#pragma unroll
+  for (int q = 0; q < CT; ++q) {
+    const bool live = q < ct;
+#pragma unroll
+    for (int r = 0; r <= q; ++r) {
+      double s = S.A[q * (q + 1) / 2 + r];
+#pragma unroll
+      for (int u = 0; u < r; ++u) s = fma(-L[q * (q + 1) / 2 + u], L[r * (r + 1) / 2 + u], s);
+      if (r == q) { L[q * (q + 1) / 2 + q] = live ? sqrt(s) : 1.0; logdet += live ? log(s) : 0.0; }
+      else L[q * (q + 1) / 2 + r] = live ? s / L[r * (r + 1) / 2 + r] : 0.0;
+    }
+    double s = S.v[q];
+#pragma unroll
+    for (int u = 0; u < q; ++u) s = fma(-L[q * (q + 1) / 2 + u], t[u], s);
+    t[q] = live ? s / L[q * (q + 1) / 2 + q] : 0.0;
+    tt = fma(t[q], t[q], tt);
+  }
+  const double rss = S.syy - tt;
+  const double prior_df = prior_b > 0.0 ? prior_b + 2.0 : prior_b;
+  const double num = rss + prior_a * prior_b;
+  const double sigma2 = num / ((reml ? (double)(n - ct) : (double)n) + prior_df);
+  const double ls = log(sigma2);
+  double ell = -0.5 * (((double)n + prior_b) * ls + S.logsum + num / sigma2);
+  if (reml) ell += 0.5 * ((double)ct * ls - logdet);
+  return ell;
+}
+
+constexpr int COND_SMAX = BLMM_COND_MAX_LOCI;
+
+// LDS: sY (n), sX (s n)
+template <int CT>
+__global__ void __launch_bounds__(64) k_cond_null(NullModel nm, CondArgs a, const double* __restrict__ grid, int ngrid) {
+  constexpr int NA = CT * (CT + 1) / 2;
+  extern __shared__ __attribute__((aligned(16))) double sh[];
+  const int n = a.n, c = a.c, s = a.s, lane = threadIdx.x;
+  double* sY = sh;
+  double* sX = sh + n;
+  const int64_t j = blockIdx.x;
+  // the trait's entries: valid ones in order; an index outside [-1, p) makes the whole trait NaN
+  int idx[COND_SMAX], nv = 0;
+  bool invalid = false;
+#pragma unroll
+  for (int e = 0; e < COND_SMAX; ++e) {
+    idx[e] = -1;
+    if (e < s) {
+      const int64_t q = a.cond[j * s + e];
+      if (q < -1 || q >= a.p) invalid = true;
+      else if (q >= 0) {
+#pragma unroll
+        for (int f = 0; f < COND_SMAX; ++f) if (f == nv) idx[f] = (int)q;
+        ++nv;
+      }
+    }
+  }
+  if (invalid) {
+    if (lane == 0) {
+      a.nk[j] = -1; a.flag[j] = 0; a.h2[j] = NAN;
+      for (int e = 0; e < s; ++e) a.kept[j * s + e] = -1;
+      atomicAdd((unsigned long long*)&a.info[4], 1ull);
+    }
+    return;
+  }
+  for (int k = lane; k < n; k += 64) {
+    sY[k] = a.Yt[(int64_t)k * a.ldy + j];
+#pragma unroll
+    for (int e = 0; e < COND_SMAX; ++e)
+      if (e < nv) sX[(size_t)e * n + k] = a.Xt[(int64_t)k * a.ldx + idx[e]];
+  }
+  __syncthreads();
+  CondSums<CT> S;
+  // ---- step 1: unweighted, in order ------------------------------------------------------------------------------------------
+  int r = 0;
+  if (nv > 0) {
+    cond_sums<CT>(S, true, 0.0, n, c, c + nv, a.Z0, a.lam, sY, sX);
+    double L[NA];
+    unsigned keepmask = 0;
+#pragma unroll
+    for (int q = 0; q < CT; ++q) {
+#pragma unroll
+      for (int u = 0; u <= q; ++u) {
+        double t = S.A[q * (q + 1) / 2 + u];
+#pragma unroll
+        for (int v = 0; v < u; ++v) t = fma(-L[q * (q + 1) / 2 + v], L[u * (u + 1) / 2 + v], t);
+        if (u == q) {
+          const bool keep = (q < c) ? true : (q < c + nv && t > MDF_TAU * S.A[q * (q + 1) / 2 + q]);
+          L[q * (q + 1) / 2 + q] = keep ? sqrt(t) : 0.0;
+          if (keep && q >= c) keepmask |= 1u << (q - c);
+        } else {
+          const double luu = L[u * (u + 1) / 2 + u];
+          L[q * (q + 1) / 2 + u] = (luu > 0.0) ? t / luu : 0.0;
+        }
+      }
+    }
+    // compact the kept columns to the front of sX (a column only ever moves to a lower slot; ascending order keeps sources intact)
+    int kidx[COND_SMAX];
+#pragma unroll
+    for (int e = 0; e < COND_SMAX; ++e) kidx[e] = -1;
+#pragma unroll
+    for (int e = 0; e < COND_SMAX; ++e) {
+      if (e < nv && ((keepmask >> e) & 1u)) {
+        if (r != e)
+          for (int k = lane; k < n; k += 64) sX[(size_t)r * n + k] = sX[(size_t)e * n + k];
+#pragma unroll
+        for (int f = 0; f < COND_SMAX; ++f) if (f == r) kidx[f] = idx[e];
+        ++r;
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < COND_SMAX; ++e) idx[e] = kidx[e];
+    __syncthreads();
+  }
+  if (lane == 0) {
+    a.nk[j] = r;
+#pragma unroll
+    for (int e = 0; e < COND_SMAX; ++e) if (e < s) a.kept[j * s + e] = (e < r) ? idx[e] : -1;
+    if (nv > r) atomicAdd((unsigned long long*)&a.info[1], (unsigned long long)(nv - r));
+    if (r >= 1) atomicAdd((unsigned long long*)&a.info[2], 1ull);
+  }
+  // ---- the null model on D_j ---------------------------------------------------------------------------------------------------
+  const int ct = c + r;
+  int nonpos = 0, hit_max = 0;
+  double best;
+  if (grid) {
+    int bi = 0;
+    double bv = -INFINITY;
+    for (int g = 0; g < ngrid; ++g) {
+      cond_sums<CT>(S, false, grid[g], n, c, ct, a.Z0, a.lam, sY, sX);
+      nonpos |= S.bad;
+      const double e = cond_ell<CT>(S, n, ct, nm.prior_a, nm.prior_b, nm.reml);
+      if (g == 0 || e > bv) { bv = e; bi = g; }
+    }
+    best = grid[bi];
+  } else {
+    auto f = [&](double h2) {
+      cond_sums<CT>(S, false, h2, n, c, ct, a.Z0, a.lam, sY, sX);
+      nonpos |= S.bad;
+      return -cond_ell<CT>(S, n, ct, nm.prior_a, nm.prior_b, nm.reml);
+    };
+    best = dyn_brent_search(f, nm.optim_interval < 1 ? 1 : nm.optim_interval, &hit_max);
+    wave_count(&a.stat[ST_H2_BOUNDARY], lane == 0 && h2_on_boundary(best));
+  }
+  if (lane == 0) {
+    a.h2[j] = best;
+    if (hit_max) atomicAdd((unsigned long long*)&a.stat[ST_BRENT_MAXIT], 1ull);
+    if (nonpos) atomicAdd((unsigned long long*)&a.stat[ST_NONPOS_W], 1ull);
+  }
+}
+
+// ---- panels: k_panels (kernels_prep.hip) on the per-trait design; LDS: lam (n), Z0 (n c) ------------------------------------------------
+template <int CT>
+__global__ void __launch_bounds__(256) k_cond_panels(NullModel nm, CondArgs a, double* __restrict__ P, int64_t ldp, double rho_min,
+                                                     int* __restrict__ list) {
+  constexpr int NA = CT * (CT + 1) / 2;
+  extern __shared__ __attribute__((aligned(16))) double sh[];
+  const int n = a.n, npad = a.npad, c = a.c, s = a.s;
+  double* sLam = sh;
+  double* sZ = sh + n;
+  for (int e = threadIdx.x; e < n; e += blockDim.x) sLam[e] = a.lam[e];
+  for (int e = threadIdx.x; e < n * c; e += blockDim.x) sZ[e] = a.Z0[e];
+  __syncthreads();
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= ldp) return;
+  const int64_t pstride = (int64_t)npad * ldp;
+  constexpr int NPAN = 2 + CT;
+  const int rj = j < a.m ? a.nk[j] : 0;
+  if (j >= a.m || rj < 0) {   // padding columns: zero; a trait with an index out of range: NaN numerators, unit weights
+    const double p0 = (j < a.m) ? NAN : 0.0, p1 = (j < a.m) ? 1.0 : 0.0;
+    for (int k = 0; k < npad; ++k) {
+      P[(int64_t)k * ldp + j] = k < n ? p0 : 0.0;
+      P[pstride + (int64_t)k * ldp + j] = k < n ? p1 : 0.0;
+      for (int q = 2; q < NPAN; ++q) P[q * pstride + (int64_t)k * ldp + j] = 0.0;
+    }
+    return;
+  }
+  const int ct = c + rj;
+  int kc[COND_SMAX];
+#pragma unroll
+  for (int e = 0; e < COND_SMAX; ++e) kc[e] = (e < rj && e < s) ? a.kept[j * s + e] : 0;
+  auto row = [&](double (&z)[CT], int k) {
+#pragma unroll
+    for (int q = 0; q < CT; ++q) {
+      double v = 0.0;
+      if (q < c) v = sZ[q * n + k];
+      else if (q < ct) {
+        int col = 0;
+#pragma unroll
+        for (int e = 0; e < COND_SMAX; ++e) if (e == q - c) col = kc[e];
+        v = a.Xt[(int64_t)k * a.ldx + col];
+      }
+      z[q] = v;
+    }
+  };
+  const double h2 = a.h2[j];
+  const double delta = h2 / (1.0 - h2);
+  double A[NA], v[CT], syy = 0.0;
+#pragma unroll
+  for (int e = 0; e < NA; ++e) A[e] = 0.0;
+#pragma unroll
+  for (int q = 0; q < CT; ++q) v[q] = 0.0;
+  for (int k = 0; k < n; ++k) {
+    const double w = fabs(1.0 / fma(delta, sLam[k], 1.0));
+    const double y = a.Yt[(int64_t)k * a.ldy + j];
+    const double wy = w * y;
+    syy = fma(wy, y, syy);
+    double z[CT];
+    row(z, k);
+#pragma unroll
+    for (int q = 0; q < CT; ++q) {
+      v[q] = fma(wy, z[q], v[q]);
+      const double wz = w * z[q];
+#pragma unroll
+      for (int r = 0; r <= q; ++r) A[q * (q + 1) / 2 + r] = fma(wz, z[r], A[q * (q + 1) / 2 + r]);
+    }
+  }
+  double L[NA], Li[NA], t[CT], beta[CT], tt = 0.0, rho = 1.0;
+#pragma unroll
+  for (int q = 0; q < CT; ++q) {
+    const bool live = q < ct;
+#pragma unroll
+    for (int r = 0; r <= q; ++r) {
+      double sacc = A[q * (q + 1) / 2 + r];
+#pragma unroll
+      for (int u = 0; u < r; ++u) sacc = fma(-L[q * (q + 1) / 2 + u], L[r * (r + 1) / 2 + u], sacc);
+      if (r == q) {
+        if (live) {
+          const double share = sacc / A[q * (q + 1) / 2 + q];
+          rho = (share < rho || !(share == share)) ? share : rho;   // NaN sticks (k_illcond_flag)
+        }
+        L[q * (q + 1) / 2 + q] = live ? sqrt(sacc) : 1.0;
+      } else {
+        L[q * (q + 1) / 2 + r] = live ? sacc / L[r * (r + 1) / 2 + r] : 0.0;
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < CT; ++q) {
+#pragma unroll
+    for (int r = 0; r <= q; ++r) {
+      double sacc = (r == q) ? 1.0 : 0.0;
+#pragma unroll
+      for (int u = r; u < q; ++u) sacc = fma(-L[q * (q + 1) / 2 + u], Li[u * (u + 1) / 2 + r], sacc);
+      Li[q * (q + 1) / 2 + r] = sacc / L[q * (q + 1) / 2 + q];
+    }
+    double sacc = 0.0;
+#pragma unroll
+    for (int r = 0; r <= q; ++r) sacc = fma(Li[q * (q + 1) / 2 + r], v[r], sacc);
+    t[q] = sacc;
+    tt = fma(sacc, sacc, tt);
+  }
+#pragma unroll
+  for (int q = 0; q < CT; ++q) {
+    double sacc = 0.0;
+#pragma unroll
+    for (int u = q; u < CT; ++u) sacc = fma(Li[u * (u + 1) / 2 + q], t[u], sacc);
+    beta[q] = sacc;
+  }
+  const double yy = syy - tt;
+  if (!(sqrt(fabs(yy)) > 2.220446049250313e-16)) atomicAdd((unsigned long long*)&a.stat[ST_ZERO_NORM], 1ull);
+  const double isy = 1.0 / sqrt(yy);
+  // the conditioning guard (a design of >= 2 columns): the trait goes on the list of k_cond_qr
+  int flagged = 0;
+  if (ct >= 2 && !(rho >= rho_min)) {
+    const unsigned long long slot = atomicAdd((unsigned long long*)&a.stat[ST_ILLCOND], 1ull);
+    list[slot] = (int)j;
+    flagged = 1;
+  }
+  a.flag[j] = flagged;
+  for (int k = 0; k < npad; ++k) {
+    double p0 = 0.0, w = 0.0;
+    double zl[CT];
+#pragma unroll
+    for (int q = 0; q < CT; ++q) zl[q] = 0.0;
+    if (k < n) {
+      w = fabs(1.0 / fma(delta, sLam[k], 1.0));
+      double z[CT];
+      row(z, k);
+      double res = a.Yt[(int64_t)k * a.ldy + j];
+#pragma unroll
+      for (int q = 0; q < CT; ++q) res = fma(-beta[q], z[q], res);
+      p0 = w * res * isy;
+#pragma unroll
+      for (int q = 0; q < CT; ++q) {
+        double sacc = 0.0;
+#pragma unroll
+        for (int r = 0; r <= q; ++r) sacc = fma(Li[q * (q + 1) / 2 + r], z[r], sacc);
+        zl[q] = w * sacc;
+      }
+    }
+    P[(int64_t)k * ldp + j] = p0;
+    P[pstride + (int64_t)k * ldp + j] = w;
+#pragma unroll
+    for (int q = 0; q < CT; ++q) P[(2 + q) * pstride + (int64_t)k * ldp + j] = zl[q];
+  }
+}
+
+// ---- the guard's re-scan: k_mdf_qr (kernels_mdf.hip) for one column per test on the per-trait design ----------------------------------
+__device__ __forceinline__ double cond_block_sum(double v, double* s_red /* [4] */) {
+  v = group_sum<64>(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+}
+__device__ __forceinline__ void cond_project_out(double* tgt, const double* Qb, int nq, int n, double* s_red) {
+  for (int r = 0; r < nq; ++r) {
+    double t = 0.0;
+    for (int k = threadIdx.x; k < n; k += 256) t = fma(Qb[(size_t)r * n + k], tgt[k], t);
+    t = cond_block_sum(t, s_red);
+    for (int k = threadIdx.x; k < n; k += 256) tgt[k] = fma(-t, Qb[(size_t)r * n + k], tgt[k]);
+  }
+}
+
+constexpr int COND_CT = BLMM_MULTIDF_MAX_COVARIATES;
+// One workgroup per listed trait at a time; buf: (CTmax + 2) n doubles (sqrt weights, the orthonormal basis, the unit trait residual)
+__global__ void __launch_bounds__(256) k_cond_qr(CondArgs a, int ctmax, const int* __restrict__ list, double* slab,
+                                                 double* __restrict__ L, int64_t ldL) {
+  extern __shared__ __attribute__((aligned(16))) double sh[];
+  __shared__ double s_red[4];
+  const int64_t cnt = a.stat[ST_ILLCOND];
+  if (cnt <= 0) return;
+  const int n = a.n, c = a.c, s = a.s;
+  double* buf = slab ? slab + (size_t)blockIdx.x * (size_t)(ctmax + 2) * n : sh;
+  double* Sw = buf;
+  double* Qb = buf + n;
+  double* yb = buf + (size_t)(1 + ctmax) * n;
+  const double scale = -0.5 * (double)n;
+  int nnan = 0, nrule = 0;
+  for (int64_t item = blockIdx.x; item < cnt; item += gridDim.x) {
+    const int64_t j = list[item];
+    const int ct = c + a.nk[j];
+    const double h2 = a.h2[j];
+    const double delta = h2 / (1.0 - h2);
+    __syncthreads();
+    for (int k = threadIdx.x; k < n; k += 256) {
+      const double sw = sqrt(fabs(1.0 / fma(delta, a.lam[k], 1.0)));
+      Sw[k] = sw;
+      for (int q = 0; q < c; ++q) Qb[(size_t)q * n + k] = sw * a.Z0[(size_t)q * n + k];
+      for (int q = c; q < ct; ++q) Qb[(size_t)q * n + k] = sw * a.Xt[(int64_t)k * a.ldx + a.kept[j * s + (q - c)]];
+      yb[k] = sw * a.Yt[(int64_t)k * a.ldy + j];
+    }
+    for (int q = 0; q < ct; ++q) {
+      double* col = Qb + (size_t)q * n;
+      cond_project_out(col, Qb, q, n, s_red);
+      cond_project_out(col, Qb, q, n, s_red);   // twice is enough
+      double nn = 0.0;
+      for (int k = threadIdx.x; k < n; k += 256) nn = fma(col[k], col[k], nn);
+      nn = cond_block_sum(nn, s_red);
+      const double inv = 1.0 / sqrt(nn);
+      for (int k = threadIdx.x; k < n; k += 256) col[k] *= inv;
+    }
+    cond_project_out(yb, Qb, ct, n, s_red);
+    cond_project_out(yb, Qb, ct, n, s_red);
+    {
+      double nn = 0.0;
+      for (int k = threadIdx.x; k < n; k += 256) nn = fma(yb[k], yb[k], nn);
+      nn = cond_block_sum(nn, s_red);
+      const double inv = 1.0 / sqrt(nn);
+      for (int k = threadIdx.x; k < n; k += 256) yb[k] *= inv;
+    }
+    __syncthreads();
+    for (int64_t i = threadIdx.x; i < a.p; i += 256) {
+      double t[COND_CT], t2[COND_CT];
+#pragma unroll
+      for (int q = 0; q < COND_CT; ++q) { t[q] = 0.0; t2[q] = 0.0; }
+      for (int k = 0; k < n; ++k) {
+        const double x = Sw[k] * a.Xt[(int64_t)k * a.ldx + i];
+#pragma unroll
+        for (int q = 0; q < COND_CT; ++q)
+          if (q < ct) t[q] = fma(Qb[(size_t)q * n + k], x, t[q]);
+      }
+      for (int k = 0; k < n; ++k) {                  // second projection pass on the first residual
+        double x = Sw[k] * a.Xt[(int64_t)k * a.ldx + i];
+#pragma unroll
+        for (int q = 0; q < COND_CT; ++q)
+          if (q < ct) x = fma(-t[q], Qb[(size_t)q * n + k], x);
+#pragma unroll
+        for (int q = 0; q < COND_CT; ++q)
+          if (q < ct) t2[q] = fma(Qb[(size_t)q * n + k], x, t2[q]);
+      }
+      double xx = 0.0, d0 = 0.0, num = 0.0;
+      for (int k = 0; k < n; ++k) {
+        const double x = Sw[k] * a.Xt[(int64_t)k * a.ldx + i];
+        d0 = fma(x, x, d0);
+        double v = x;
+#pragma unroll
+        for (int q = 0; q < COND_CT; ++q)
+          if (q < ct) v = fma(-(t[q] + t2[q]), Qb[(size_t)q * n + k], v);
+        xx = fma(v, v, xx);
+        num = fma(v, yb[k], num);
+      }
+      double lod;
+      if (!(xx > MDF_TAU * d0)) { lod = 0.0; ++nrule; }
+      else {
+        const double u1 = 1.0 - (num * num) / xx;
+        lod = scale * log10(u1);
+        if (!(u1 > 0.0)) { lod = (u1 == 0.0) ? INFINITY : NAN; nnan += (u1 == 0.0) ? 0 : 1; }
+      }
+      L[j * ldL + i] = lod;
+    }
+  }
+  if (nnan) atomicAdd((unsigned long long*)&a.stat[ST_NAN_LOD], (unsigned long long)nnan);
+  if (nrule) atomicAdd((unsigned long long*)&a.info[0], (unsigned long long)nrule);
+}
+
+// ---- launchers -------------------------------------------------------------------------------------------------------------------
+int launch_cond_null(blmm_ctx* ctx, const NullModel& nm, const CondArgs& a, const double* grid_dev, int ngrid) {
+  if (a.m <= 0) return BLMM_OK;
+  const size_t lds = sizeof(double) * (size_t)a.n * (1 + a.s);
+#define CN(CT) do { if (lds > 48 * 1024) BLMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cond_null<CT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+    hipLaunchKernelGGL(k_cond_null<CT>, dim3((unsigned)a.m), dim3(64), lds, ctx->stream, nm, a, grid_dev, ngrid); } while (0)
+  switch (a.c + a.s) {
+    BLMM_FOR_EACH_C(CN)
+    default: return fail(ctx, BLMM_ERR_UNSUPPORTED, "bulkscan_cond: 1 .. 8 null-design columns");
+  }
+#undef CN
+  KCHECK();
+  return BLMM_OK;
+}
+
+int launch_cond_panels(blmm_ctx* ctx, const NullModel& nm, const CondArgs& a, double* panels, int64_t ldp, double rho_min, int* list) {
+  const unsigned blocks = (unsigned)((ldp + 255) / 256);
+  const size_t lds = sizeof(double) * (size_t)a.n * (1 + a.c);
+#define CP(CT) do { if (lds > 48 * 1024) BLMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cond_panels<CT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+    hipLaunchKernelGGL(k_cond_panels<CT>, dim3(blocks), dim3(256), lds, ctx->stream, nm, a, panels, ldp, rho_min, list); } while (0)
+  switch (a.c + a.s) {
+    BLMM_FOR_EACH_C(CP)
+    default: return fail(ctx, BLMM_ERR_UNSUPPORTED, "bulkscan_cond: 1 .. 8 null-design columns");
+  }
+#undef CP
+  KCHECK();
+  return BLMM_OK;
+}
+
+int launch_cond_qr(blmm_ctx* ctx, const NullModel& nm, const CondArgs& a, const int* list, double* L, int64_t ldL) {
+  const int ctmax = a.c + a.s;
+  if (a.p <= 0 || ctmax < 2) return BLMM_OK;
+  const size_t per = (size_t)(ctmax + 2) * nm.n;
+  const unsigned grid = (unsigned)(2 * (ctx->num_cus > 0 ? ctx->num_cus : 256));
+  double* slab = nullptr;
+  size_t lds = sizeof(double) * per;
+  if (lds > 64 * 1024) {
+    int rc = ensure(ctx, ctx->qrSlab, sizeof(double) * per * grid);
+    if (rc) return rc;
+    slab = ptr<double>(ctx->qrSlab);
+    lds = 0;
+  }
+  if (lds > 48 * 1024) BLMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cond_qr), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(k_cond_qr, dim3(grid), dim3(256), lds, ctx->stream, a, ctmax, list, slab, L, ldL);
+  KCHECK();
+  return BLMM_OK;
+}
+
+}  // namespace blmm

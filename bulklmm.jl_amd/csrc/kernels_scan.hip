@@ -215,9 +215,16 @@ __device__ __forceinline__ void tile_of32(uint32_t id, uint32_t ntile_t, uint32_
 // MORE (exact mode, c > CFAST): the covariate panels beyond the first CFAST are contracted CFAST at a time ahead of the main
 // loop and folded into the Sxx accumulator as -u_q^2 (an MFMA accumulates on top of whatever its accumulator holds), so the
 // register budget does not grow with c; the marker tile is re-read from L2 once per chunk.
-template <int NX, int MB, int NB, bool TABLE, int W2, bool PERM = false, bool MORE = false, bool PV = false, bool RED = false>
+// COND (exact mode; blmm_bulkscan_cond, kernels_cond.hip): the panels 2 .. are an orthonormalised PER-TRAIT null design (the
+// covariates, then the trait's own conditioning loci; zero panels where a trait has fewer) and the markers are rotated without
+// the centring projection, so acc[1] is |x~_i|^2 itself.  The epilogue applies multidf's rank rule, |r_i|^2 <= MDF_TAU |x~_i|^2 ->
+// L = +0.0 (counted in a.cinfo[0]), and with MORE the panels beyond the first CFAST are contracted AFTER the main loop, three at
+// a time in the accumulators the in-loop panels have left (the rule needs Sxx unfolded).  Traits a.cflag marks are re-scanned by
+// k_cond_qr, which counts their NaNs and rule hits itself.
+template <int NX, int MB, int NB, bool TABLE, int W2, bool PERM = false, bool MORE = false, bool PV = false, bool RED = false, bool COND = false>
 __global__ void __launch_bounds__(64 * W2 * W2, 2) k_scan(ScanArgs a, int ntile_i, int64_t nwg) {
   static_assert(!(RED && PV), "reduce-in-epilogue: no p-value output");
+  static_assert(!COND || (!TABLE && !PV && !RED && NX >= 1), "conditional scan: exact mode, L only");
   constexpr int NP = 1 + NX;  // A-side panels consumed
   constexpr int NT = 64 * W2 * W2;
   static_assert(!PERM || (TABLE && NX == 0), "permuted columns: table mode");
@@ -312,7 +319,7 @@ __global__ void __launch_bounds__(64 * W2 * W2, 2) k_scan(ScanArgs a, int ntile_
         }
       }
   };
-  if constexpr (MORE) {
+  if constexpr (MORE && !COND) {
     stage_and_zero();
     for (int q0 = CFAST; q0 < a.c; q0 += CFAST) {
       const int nq = (a.c - q0 < CFAST) ? a.c - q0 : CFAST;     // wave-uniform
@@ -347,7 +354,7 @@ __global__ void __launch_bounds__(64 * W2 * W2, 2) k_scan(ScanArgs a, int ntile_
   }
   double a0[NP][MB], b0[NB], a1[NP][MB], b1[NB];
   load_set(a0, b0, 0);
-  if constexpr (!MORE) {
+  if constexpr (!MORE || COND) {
     __builtin_amdgcn_sched_barrier(0);
     stage_and_zero();       // under the first fragments' round trip
     __builtin_amdgcn_sched_barrier(0);
@@ -364,12 +371,61 @@ __global__ void __launch_bounds__(64 * W2 * W2, 2) k_scan(ScanArgs a, int ntile_
     __builtin_amdgcn_sched_barrier(0);
   }
   if (ks < a.ks) mfma_set(a0, b0);
+  if constexpr (COND && MORE) {
+    // acc[2] <- Sxx - (the in-loop u_q^2); acc[3 ..] then take the panels 2 + CFAST .. 1 + a.c, CFAST - 1 per pass
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+          double xx = acc[1][mb][nb][reg];
+#pragma unroll
+          for (int q = 2; q < NP; ++q) xx = fma(-acc[q][mb][nb][reg], acc[q][mb][nb][reg], xx);
+          acc[2][mb][nb][reg] = xx;
+        }
+    constexpr int CH = CFAST - 1;
+    for (int q0 = CFAST; q0 < a.c; q0 += CH) {
+      const int nq = (a.c - q0 < CH) ? a.c - q0 : CH;     // wave-uniform
+#pragma unroll
+      for (int q = 0; q < CH; ++q)
+#pragma unroll
+        for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+          for (int nb = 0; nb < NB; ++nb) acc[3 + q][mb][nb] = (d4){0, 0, 0, 0};
+      for (int step = 0; step < a.ks; ++step) {
+        double A[CH][MB], B[NB];
+        bufload_m<NB>(B, make_srd(PB + step * sb), voffB);
+#pragma unroll
+        for (int q = 0; q < CH; ++q)
+          if (q < nq) bufload<MB>(A[q], make_srd(PA + (2 + q0 + q) * a.pstride + step * sa), voffA);
+#pragma unroll
+        for (int q = 0; q < CH; ++q)
+          if (q < nq) {
+#pragma unroll
+            for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+              for (int nb = 0; nb < NB; ++nb)
+                acc[3 + q][mb][nb] = __builtin_amdgcn_mfma_f64_16x16x4f64(A[q][mb], B[nb], acc[3 + q][mb][nb], 0, 0, 0);
+          }
+      }
+#pragma unroll
+      for (int q = 0; q < CH; ++q)
+#pragma unroll
+        for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+          for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg)
+              acc[2][mb][nb][reg] = fma(-acc[3 + q][mb][nb][reg], acc[3 + q][mb][nb][reg], acc[2][mb][nb][reg]);
+    }
+  }
 
   // ---- epilogue: projection, normalisation, r -> LOD, 32-byte stores ---------------------------------
   __syncthreads();
   const double scale = a.lodc[0];
   const LodPoly5 lp = lod_poly5_of(a.lodc);
-  int nnan = 0;
+  int nnan = 0, nrule = 0;
 #pragma unroll
   for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
@@ -390,6 +446,9 @@ __global__ void __launch_bounds__(64 * W2 * W2, 2) k_scan(ScanArgs a, int ntile_
       // the NB outputs of a row are independent chains; u outside the LOD table's range (LOD beyond ~1.2 n / 2, r^2 >= 1 --
       // +Inf / DomainError in Julia, NaN here --, NaN) is rare and handled per ROW behind one branch
       double uv[NB], out[NB];
+      bool rule[COND ? NB : 1];
+      bool counted = true;                       // COND: a trait the guard re-scans is counted there
+      if constexpr (COND) counted = a.cflag[trait] == 0;
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb) {
         const double num = acc[0][mb][nb][reg];
@@ -397,6 +456,15 @@ __global__ void __launch_bounds__(64 * W2 * W2, 2) k_scan(ScanArgs a, int ntile_
         if constexpr (TABLE) {
           const double rr = num * sc[nb];
           r2 = rr * rr;
+        } else if constexpr (COND) {
+          const double xx0 = acc[1][mb][nb][reg];
+          double xx = MORE ? acc[2][mb][nb][reg] : xx0;
+          if constexpr (!MORE) {
+#pragma unroll
+            for (int q = 2; q < NP; ++q) xx = fma(-acc[q][mb][nb][reg], acc[q][mb][nb][reg], xx);
+          }
+          rule[nb] = !(xx > MDF_TAU * xx0);      // NaN: dropped, as mdf_chol
+          r2 = rule[nb] ? 0.0 : (num * num) * fast_rcp1(xx);
         } else {
           double xx = acc[1][mb][nb][reg];
 #pragma unroll
@@ -411,7 +479,12 @@ __global__ void __launch_bounds__(64 * W2 * W2, 2) k_scan(ScanArgs a, int ntile_
       if (__builtin_expect(!ok, 0)) {
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb)
-          if (!lod_fast_ok(uv[nb])) out[nb] = lod_out_of_range(uv[nb], s_lod, lp, scale, i0 + mslot<NB>(r, nb) < a.p, &nnan);
+          if (!lod_fast_ok(uv[nb])) out[nb] = lod_out_of_range(uv[nb], s_lod, lp, scale, counted && i0 + mslot<NB>(r, nb) < a.p, &nnan);
+      }
+      if constexpr (COND) {
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb)
+          if (rule[nb]) { out[nb] = 0.0; nrule += (counted && i0 + mslot<NB>(r, nb) < a.p) ? 1 : 0; }
       }
       if constexpr (RED) red_row<NB>(a.red, trait, i0, r, lane, out, red_valid(a.p, i0, 16 * NB));
       else store_m<NB>(a.L + trait * a.ldL + i0, r, out, a.p - i0);
@@ -423,6 +496,9 @@ __global__ void __launch_bounds__(64 * W2 * W2, 2) k_scan(ScanArgs a, int ntile_
       }
     }
   if (nnan) atomicAdd((unsigned long long*)&a.stat[ST_NAN_LOD], (unsigned long long)nnan);
+  if constexpr (COND) {
+    if (nrule) atomicAdd((unsigned long long*)&a.cinfo[0], (unsigned long long)nrule);
+  }
 }
 
 template <int NX, bool TABLE, int MB, int W2 = 2, bool MORE = false>
@@ -461,6 +537,32 @@ int launch_scan_exact(blmm_ctx* ctx, const ScanArgs& a, int c) {
   }
   if (c > CFAST && c <= CMAX && a.c == c) return launch_scan_t<1 + CFAST, false, 1, 2, true>(ctx, a);
   return fail(ctx, BLMM_ERR_UNSUPPORTED, BLMM_C_ERR);
+}
+
+// blmm_bulkscan_cond: ct = the columns of the per-trait null design (covariates incl. the intercept + conditioning loci, <= CTPL)
+template <int NX, int MB, bool MORE>
+static int launch_scan_cond_t(blmm_ctx* ctx, const ScanArgs& a) {
+  constexpr int NB = 4, W2 = 2;
+  const int64_t ntile_t = (a.m + 16 * W2 * MB - 1) / (16 * W2 * MB);
+  const int64_t ntile_i = (a.p + 16 * W2 * NB - 1) / (16 * W2 * NB);
+  const int64_t nwg = ntile_t * ntile_i;
+  if (nwg <= 0) return BLMM_OK;
+  if (nwg > 0x7fffffffLL) return fail(ctx, BLMM_ERR_INVALID, "problem too large for one launch");
+  hipLaunchKernelGGL((k_scan<NX, MB, NB, false, W2, false, MORE, false, false, true>), dim3((unsigned)nwg), dim3(64 * W2 * W2), 0, ctx->stream, a, (int)ntile_i, nwg);
+  KCHECK();
+  return BLMM_OK;
+}
+
+int launch_scan_cond(blmm_ctx* ctx, const ScanArgs& a, int ct) {
+  if (!a.cflag || !a.cinfo || a.Pv || a.red.pmax || a.c != ct) return fail(ctx, BLMM_ERR_INVALID, "launch_scan_cond: bad arguments");
+  switch (ct) {
+    case 1: return launch_scan_cond_t<2, 2, false>(ctx, a);
+    case 2: return launch_scan_cond_t<3, 1, false>(ctx, a);
+    case 3: return launch_scan_cond_t<4, 1, false>(ctx, a);
+    case 4: return launch_scan_cond_t<5, 1, false>(ctx, a);
+    case 5: case 6: case 7: case 8: return launch_scan_cond_t<1 + CFAST, 1, true>(ctx, a);
+  }
+  return fail(ctx, BLMM_ERR_UNSUPPORTED, "bulkscan_cond: 1 .. 8 null-design columns");
 }
 
 // ------------------------------------------------------------------------------------------------

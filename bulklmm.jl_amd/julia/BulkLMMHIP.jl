@@ -11,7 +11,7 @@
 # every `ccall`'s symbol, return type and argument tuple (arity and types) against the prototype in include/bulklmm_hip.h.
 module BulkLMMHIP
 
-export bulkscan_effects, bulkscan_multidf, calcKinship_loco, bulkscan_loco, bulkscan_loco_reduced, bulkscan_loco_perms, bulkscan_perms, bulkscan_reduced, bulkscan_reduced_async!, synchronize, DeviceLOD, lod_columns, set_tuning, calcKinship, bulkscan, bulkscan_null, bulkscan_null_grid, bulkscan_alt_grid, bulkscan_alt_exact, scan, bulkscan_multi, lod2log10p, get_thresholds,
+export bulkscan_cond, bulkscan_effects, bulkscan_multidf, calcKinship_loco, bulkscan_loco, bulkscan_loco_reduced, bulkscan_loco_perms, bulkscan_perms, bulkscan_reduced, bulkscan_reduced_async!, synchronize, DeviceLOD, lod_columns, set_tuning, calcKinship, bulkscan, bulkscan_null, bulkscan_null_grid, bulkscan_alt_grid, bulkscan_alt_exact, scan, bulkscan_multi, lod2log10p, get_thresholds,
        lod_threshold, lod_colmax, pinned_matrix, host_register, host_unregister
 
 const libblmm = get(ENV, "BULKLMM_HIP_LIB", joinpath(@__DIR__, "..", "csrc", "libbulklmm_hip.so"))
@@ -399,6 +399,65 @@ function bulkscan_multidf(Y::Array{Float64, 2}, G::Array{Float64, 2}, Covar::Arr
     res = (L = keep_on_device ? DeviceLOD(P, m) : L, h2_null_list = h2)
     if output_pvals
         return merge(res, (log10Pvals_mat = _last_log10p((P, m), chisq_df), Chisq_df = chisq_df))
+    end
+    return res
+end
+
+# ---- conditional bulkscan (blmm_bulkscan_cond): column j of L is the scan of trait j with the null design [Covar G[:, cond[j, :]]].
+# cond: m (or m x s, s <= 4) 1-based columns of G, 0 for none; or "peak": bulkscan_reduced first, every trait conditioned on its peak.
+# Markers collinear with a trait's design (the conditioning marker itself) get LOD 0.  Returns L, h2_null_list (with the loci in the
+# null model), cond (as used, 1-based), n_rule_zero, n_cond_dropped, n_cond_traits.
+function bulkscan_cond(Y::Array{Float64, 2}, G::Array{Float64, 2}, K::Array{Float64, 2}, cond; kwargs...)
+    return bulkscan_cond(Y, G, ones(size(Y, 1), 1), K, cond; kwargs..., addIntercept = false)
+end
+function bulkscan_cond(Y::Array{Float64, 2}, G::Array{Float64, 2}, Covar::Array{Float64, 2}, K::Array{Float64, 2}, cond;
+                       method::String = "null-grid", h2_grid::Array{Float64, 1} = collect(0.0:0.1:0.9), addIntercept::Bool = true,
+                       weights::Union{Missing, Array{Float64, 1}} = missing, prior_variance::Float64 = 1.0,
+                       prior_sample_size::Float64 = 0.0, reml::Bool = false, optim_interval::Int64 = 1,
+                       decomp_scheme::String = "eigen", output_pvals::Bool = false, chisq_df::Int64 = 1,
+                       keep_on_device::Bool = false)
+    (n, m) = size(Y); p = size(G, 2)
+    (size(G, 1) != n || size(K, 1) != n || size(K, 2) != n || size(Covar, 1) != n) && error("Dimension mismatch.")
+    (weights !== missing && length(weights) != n) && error("Dimension mismatch.")
+    method in ("null-grid", "null-exact", "alt-grid") || error("Unknown method `$method`; choose null-exact, null-grid or alt-grid.")
+    method == "alt-grid" && error("bulkscan_cond: alt-grid is not supported; use null-grid or null-exact")
+    check_n(n)
+    if cond isa AbstractString
+        cond == "peak" || error("bulkscan_cond: cond is an index array or the string \"peak\"")
+        red = bulkscan_reduced(Y, G, Covar, K; method = method, h2_grid = h2_grid, addIntercept = addIntercept, weights = weights,
+                               prior_variance = prior_variance, prior_sample_size = prior_sample_size, reml = reml,
+                               optim_interval = optim_interval, decomp_scheme = decomp_scheme)
+        cond = reshape(Int64.(red.argmax), m, 1)
+    end
+    cmat = ndims(cond) == 1 ? reshape(Int64.(cond), :, 1) : Int64.(cond)
+    size(cmat, 1) == m || error("bulkscan_cond: cond must have m rows")
+    s = size(cmat, 2)
+    s <= 4 || error("bulkscan_cond: at most 4 conditioning loci per trait")
+    all(0 .<= cmat .<= p) || error("bulkscan_cond: a conditioning index outside 0 .. p")
+    ctab = Array{Int64, 2}(permutedims(cmat .- 1))      # s x m, 0-based, -1: none
+    meth = method == "null-exact" ? NULL_EXACT : NULL_GRID
+    o = BlmmOpts(meth, reml, addIntercept, decomp(decomp_scheme), optim_interval, 0, prior_variance, prior_sample_size)
+    L = keep_on_device ? nothing : Array{Float64, 2}(undef, p, m)
+    h2 = Array{Float64, 1}(undef, m)
+    info = zeros(Int64, 4)
+    st = BlmmStatus()
+    if output_pvals
+        check(ccall((:blmm_set_log10p_output, libblmm), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64),
+                    context(), Ptr{Float64}(C_NULL), Int64(0), chisq_df))
+    end
+    GC.@preserve Y G Covar K weights h2_grid ctab L h2 info begin
+        check(ccall((:blmm_bulkscan_cond, libblmm), Cint,
+                    (Ptr{Cvoid}, Ref{BlmmOpts}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64,
+                     Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Int64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Int64},
+                     Ref{BlmmStatus}),
+                    context(), o, Y, n, m, G, p, Covar, size(Covar, 2), K, ptr_or_null(weights), h2_grid,
+                    length(h2_grid), ctab, Int64(s), ptr_or_null(L), h2, info, st))
+    end
+    raise_status(st)
+    res = (L = keep_on_device ? DeviceLOD(p, m) : L, h2_null_list = h2, cond = cmat, n_rule_zero = info[1],
+           n_cond_dropped = info[2], n_cond_traits = info[3])
+    if output_pvals
+        return merge(res, (log10Pvals_mat = _last_log10p((p, m), chisq_df), Chisq_df = chisq_df))
     end
     return res
 end

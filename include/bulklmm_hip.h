@@ -562,6 +562,47 @@ int blmm_bulkscan_multidf_dev(blmm_ctx* ctx, const blmm_opts* opts, const double
                               const double* h2_grid, int64_t ngrid, double* dL_out, int64_t ldL, double* dh2_out,
                               blmm_status* status);
 
+/* ---- conditional bulkscan: every trait scanned with its OWN loci in the null model (secondary QTL given the peak) -----------------
+ * Inputs as blmm_bulkscan_multidf with k = 1 (Y n x m, G n x p, Covar / add_intercept, K, weights, h2_grid; opts: null-grid or
+ * null-exact, reml, the prior, optim_interval, decomp_scheme) plus cond: s x m int64, cond[j s + a] = the 0-based column of G that
+ * is trait j's a-th conditioning locus, or -1 for none.  A trait may have 0 .. s loci; s = 0 or cond == NULL: none at all.
+ * In the rotated space of transform_rotation, for trait j:
+ *   1. Conditioning columns, decided once and unweighted: taking the trait's valid entries in order, column a is kept iff the part
+ *      of x0_a orthogonal to span[Z0, the kept columns before it] has squared norm > BLMM_COND_TAU |x0_a|^2.  A repeated index, a
+ *      marker equal to a covariate and a constant marker drop out.  D_j = [Z0, kept columns], r_j = the number kept.
+ *   2. Null model on D_j: null-exact fitlmm(y0_j, D_j, lambda, prior; reml, optim_interval) (src/lmm.jl:56-86); null-grid the first
+ *      arg-max over the grid of wls(y0_j, D_j, makeweights(g), prior; reml).ell (src/wls.jl:27-97; REML's p is c + r_j).  h2_out[j]
+ *      is that h2; with r_j = 0 it is blmm_bulkscan's null model (the search's own tolerance apart for null-exact).
+ *   3. Scan: sw = sqrt(|makeweights(h2_j)|), D~ = sw .* D_j, e = the residual of sw .* y0_j on span(D~), x~_i = sw .* x0_i, r_i = the
+ *      residual of x~_i on span(D~).  Rank rule (blmm_bulkscan_multidf's, at the trait's weights): |r_i|^2 <= BLMM_COND_TAU |x~_i|^2
+ *      gives L[i, j] = +0.0, else L[i, j] = -(n/2) log10(1 - (r_i'e)^2 / (|r_i|^2 |e|^2)).  NaN / +Inf / e = 0 as in multidf
+ *      (n_nan_lod, n_zero_norm).
+ * So column j is what the reference's scan returns for (y_j, G, [Covar G[:, cond_j]], K), except at the markers the rule sets to 0
+ * (the conditioning markers themselves and their duplicates), where the reference divides by zero.
+ *   L_out      p x m, or NULL: L stays resident for the blmm_last_* consumers
+ *   cinfo_out  int64[BLMM_COND_INFO_LEN], may be NULL: [0] entries of L the rank rule set to 0, [1] conditioning entries dropped in
+ *              step 1, [2] traits with r_j >= 1, [3] 0
+ *   status     as blmm_bulkscan fills it; n_illcond_rescan: traits whose weighted design D~ was nearly collinear (a marker beside
+ *              the intercept at h2 -> 1) and whose columns were recomputed with an orthonormal basis and explicit residuals
+ * Limits: s <= BLMM_COND_MAX_LOCI, c + s <= BLMM_MULTIDF_MAX_COVARIATES (c: null covariates incl. the intercept), c + s < n,
+ * n <= 2048.  Refused before anything is uploaded: alt-grid, s or c + s above the limit, n > 2048 (BLMM_ERR_UNSUPPORTED), an
+ * unknown method (BLMM_ERR_METHOD), an index outside [-1, p) (BLMM_ERR_INVALID; host form).  The _dev form cannot see its indices:
+ * such a trait gets a NaN column and a NaN h2, nothing out of range is touched, and the call returns BLMM_ERR_INVALID when a status
+ * is asked for.  A pending blmm_set_log10p_output request is honoured by a column pass over the finished L.
+ * The _dev form: device Y / G / Covar / weights / cond / L_out (ld ldL >= p) / h2_out / cinfo_out; stream-ordered like
+ * blmm_bulkscan_multidf_dev. */
+#define BLMM_COND_TAU BLMM_MULTIDF_TAU
+#define BLMM_COND_MAX_LOCI 4
+#define BLMM_COND_INFO_LEN 4
+int blmm_bulkscan_cond(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, int64_t n, int64_t m, const double* G, int64_t p,
+                       const double* Covar, int64_t ncov, const double* K, const double* weights, const double* h2_grid,
+                       int64_t ngrid, const int64_t* cond, int64_t s, double* L_out, double* h2_out, int64_t* cinfo_out,
+                       blmm_status* status);
+int blmm_bulkscan_cond_dev(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG, int64_t p,
+                           const double* dCovar, int64_t ncov, const double* dK, const double* dweights, const double* h2_grid,
+                           int64_t ngrid, const int64_t* dcond, int64_t s, double* dL_out, int64_t ldL, double* dh2_out,
+                           int64_t* dcinfo_out, blmm_status* status);
+
 /* ---- effects at chosen tests: coefficients and standard errors where a scan found something ------------------------------------
  * Takes what blmm_bulkscan_multidf takes (opts: null-grid or null-exact, reml, the prior, add_intercept, optim_interval,
  * decomp_scheme; Y n x m; G n x p with p = P k, locus l = columns l k .. l k + k - 1, k = 1: the ordinary marker test; Covar, K,
