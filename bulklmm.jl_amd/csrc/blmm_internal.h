@@ -481,6 +481,27 @@ int launch_alt_ctab(blmm_ctx* ctx, const double* EllTab, int ngrid, int64_t m, i
 int launch_bperm_panels(blmm_ctx* ctx, const NullModel& nm, const double* Yt, int64_t ldy, const double* Z0, const double* lam,
                         const double* h2c, int64_t mt, const int32_t* perm, int64_t nperms, double* panel, int64_t ldp, int* bin,
                         int64_t* stat);
+// ---- the quantiles of a vector of maxima, as every kernel that takes them sorts and interpolates (k_bitonic_*, k_quantiles,
+// k_bperm_summary) ----
+// total order of the sort: NaN is the largest key
+__host__ __device__ inline bool key_less(double a, double b) {
+  if (a != a) return false;
+  if (b != b) return true;
+  return a < b;
+}
+// Julia's default quantile (type 7) between the neighbouring order statistics a <= b, g = h - floor(h) in [0, 1), h = (n - 1) q:
+//   g == 0 or a == b  ->  a              (an order statistic itself; two equal infinities are that infinity, not inf - inf)
+//   both finite       ->  a + g (b - a)
+//   otherwise         ->  (1 - g) a + g b in the extended reals: +inf above a finite a, -inf below a finite b; -inf beside +inf is
+//                         the limit of (1 - g)(-M) + g M = (2 g - 1) M: -inf below g = 1/2, +inf above it, 0 at it
+// so a threshold is NaN only when one of its two neighbours is.
+__host__ __device__ inline double quantile7_interp(double a, double b, double g) {
+  if (g == 0.0 || a == b) return a;
+  const bool fa = a - a == 0.0, fb = b - b == 0.0;   // finite
+  if (fa && fb) return a + g * (b - a);
+  if (!fa && !fb && a < b) return g < 0.5 ? a : (g > 0.5 ? b : 0.0);
+  return (1.0 - g) * a + g * b;
+}
 // quantile levels of the thresholds, passed by value (at most 64, as blmm_get_thresholds)
 struct BpermProbs { double v[64]; };
 // per trait of the chunk: peak and marker, the permutation maxima (max_perms: nperms x m, ld = nperms), thresholds (nprobs x m,

@@ -318,11 +318,6 @@ int launch_bperm_panels(blmm_ctx* ctx, const NullModel& nm, const double* Yt, in
 // default type 7) equal blmm_get_thresholds on the trait's L_perms bit for bit.  pval = (1 + #{b : max_b >= peak}) / (nperms + 1),
 // a -inf maximum (no finite-comparable LOD) never counted.  row0 is added to every marker written (-1 stays -1); lod_max /
 // lod_argmax may be NULL.
-__device__ __forceinline__ bool bperm_key_less(double a, double b) {
-  if (a != a) return false;
-  if (b != b) return true;
-  return a < b;
-}
 __global__ void __launch_bounds__(256) k_bperm_summary(const double* __restrict__ mx, const int64_t* __restrict__ arg, int64_t nperms,
                                                        int npow, BpermProbs probs, int nprobs, int64_t j0, int64_t row0,
                                                        double* __restrict__ lod_max, int64_t* __restrict__ lod_argmax,
@@ -358,7 +353,7 @@ __global__ void __launch_bounds__(256) k_bperm_summary(const double* __restrict_
         if (x > e) {
           const double a = sv[e], b = sv[x];
           const bool up = (e & k) == 0;
-          if (up ? bperm_key_less(b, a) : bperm_key_less(a, b)) { sv[e] = b; sv[x] = a; }
+          if (up ? key_less(b, a) : key_less(a, b)) { sv[e] = b; sv[x] = a; }
         }
       }
       __syncthreads();
@@ -373,7 +368,7 @@ __global__ void __launch_bounds__(256) k_bperm_summary(const double* __restrict_
       const int64_t lo = (int64_t)floor(hq);
       const int64_t hi = lo + 1 < nperms ? lo + 1 : nperms - 1;
       const double a = sv[lo], b = sv[hi];
-      out = a + (hq - (double)lo) * (b - a);
+      out = quantile7_interp(a, b, hq - (double)lo);
     }
     thr[j * nprobs + t] = out;
   }

@@ -264,12 +264,7 @@ __global__ void __launch_bounds__(256) k_gather_cols(const double* __restrict__ 
 }
 
 // ---- quantiles of a device vector (the per-permutation maxima): bitonic sort + linear interpolation ------------------
-// NaN sorts last.  npow = the next power of two >= count; the tail is padded with +inf.
-__device__ __forceinline__ bool key_less(double a, double b) {   // total order with NaN as the largest key
-  if (a != a) return false;
-  if (b != b) return true;
-  return a < b;
-}
+// NaN sorts last (key_less, blmm_internal.h).  npow = the next power of two >= count; the tail is padded with +inf.
 __global__ void __launch_bounds__(1024) k_bitonic_lds(double* __restrict__ v, int npow) {   // npow <= 16384: one workgroup
   extern __shared__ double sv[];
   for (int e = threadIdx.x; e < npow; e += blockDim.x) sv[e] = v[e];
@@ -302,7 +297,7 @@ __global__ void k_pad_inf(double* __restrict__ v, int64_t count, int64_t npow) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= count && e < npow) v[e] = INFINITY;
 }
-// Julia's default quantile (type 7): h = (n - 1) q; v[floor(h)] + (h - floor(h)) (v[floor(h) + 1] - v[floor(h)]).
+// Julia's default quantile (type 7): h = (n - 1) q, between v[floor(h)] and v[floor(h) + 1] by quantile7_interp (blmm_internal.h).
 __global__ void k_quantiles(const double* __restrict__ sorted, int64_t count, const double* __restrict__ probs, int nprobs,
                             double* __restrict__ out) {
   const int t = threadIdx.x;
@@ -314,7 +309,7 @@ __global__ void k_quantiles(const double* __restrict__ sorted, int64_t count, co
   const int64_t lo = (int64_t)floor(h);
   const int64_t hi = lo + 1 < count ? lo + 1 : count - 1;
   const double a = sorted[lo], b = sorted[hi];
-  out[t] = a + (h - (double)lo) * (b - a);
+  out[t] = quantile7_interp(a, b, h - (double)lo);
 }
 
 // sorts `work` (count values, capacity npow) in place and evaluates the quantiles; probs/out are device arrays

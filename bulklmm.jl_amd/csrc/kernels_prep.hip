@@ -2915,8 +2915,10 @@ int launch_perm_panel(blmm_ctx* ctx, const NullModel& nm, const double* Yt, int6
 // ------------------------------------------------------------------------------------------------
 // Column maxima of an LOD matrix (p x m, ld = ldL): per-trait / per-permutation peak and the marker where it sits.
 // The consumer behind get_thresholds (src/analysis_helpers/single_trait_analysis.jl:13-23) and the usual
-// "max LOD per trait" summary, so the 2 GB matrix need not leave HBM.  One wave per column,
-// 16-byte loads, first maximum wins; NaNs are ignored (a column of NaNs gives -inf, marker -1).
+// "max LOD per trait" summary, so the 2 GB matrix need not leave HBM.  One wave per column, lane l
+// reading rows l, l + 64, ... as scalar 8-byte loads (a wave instruction covers 512 contiguous bytes); the maximum at its lowest
+// row wins, whichever lane holds it; NaNs are ignored.  A column with no entry above -inf (empty, all NaN, all -inf) gives
+// -inf, marker -1.
 // ------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_colmax(const double* __restrict__ L, int64_t p, int64_t m, int64_t ldL,
                                                 double* __restrict__ mx, int64_t* __restrict__ arg, int64_t row0) {

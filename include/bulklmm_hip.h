@@ -700,7 +700,12 @@ int blmm_lod_threshold_dev(blmm_ctx* ctx, const double* dL, int64_t p, int64_t m
                            int32_t* di_out, int32_t* dj_out, double* dlod_out, int64_t* dcount_out);
 /* ---- get_thresholds (src/analysis_helpers/single_trait_analysis.jl:13-23): quantiles (Julia's default, linear
  * interpolation) at `probs` (HOST array, nprobs <= 64) of the per-permutation maxima; column maxima, sort and
- * interpolation on the device, thrs_out (nprobs doubles) in HOST memory. */
+ * interpolation on the device, thrs_out (nprobs doubles) in HOST memory.  A level is clamped to [0, 1]; with h = (nperms - 1) q,
+ * a <= b the maxima of rank floor(h) and floor(h) + 1 and g = h - floor(h), the threshold is a + g (b - a) for finite a, b.
+ * Maxima may be infinite (+inf: an LOD of 1 - R^2 = 0; -inf: a column without a comparable LOD): g == 0 or a == b gives a (two
+ * equal infinities give that infinity, not inf - inf), otherwise (1 - g) a + g b in the extended reals -- +inf above a finite a,
+ * -inf below a finite b, and -inf beside +inf the limit of (2 g - 1) M: -inf below g = 1/2, +inf above, 0 at it.  A threshold
+ * lies between two order statistics and is never NaN. */
 int blmm_get_thresholds(blmm_ctx* ctx, const double* Lperms, int64_t p, int64_t nperms, const double* probs, int64_t nprobs,
                         double* thrs_out);
 int blmm_get_thresholds_dev(blmm_ctx* ctx, const double* dLperms, int64_t p, int64_t nperms, int64_t ld, const double* probs,
