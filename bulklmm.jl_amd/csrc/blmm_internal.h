@@ -457,6 +457,20 @@ int launch_illcond_flag(blmm_ctx* ctx, const NullModel& nm, int64_t m, const dou
 int launch_scan_qr(blmm_ctx* ctx, const NullModel& nm, const double* Yt, int64_t ldy, const double* Xt, int64_t ldx, int64_t p,
                    const double* Z0, const double* lam, const double* h2, const int* list, double* L, int64_t ldL, int64_t* stat,
                    const RedArgs& red = RedArgs());
+// The workspace of the QR-grade re-scans (ortho_basis.h): (cols + 2) n doubles per workgroup -- the weights' square roots, `cols`
+// basis columns, the trait residual -- as dynamic LDS up to 64 KiB (*slab = nullptr; the launcher raises the kernel's limit above
+// 48 KiB), beyond that *lds = 0 and a slab of ctx->qrSlab per workgroup.  *grid: two workgroups per CU, striding over the listed traits.
+inline int qr_workspace(blmm_ctx* ctx, int cols, int n, size_t* lds, double** slab, unsigned* grid) {
+  const size_t per = (size_t)(cols + 2) * n;
+  *grid = (unsigned)(2 * (ctx->num_cus > 0 ? ctx->num_cus : 256));
+  *lds = sizeof(double) * per;
+  *slab = nullptr;
+  if (*lds <= 64 * 1024) return BLMM_OK;
+  if (int rc = ensure(ctx, ctx->qrSlab, sizeof(double) * per * *grid)) return rc;
+  *slab = ptr<double>(ctx->qrSlab);
+  *lds = 0;
+  return BLMM_OK;
+}
 // kernels_lowrank.hip
 // the segments a call with n individuals uses (one when the basis comes from the multi-workgroup / LDS kernels: n > 80)
 LrSeg lr_segments(const blmm_ctx* ctx, int n);

@@ -15,9 +15,10 @@
 //                  (k_illcond_flag's: the smallest pivot share of D_j'WD_j below rho_min) -> flag[], list, stat[ST_ILLCOND].
 //   the scan       k_scan<.., COND> (kernels_scan.hip): the f64-MFMA contraction with 2 + CT accumulators and the rank-rule epilogue.
 //   k_cond_qr      the listed traits again with an orthonormal basis of span(sqrt(W) D_j) (Gram-Schmidt twice) and explicit
-//                  residuals, the rank rule on the explicit norms (k_scan_qr's / k_mdf_qr's method).
+//                  residuals (ortho_basis.h), the rank rule on the explicit norms.
 #include "blmm_internal.h"
 #include "fastmath.h"
+#include "ortho_basis.h"
 #include "brent_scalar.h"
 #include <cmath>
 
@@ -380,23 +381,7 @@ __global__ void __launch_bounds__(256) k_cond_panels(NullModel nm, CondArgs a, d
   }
 }
 
-// ---- the guard's re-scan: k_mdf_qr (kernels_mdf.hip) for one column per test on the per-trait design ----------------------------------
-__device__ __forceinline__ double cond_block_sum(double v, double* s_red /* [4] */) {
-  v = group_sum<64>(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
-}
-__device__ __forceinline__ void cond_project_out(double* tgt, const double* Qb, int nq, int n, double* s_red) {
-  for (int r = 0; r < nq; ++r) {
-    double t = 0.0;
-    for (int k = threadIdx.x; k < n; k += 256) t = fma(Qb[(size_t)r * n + k], tgt[k], t);
-    t = cond_block_sum(t, s_red);
-    for (int k = threadIdx.x; k < n; k += 256) tgt[k] = fma(-t, Qb[(size_t)r * n + k], tgt[k]);
-  }
-}
-
+// ---- the guard's re-scan: ortho_basis.h's front on the per-trait design, one column per test ------------------------------------------
 constexpr int COND_CT = BLMM_MULTIDF_MAX_COVARIATES;
 // One workgroup per listed trait at a time; buf: (CTmax + 2) n doubles (sqrt weights, the orthonormal basis, the unit trait residual)
 __global__ void __launch_bounds__(256) k_cond_qr(CondArgs a, int ctmax, const int* __restrict__ list, double* slab,
@@ -415,55 +400,15 @@ __global__ void __launch_bounds__(256) k_cond_qr(CondArgs a, int ctmax, const in
   for (int64_t item = blockIdx.x; item < cnt; item += gridDim.x) {
     const int64_t j = list[item];
     const int ct = c + a.nk[j];
-    const double h2 = a.h2[j];
-    const double delta = h2 / (1.0 - h2);
-    __syncthreads();
-    for (int k = threadIdx.x; k < n; k += 256) {
-      const double sw = sqrt(fabs(1.0 / fma(delta, a.lam[k], 1.0)));
-      Sw[k] = sw;
-      for (int q = 0; q < c; ++q) Qb[(size_t)q * n + k] = sw * a.Z0[(size_t)q * n + k];
-      for (int q = c; q < ct; ++q) Qb[(size_t)q * n + k] = sw * a.Xt[(int64_t)k * a.ldx + a.kept[j * s + (q - c)]];
-      yb[k] = sw * a.Yt[(int64_t)k * a.ldy + j];
-    }
-    for (int q = 0; q < ct; ++q) {
-      double* col = Qb + (size_t)q * n;
-      cond_project_out(col, Qb, q, n, s_red);
-      cond_project_out(col, Qb, q, n, s_red);   // twice is enough
-      double nn = 0.0;
-      for (int k = threadIdx.x; k < n; k += 256) nn = fma(col[k], col[k], nn);
-      nn = cond_block_sum(nn, s_red);
-      const double inv = 1.0 / sqrt(nn);
-      for (int k = threadIdx.x; k < n; k += 256) col[k] *= inv;
-    }
-    cond_project_out(yb, Qb, ct, n, s_red);
-    cond_project_out(yb, Qb, ct, n, s_red);
-    {
-      double nn = 0.0;
-      for (int k = threadIdx.x; k < n; k += 256) nn = fma(yb[k], yb[k], nn);
-      nn = cond_block_sum(nn, s_red);
-      const double inv = 1.0 / sqrt(nn);
-      for (int k = threadIdx.x; k < n; k += 256) yb[k] *= inv;
-    }
+    const int* kj = a.kept + j * s;
+    auto col = [&](int q, int k) { return q < c ? a.Z0[(size_t)q * n + k] : a.Xt[(int64_t)k * a.ldx + kj[q - c]]; };
+    const double nn = weighted_basis<256, 1>(n, ct, a.h2[j], a.lam, col, a.Yt + j, a.ldy, Sw, Qb, yb, s_red);
+    const double inv = 1.0 / sqrt(nn);
+    for (int k = threadIdx.x; k < n; k += 256) yb[k] *= inv;
     __syncthreads();
     for (int64_t i = threadIdx.x; i < a.p; i += 256) {
-      double t[COND_CT], t2[COND_CT];
-#pragma unroll
-      for (int q = 0; q < COND_CT; ++q) { t[q] = 0.0; t2[q] = 0.0; }
-      for (int k = 0; k < n; ++k) {
-        const double x = Sw[k] * a.Xt[(int64_t)k * a.ldx + i];
-#pragma unroll
-        for (int q = 0; q < COND_CT; ++q)
-          if (q < ct) t[q] = fma(Qb[(size_t)q * n + k], x, t[q]);
-      }
-      for (int k = 0; k < n; ++k) {                  // second projection pass on the first residual
-        double x = Sw[k] * a.Xt[(int64_t)k * a.ldx + i];
-#pragma unroll
-        for (int q = 0; q < COND_CT; ++q)
-          if (q < ct) x = fma(-t[q], Qb[(size_t)q * n + k], x);
-#pragma unroll
-        for (int q = 0; q < COND_CT; ++q)
-          if (q < ct) t2[q] = fma(Qb[(size_t)q * n + k], x, t2[q]);
-      }
+      double t[COND_CT];
+      ortho_coeffs<COND_CT>(Sw, Qb, n, ct, a.Xt + i, a.ldx, t);
       double xx = 0.0, d0 = 0.0, num = 0.0;
       for (int k = 0; k < n; ++k) {
         const double x = Sw[k] * a.Xt[(int64_t)k * a.ldx + i];
@@ -471,7 +416,7 @@ __global__ void __launch_bounds__(256) k_cond_qr(CondArgs a, int ctmax, const in
         double v = x;
 #pragma unroll
         for (int q = 0; q < COND_CT; ++q)
-          if (q < ct) v = fma(-(t[q] + t2[q]), Qb[(size_t)q * n + k], v);
+          if (q < ct) v = fma(-t[q], Qb[(size_t)q * n + k], v);
         xx = fma(v, v, xx);
         num = fma(v, yb[k], num);
       }
@@ -521,16 +466,8 @@ int launch_cond_panels(blmm_ctx* ctx, const NullModel& nm, const CondArgs& a, do
 int launch_cond_qr(blmm_ctx* ctx, const NullModel& nm, const CondArgs& a, const int* list, double* L, int64_t ldL) {
   const int ctmax = a.c + a.s;
   if (a.p <= 0 || ctmax < 2) return BLMM_OK;
-  const size_t per = (size_t)(ctmax + 2) * nm.n;
-  const unsigned grid = (unsigned)(2 * (ctx->num_cus > 0 ? ctx->num_cus : 256));
-  double* slab = nullptr;
-  size_t lds = sizeof(double) * per;
-  if (lds > 64 * 1024) {
-    int rc = ensure(ctx, ctx->qrSlab, sizeof(double) * per * grid);
-    if (rc) return rc;
-    slab = ptr<double>(ctx->qrSlab);
-    lds = 0;
-  }
+  size_t lds; double* slab; unsigned grid;
+  if (int rc = qr_workspace(ctx, ctmax, nm.n, &lds, &slab, &grid)) return rc;
   if (lds > 48 * 1024) BLMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cond_qr), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(k_cond_qr, dim3(grid), dim3(256), lds, ctx->stream, a, ctmax, list, slab, L, ldL);
   KCHECK();

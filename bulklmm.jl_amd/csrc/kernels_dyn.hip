@@ -15,6 +15,7 @@
 // Both are no-ops for c = 1 and for data without such traits (a fixed grid reads the count on the device).
 #include "blmm_internal.h"
 #include "fastmath.h"
+#include "ortho_basis.h"
 #include "brent_scalar.h"
 #include <algorithm>
 #include <cmath>
@@ -80,46 +81,7 @@ __global__ void __launch_bounds__(256) k_illcond_flag(int n, int64_t m, const do
   }
 }
 
-// ---- block-wide sums of NV values per thread (256 threads), fixed summation order ---------------------------------------
-template <int NV>
-__device__ __forceinline__ void block_sum(double (&v)[NV], double* s_red /* [4][NV] */) {
-#pragma unroll
-  for (int q = 0; q < NV; ++q) v[q] = group_sum<64>(v[q]);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();                              // the readers of the previous reduction are done with s_red
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int q = 0; q < NV; ++q) s_red[w * NV + q] = v[q];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < NV; ++q) v[q] = (s_red[q] + s_red[NV + q]) + (s_red[2 * NV + q] + s_red[3 * NV + q]);
-}
-
-// Removes from column `tgt` (n doubles, thread t owns the rows t, t + 256, ..) its components along the orthonormal columns
-// Qb[0 .. nq): eight coefficients per block reduction (classical Gram-Schmidt inside a chunk, modified across chunks).
-__device__ __forceinline__ void project_out(double* tgt, const double* Qb, int nq, int n, double* s_red) {
-  for (int r0 = 0; r0 < nq; r0 += 8) {
-    double t[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) t[u] = 0.0;
-    for (int k = threadIdx.x; k < n; k += 256) {
-      const double v = tgt[k];
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        if (r0 + u < nq) t[u] = fma(Qb[(size_t)(r0 + u) * n + k], v, t[u]);
-    }
-    block_sum<8>(t, s_red);
-    for (int k = threadIdx.x; k < n; k += 256) {
-      double v = tgt[k];
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        if (r0 + u < nq) v = fma(-t[u], Qb[(size_t)(r0 + u) * n + k], v);
-      tgt[k] = v;
-    }
-  }
-}
-
+// ---- the QR-grade re-scan: the front is ortho_basis.h's, eight coefficients per reduction -----------------------------------------
 // CQ: compile-time bound of the per-marker coefficient arrays (c <= CQ).  buf: (c + 2) * n doubles per workgroup -- the
 // weights' square roots S, the orthonormal basis Qb (c columns) and the normalised trait residual yb -- in LDS when it fits
 // (`slab` == nullptr) and in a per-workgroup slab of global memory otherwise.
@@ -143,37 +105,13 @@ __global__ void __launch_bounds__(256) k_scan_qr(int n, int c, const double* __r
   const double scale = -0.5 * (double)n;
   for (int64_t item = blockIdx.x; item < cnt; item += gridDim.x) {
     const int64_t j = list[item];
-    const double h2 = h2v[j];
-    const double delta = h2 / (1.0 - h2);
-    __syncthreads();                            // the marker loop of the previous trait has finished reading buf
-    // sqrt.(abs.(makeweights(h2, lambda))) and the weighted columns (src/bulkscan_helpers.jl:138-141); every thread works
-    // on its own rows k = t, t + 256, .. until the marker loop
-    for (int k = threadIdx.x; k < n; k += 256) {
-      const double s = sqrt(fabs(1.0 / fma(delta, lam[k], 1.0)));
-      S[k] = s;
-      for (int q = 0; q < c; ++q) Qb[(size_t)q * n + k] = s * Z0[(size_t)q * n + k];
-      yb[k] = s * Yt[(int64_t)k * ldy + j];
-    }
-    for (int q = 0; q < c; ++q) {
-      double* col = Qb + (size_t)q * n;
-      project_out(col, Qb, q, n, s_red);
-      project_out(col, Qb, q, n, s_red);        // "twice is enough": orthogonal to rounding
-      double nn[1] = {0.0};
-      for (int k = threadIdx.x; k < n; k += 256) nn[0] = fma(col[k], col[k], nn[0]);
-      block_sum<1>(nn, s_red);
-      const double inv = 1.0 / sqrt(nn[0]);
-      for (int k = threadIdx.x; k < n; k += 256) col[k] *= inv;
-    }
-    project_out(yb, Qb, c, n, s_red);
-    project_out(yb, Qb, c, n, s_red);
-    {
-      double nn[1] = {0.0};
-      for (int k = threadIdx.x; k < n; k += 256) nn[0] = fma(yb[k], yb[k], nn[0]);
-      block_sum<1>(nn, s_red);
-      if (threadIdx.x == 0 && !(sqrt(nn[0]) > 2.220446049250313e-16)) atomicAdd((unsigned long long*)&stat[ST_ZERO_NORM], 1ull);
-      const double inv = 1.0 / sqrt(nn[0]);
-      for (int k = threadIdx.x; k < n; k += 256) yb[k] *= inv;
-    }
+    // (its barrier: the marker loop of the previous trait has finished reading buf; until the marker loop every thread works on
+    // its own rows k = t, t + 256, ..)
+    const double nn = weighted_basis<256, 8>(n, c, h2v[j], lam, [&](int q, int k) { return Z0[(size_t)q * n + k]; },
+                                             Yt + j, ldy, S, Qb, yb, s_red);
+    if (threadIdx.x == 0 && !(sqrt(nn) > 2.220446049250313e-16)) atomicAdd((unsigned long long*)&stat[ST_ZERO_NORM], 1ull);
+    const double inv = 1.0 / sqrt(nn);
+    for (int k = threadIdx.x; k < n; k += 256) yb[k] *= inv;
     __syncthreads();                            // basis and trait residual complete: from here every thread reads all rows
     const int64_t iend = RED ? 128 * ((p + 127) / 128) : p;   // RED: whole waves up to the last slot
     for (int64_t i0 = 0; i0 < iend; i0 += 256) {
@@ -182,30 +120,14 @@ __global__ void __launch_bounds__(256) k_scan_qr(int n, int c, const double* __r
         if (i - (threadIdx.x & 63) >= iend) continue;          // a slot that does not exist: the whole wave
         // (lanes beyond p compute on Xt's zero padding, i < ldx, and are masked: the whole wave reaches the reduction)
       } else if (i >= p) continue;
-      double t[CQ], t2[CQ];
-#pragma unroll
-      for (int q = 0; q < CQ; ++q) { t[q] = 0.0; t2[q] = 0.0; }
-      for (int k = 0; k < n; ++k) {
-        const double x = S[k] * Xt[(int64_t)k * ldx + i];
-#pragma unroll
-        for (int q = 0; q < CQ; ++q)
-          if (q < c) t[q] = fma(Qb[(size_t)q * n + k], x, t[q]);
-      }
-      for (int k = 0; k < n; ++k) {             // second projection pass: coefficients of the first residual
-        double xp = S[k] * Xt[(int64_t)k * ldx + i];
-#pragma unroll
-        for (int q = 0; q < CQ; ++q)
-          if (q < c) xp = fma(-t[q], Qb[(size_t)q * n + k], xp);
-#pragma unroll
-        for (int q = 0; q < CQ; ++q)
-          if (q < c) t2[q] = fma(Qb[(size_t)q * n + k], xp, t2[q]);
-      }
+      double t[CQ];
+      ortho_coeffs<CQ>(S, Qb, n, c, Xt + i, ldx, t);
       double xx = 0.0, num = 0.0;
       for (int k = 0; k < n; ++k) {
         double xp = S[k] * Xt[(int64_t)k * ldx + i];
 #pragma unroll
         for (int q = 0; q < CQ; ++q)
-          if (q < c) xp = fma(-(t[q] + t2[q]), Qb[(size_t)q * n + k], xp);
+          if (q < c) xp = fma(-t[q], Qb[(size_t)q * n + k], xp);
         xx = fma(xp, xp, xx);
         num = fma(xp, yb[k], num);
       }
@@ -832,16 +754,8 @@ int launch_scan_qr(blmm_ctx* ctx, const NullModel& nm, const double* Yt, int64_t
                    int64_t* stat, const RedArgs& red) {
   if (p <= 0 || nm.c < 2 || !(illcond_rho_min(ctx) > 0.0)) return BLMM_OK;
   if (red.pmax && nm.c > 8) return fail(ctx, BLMM_ERR_UNSUPPORTED, "k_scan_qr: the reduced form takes c <= 8");
-  const size_t per = (size_t)(nm.c + 2) * nm.n;
-  const unsigned grid = (unsigned)(2 * (ctx->num_cus > 0 ? ctx->num_cus : 256));
-  double* slab = nullptr;
-  size_t lds = sizeof(double) * per;
-  if (lds > 64 * 1024) {
-    int rc = ensure(ctx, ctx->qrSlab, sizeof(double) * per * grid);
-    if (rc) return rc;
-    slab = ptr<double>(ctx->qrSlab);
-    lds = 0;
-  }
+  size_t lds; double* slab; unsigned grid;
+  if (int rc = qr_workspace(ctx, nm.c, nm.n, &lds, &slab, &grid)) return rc;
   if (red.pmax) {
     if (lds > 48 * 1024) BLMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scan_qr<8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL((k_scan_qr<8, true>), dim3(grid), dim3(256), lds, ctx->stream, nm.n, nm.c, Yt, ldy, Xt, ldx, p, Z0, lam, h2, list, slab, nullptr, ldL, stat, nullptr, 0, nullptr, red);

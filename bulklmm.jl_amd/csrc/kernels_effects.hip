@@ -2,7 +2,7 @@
 //
 // Test t = (locus l: the k columns l k .. l k + k - 1 of G, trait j).  With w = |makeweights(h2_j)|, s = sqrt(w), everything in the
 // rotated space of transform_rotation:
-//   q~   orthonormal basis of span(s .* Z0)   (Gram-Schmidt, every projection done twice: k_mdf_qr's / k_scan_qr's method, so nearly
+//   q~   orthonormal basis of span(s .* Z0)   (Gram-Schmidt, every projection done twice: ortho_basis.h, so nearly
 //        collinear weighted covariates at h2 -> 1 need no separate guard)
 //   e~ = s .* y0_j minus its q~ components,  rss0 = |e~|^2                                   -- these three depend on the trait only
 //   r_a = s .* x0_a minus its q~ components;  u_a = r_a minus its components along the accepted u_b (b < a), normalised, ACCEPTED iff
@@ -16,12 +16,13 @@
 // list is cut into chunks of `chunk` positions and ONE WAVE (a 64-thread workgroup) takes a chunk: it rebuilds the trait part only
 // when the trait changes, so a long run of one trait is split over many waves (each builds the trait part once) and a chunk of
 // one-test traits builds it per test.  Every vector lives in the wave's buffer of (c + 2 + k) n doubles -- LDS, or beyond
-// EFF_LDS_MAX bytes a per-workgroup slab of global memory with a bounded grid striding over the chunks (launch_mdf_qr's qrSlab
-// switch).  Lane t owns the elements t, t + 64, .. of every vector and only ever reads what it wrote itself, so neither form needs
+// EFF_LDS_MAX bytes a per-workgroup slab of global memory with a bounded grid striding over the chunks (as qr_workspace,
+// blmm_internal.h).  Lane t owns the elements t, t + 64, .. of every vector and only ever reads what it wrote itself, so neither form needs
 // a barrier; sums go through the wave's xor butterfly (the same bits in every lane, in a fixed order: results do not depend on where
 // a test lands in the sorted list).  The markers come column-major (launch_untranspose of bulkscan_multidf's uncentred rotation),
 // so a test reads k n contiguous doubles.
 #include "blmm_internal.h"
+#include "ortho_basis.h"
 #include <cmath>
 
 namespace blmm {
@@ -79,42 +80,11 @@ __global__ void __launch_bounds__(256) k_eff_scatter(EffArgs a) {
 }
 
 // ---- the wave's vector algebra ----------------------------------------------------------------------------------------------------
+// (the wave's sums: ortho_basis.h's 64-thread forms with the plain xor butterfly, which take no LDS)
 __device__ __forceinline__ double eff_wsum(double v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-// tgt -= its components along the columns B[0 .. nq) (orthonormal or zero), all nq of them from one sweep; coef += the components
-template <int NQ>
-__device__ __forceinline__ void eff_project(double* tgt, const double* B, int nq, int n, int lane, double* coef) {
-  double d[NQ];
-#pragma unroll
-  for (int r = 0; r < NQ; ++r) d[r] = 0.0;
-  for (int i = lane; i < n; i += 64) {
-    const double v = tgt[i];
-#pragma unroll
-    for (int r = 0; r < NQ; ++r)
-      if (r < nq) d[r] = fma(B[(size_t)r * n + i], v, d[r]);
-  }
-#pragma unroll
-  for (int r = 0; r < NQ; ++r)
-    if (r < nq) d[r] = eff_wsum(d[r]);   // nq is the same in every lane
-  for (int i = lane; i < n; i += 64) {
-    double v = tgt[i];
-#pragma unroll
-    for (int r = 0; r < NQ; ++r)
-      if (r < nq) v = fma(-d[r], B[(size_t)r * n + i], v);
-    tgt[i] = v;
-  }
-  if (coef) {
-#pragma unroll
-    for (int r = 0; r < NQ; ++r)
-      if (r < nq) coef[r] += d[r];
-  }
-}
-__device__ __forceinline__ double eff_norm2(const double* v, int n, int lane) {
-  double s = 0.0;
-  for (int i = lane; i < n; i += 64) s = fma(v[i], v[i], s);
-  return eff_wsum(s);
+  double t[1] = {v};
+  team_sum<64, 1, true>(t, nullptr);
+  return t[0];
 }
 
 template <int K>
@@ -142,24 +112,8 @@ __global__ void __launch_bounds__(64) k_effects(EffArgs a) {
       const int64_t j = a.trait[t], l = a.locus[t];
       if (j != cur) {
         cur = j;
-        const double h2 = a.h2[j];
-        const double delta = h2 / (1.0 - h2);
-        for (int i = lane; i < n; i += 64) {
-          const double s = sqrt(fabs(1.0 / fma(delta, a.lam[i], 1.0)));
-          Sw[i] = s;
-          for (int q = 0; q < c; ++q) Qb[(size_t)q * n + i] = s * a.Z0[(size_t)q * n + i];
-          eb[i] = s * a.Yt[(int64_t)i * a.ldy + j];
-        }
-        for (int q = 0; q < c; ++q) {
-          double* col = Qb + (size_t)q * n;
-          eff_project<MDF_CMAX>(col, Qb, q, n, lane, nullptr);
-          eff_project<MDF_CMAX>(col, Qb, q, n, lane, nullptr);   // twice is enough
-          const double inv = 1.0 / sqrt(eff_norm2(col, n, lane));
-          for (int i = lane; i < n; i += 64) col[i] *= inv;
-        }
-        eff_project<MDF_CMAX>(eb, Qb, c, n, lane, nullptr);
-        eff_project<MDF_CMAX>(eb, Qb, c, n, lane, nullptr);
-        rss0 = eff_norm2(eb, n, lane);
+        rss0 = weighted_basis<64, MDF_CMAX, true>(n, c, a.h2[j], a.lam, [&](int q, int i) { return a.Z0[(size_t)q * n + i]; },
+                                                  a.Yt + j, a.ldy, Sw, Qb, eb, nullptr);
       }
       const double* xp = a.Xc + (size_t)l * K * n;
       int mask = 0;
@@ -172,14 +126,14 @@ __global__ void __launch_bounds__(64) k_effects(EffArgs a) {
           x2 = fma(v, v, x2);
         }
         x2 = eff_wsum(x2);
-        eff_project<MDF_CMAX>(col, Qb, c, n, lane, nullptr);
-        eff_project<MDF_CMAX>(col, Qb, c, n, lane, nullptr);
+        project_out<64, MDF_CMAX, true>(col, Qb, c, n, nullptr);
+        project_out<64, MDF_CMAX, true>(col, Qb, c, n, nullptr);
         double coef[K];
 #pragma unroll
         for (int r = 0; r < K; ++r) coef[r] = 0.0;
-        eff_project<K>(col, Rb, q, n, lane, coef);
-        eff_project<K>(col, Rb, q, n, lane, coef);
-        const double nv = eff_norm2(col, n, lane);
+        project_out<64, K, true>(col, Rb, q, n, nullptr, coef);   // the accepted u_b before it, or zero columns
+        project_out<64, K, true>(col, Rb, q, n, nullptr, coef);
+        const double nv = team_norm2<64, true>(col, n, nullptr);
         const bool acc = nv > MDF_TAU * x2;            // NaN / not above the threshold: dropped
         const double rqq = acc ? sqrt(nv) : 0.0;
         const double inv = acc ? 1.0 / rqq : 0.0;

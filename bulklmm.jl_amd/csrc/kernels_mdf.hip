@@ -22,12 +22,13 @@
 //              per pass, u_q -- folded into S at once -- then factors S per (locus, trait) in its epilogue.
 //   guard      (null-exact, c >= 2, traits launch_illcond_flag listed: nearly collinear weighted covariates at h2 -> 1):
 //              k_mdf_qr recomputes their columns with an orthonormal basis of span(Z~) from Gram-Schmidt with re-orthogonalisation
-//              and explicit residuals (k_scan_qr's method, kernels_dyn.hip).
+//              and explicit residuals (ortho_basis.h).
 //
 // Layout of the scan kernels: one wave = 64 consecutive loci (one per lane) x TJ traits; the traits are wave-uniform, so their
 // panel values come in through scalar loads and every lane reuses them for its own locus (k vector loads per individual, k TJ
 // FMAs for the grid form).  Four waves per workgroup share the loci (the Xt rows hit L1) and take four trait groups.
 #include "blmm_internal.h"
+#include "ortho_basis.h"
 #include <cmath>
 
 namespace blmm {
@@ -338,32 +339,6 @@ __global__ void __launch_bounds__(256) k_mdf_exact(MdfArgs a) {
 }
 
 // ---- the conditioning guard's re-scan of listed traits (null-exact, c >= 2) ------------------------------------------------------
-// block-wide sums of NV values per thread (256 threads), fixed order
-template <int NV>
-__device__ __forceinline__ void mdf_block_sum(double (&v)[NV], double* s_red /* [4][NV] */) {
-#pragma unroll
-  for (int q = 0; q < NV; ++q)
-    for (int off = 32; off > 0; off >>= 1) v[q] += __shfl_xor(v[q], off);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int q = 0; q < NV; ++q) s_red[w * NV + q] = v[q];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < NV; ++q) v[q] = (s_red[q] + s_red[NV + q]) + (s_red[2 * NV + q] + s_red[3 * NV + q]);
-}
-// tgt (n doubles) -= its components along the orthonormal columns Qb[0 .. nq)
-__device__ __forceinline__ void mdf_project_out(double* tgt, const double* Qb, int nq, int n, double* s_red) {
-  for (int r = 0; r < nq; ++r) {
-    double t[1] = {0.0};
-    for (int k = threadIdx.x; k < n; k += 256) t[0] = fma(Qb[(size_t)r * n + k], tgt[k], t[0]);
-    mdf_block_sum<1>(t, s_red);
-    for (int k = threadIdx.x; k < n; k += 256) tgt[k] = fma(-t[0], Qb[(size_t)r * n + k], tgt[k]);
-  }
-}
-
 // One workgroup per listed trait at a time (grid-stride over the device count stat[ST_ILLCOND]); buf: (c + 2) n doubles (weights'
 // square roots, the orthonormal basis, the unit trait residual), in LDS or in a per-workgroup slab of global memory.
 template <int K>
@@ -385,34 +360,10 @@ __global__ void __launch_bounds__(256) k_mdf_qr(int n, int c, const double* __re
   int nnan = 0;
   for (int64_t item = blockIdx.x; item < cnt; item += gridDim.x) {
     const int64_t j = list[item];
-    const double h2 = h2v[j];
-    const double delta = h2 / (1.0 - h2);
-    __syncthreads();
-    for (int k = threadIdx.x; k < n; k += 256) {
-      const double s = sqrt(fabs(1.0 / fma(delta, lam[k], 1.0)));
-      Sw[k] = s;
-      for (int q = 0; q < c; ++q) Qb[(size_t)q * n + k] = s * Z0[(size_t)q * n + k];
-      yb[k] = s * Yt[(int64_t)k * ldy + j];
-    }
-    for (int q = 0; q < c; ++q) {
-      double* col = Qb + (size_t)q * n;
-      mdf_project_out(col, Qb, q, n, s_red);
-      mdf_project_out(col, Qb, q, n, s_red);   // twice is enough
-      double nn[1] = {0.0};
-      for (int k = threadIdx.x; k < n; k += 256) nn[0] = fma(col[k], col[k], nn[0]);
-      mdf_block_sum<1>(nn, s_red);
-      const double inv = 1.0 / sqrt(nn[0]);
-      for (int k = threadIdx.x; k < n; k += 256) col[k] *= inv;
-    }
-    mdf_project_out(yb, Qb, c, n, s_red);
-    mdf_project_out(yb, Qb, c, n, s_red);
-    {
-      double nn[1] = {0.0};
-      for (int k = threadIdx.x; k < n; k += 256) nn[0] = fma(yb[k], yb[k], nn[0]);
-      mdf_block_sum<1>(nn, s_red);
-      const double inv = 1.0 / sqrt(nn[0]);
-      for (int k = threadIdx.x; k < n; k += 256) yb[k] *= inv;
-    }
+    const double nn = weighted_basis<256, 1, true>(n, c, h2v[j], lam, [&](int q, int k) { return Z0[(size_t)q * n + k]; },
+                                                   Yt + j, ldy, Sw, Qb, yb, s_red);
+    const double inv = 1.0 / sqrt(nn);
+    for (int k = threadIdx.x; k < n; k += 256) yb[k] *= inv;
     __syncthreads();
     for (int64_t l = threadIdx.x; l < nloci; l += 256) {
       const double* xp = Xt + l * K;
@@ -531,16 +482,8 @@ int launch_mdf_scan(blmm_ctx* ctx, const MdfArgs& a, bool exact) {
 int launch_mdf_qr(blmm_ctx* ctx, const NullModel& nm, const double* Yt, int64_t ldy, const double* Xt, int64_t ldx, int64_t nloci, int k,
                   const double* Z0, const double* lam, const double* h2, const int* list, double* L, int64_t ldL, int64_t* stat) {
   if (nloci <= 0 || nm.c < 2) return BLMM_OK;
-  const size_t per = (size_t)(nm.c + 2) * nm.n;
-  const unsigned grid = (unsigned)(2 * (ctx->num_cus > 0 ? ctx->num_cus : 256));
-  double* slab = nullptr;
-  size_t lds = sizeof(double) * per;
-  if (lds > 64 * 1024) {
-    int rc = ensure(ctx, ctx->qrSlab, sizeof(double) * per * grid);
-    if (rc) return rc;
-    slab = ptr<double>(ctx->qrSlab);
-    lds = 0;
-  }
+  size_t lds; double* slab; unsigned grid;
+  if (int rc = qr_workspace(ctx, nm.c, nm.n, &lds, &slab, &grid)) return rc;
 #define QR(K) do { if (lds > 48 * 1024) BLMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mdf_qr<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
     hipLaunchKernelGGL(k_mdf_qr<K>, dim3(grid), dim3(256), lds, ctx->stream, nm.n, nm.c, Yt, ldy, Xt, ldx, nloci, Z0, lam, h2, list, slab, L, ldL, stat); } while (0)
   switch (k) {

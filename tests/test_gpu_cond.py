@@ -230,6 +230,21 @@ def test_conditioning_guard(blmm):
     assert_cond_close(r2["L"], r2["h2_null_list"], Y, G, K, cond, assert_lod_close, Covar=Cov)
 
 
+def test_conditioning_guard_in_the_global_memory_slab(blmm):
+    """n = 900 with c + s = 8 (intercept, four covariates, three loci): the (c + s + 2) n doubles of k_cond_qr's basis are 72 KB,
+    beyond the 64 KiB that stay in LDS, so every workgroup builds it in its slab of global memory (qr_workspace)."""
+    m, p = 12, 130
+    Y, G, K, Cov = make_data(n=900, p=p, m=m, seed=90038, ncov=4)
+    cond = _cond(np.random.default_rng(903), m, p, 3)
+    cond[0] = [5, 77, 120]                                      # one trait with all three
+    blmm.default_context().set_tuning("illcond_rho", 2)         # every trait through the re-scan (reset by the conftest fixture)
+    r = blmm.bulkscan_cond(Y, G, K, cond, Cov, method="null-exact", return_status=True)
+    assert r["status"].n_illcond_rescan == m
+    nrule, nband = assert_cond_close(r["L"], r["h2_null_list"], Y, G, K, r["cond"], assert_lod_close, Covar=Cov)
+    if nband == 0:
+        assert r["n_rule_zero"] == nrule
+
+
 @pytest.mark.parametrize("method", ["null-grid", "null-exact"])
 def test_bxd_shape_peaks(blmm, method):
     n, p, m = 79, 7321, 35554

@@ -1150,11 +1150,12 @@ def test_illconditioned_weighted_covariates_at_the_h2_one_boundary(blmm):
     assert np.abs(h2 - ref.h2_null_list).max() <= 1e-6
 
 
-@pytest.mark.parametrize("ncov,n", [(1, 79), (2, 79), (7, 79), (3, 200), (5, 300)])
+@pytest.mark.parametrize("ncov,n", [(1, 79), (2, 79), (7, 79), (10, 79), (3, 200), (5, 300)])
 def test_qr_grade_rescan_equals_oracle_when_every_trait_is_flagged(blmm, ncov, n, monkeypatch):
     """Tuning illcond_rho = 2 puts EVERY trait on the guard's list (the pivot shares are <= 1): the orthogonalised re-scan kernel
     (k_scan_qr) is then compared with the oracle as a whole, for the low-rank path (c = 2, 3), the full-rank path (c = 8, 6)
-    and beyond the LDS Jacobi (n = 200, 300)."""
+    and beyond the LDS Jacobi (n = 200, 300); c = 11 is the kernel's form for more than eight columns, whose projections take
+    two chunks of coefficients."""
     Y, G, K, Cov = make_data(n=n, p=333, m=70, seed=9100 + ncov, ncov=ncov, bxd=(n == 79))
     dctx = blmm.default_context()
     dctx.set_tuning("illcond_rho", 2)                  # (reset by the conftest fixture)
@@ -1171,6 +1172,16 @@ def test_qr_grade_rescan_equals_oracle_when_every_trait_is_flagged(blmm, ncov, n
     s = blmm.scan(y, G, K, Cov)                        # scan(): the trait's own LOD vector takes the guard too
     r = O.bulkscan_null(Y[:, :1], G, K, Covar=Cov, h2_override=[s["h2_null"]])
     assert_lod_close(s["lod"], r.L[:, 0])
+
+
+def test_qr_grade_rescan_in_the_global_memory_slab(blmm):
+    """n = 900 with c = 8: the (c + 2) n doubles of k_scan_qr's basis are 72 KB, beyond the 64 KiB that stay in LDS, so every
+    workgroup builds it in its slab of global memory (qr_workspace)."""
+    Y, G, K, Cov = make_data(n=900, p=130, m=12, seed=9907, ncov=7)
+    blmm.default_context().set_tuning("illcond_rho", 2)           # (reset by the conftest fixture)
+    L, h2, st = _null_exact_with_status(blmm, Y, G, K, Cov)
+    assert st.n_illcond_rescan == Y.shape[1]
+    assert_lod_close(L, O.bulkscan_null(Y, G, K, Covar=Cov, h2_override=h2).L)
 
 
 def test_h2_boundary_counter_and_profile_audit(blmm):
