@@ -1479,6 +1479,88 @@ def bulkscan_multidf_dev(ctx: Context, Y, G, K, k: int, L_out, h2_out, *, method
     return st
 
 
+# ---- permutation thresholds of the k-degree-of-freedom scan (blmm_bulkscan_multidf_perms) --------------------------------------
+def _multidf_perms_checks(n: int, p: int, k, nperms: int, ncov: int, addIntercept: bool, nprobs: int):
+    """The library's refusals of blmm_bulkscan_multidf_perms that need no data (blmm_api.hip: mdf_perms_check), before any context:
+    bulkscan_perms' on nperms, the covariates and the levels, bulkscan_multidf's (null-grid's limit on k) on k, p and n."""
+    nperms = int(nperms)
+    if nperms < 0:
+        raise BulkLMMError("The required number of permutations must be a positive integer.", -9)
+    if nprobs > 64:
+        raise BulkLMMError("bulkscan_multidf_perms: 0 .. 64 threshold levels", -1)
+    if nperms > BPERM_MAX_NPERMS:
+        raise BulkLMMError("bulkscan_multidf_perms: more than 16384 permutations (the per-trait sort runs in LDS)", -10)
+    if _null_covariates(ncov, addIntercept) > BPERM_MAX_COVARIATES:
+        raise BulkLMMError("bulkscan_multidf_perms: more than 8 null covariates (incl. intercept) are not supported", -10)
+    k = int(k)
+    if k < 1 or p % k != 0:
+        raise BulkLMMError("bulkscan_multidf_perms: the number of columns of G must be a multiple of k >= 1", -2)
+    if k > L.BLMM_MULTIDF_MAX_K_GRID:
+        raise BulkLMMError("bulkscan_multidf_perms: takes 1 <= k <= %d" % L.BLMM_MULTIDF_MAX_K_GRID, -10)
+    _check_n(n)
+    return k, nperms
+
+
+def bulkscan_multidf_perms(Y, G, K, k: int, Covar=None, *, nperms: int = 1024, rndseed: int = 0, perm_idx=None,
+                           signif_level=(0.10, 0.05), weights=None, prior_variance: float = 0.0, prior_sample_size: float = 0.0,
+                           addIntercept: bool = True, reml: bool = False, optim_interval: int = 1, decomp_scheme: str = "eigen",
+                           ctx: Optional[Context] = None, return_status: bool = False) -> dict:
+    """Permutation thresholds for the k-degree-of-freedom scan (blmm_bulkscan_multidf_perms): bulkscan_perms with bulkscan_multidf's
+    loci.  G is n x (P k), locus l the columns l k .. l k + k - 1; every trait's null model is bulkscan_perms' (h2_null and sigma2_e
+    bit for bit, the same permutation set for the same rndseed / perm_idx), and permutation b of trait j is scanned as
+    L_b[l] = -(n/2) log10(1 - |P_Q (I - P_Z) v_b|^2 / |v_b|^2), v_b the permuted, reweighted null residual and Q the locus's accepted
+    columns (bulkscan_multidf's rank rule at the trait's own weights, 1 <= k <= 8).  The unpermuted column is bulkscan_multidf's
+    null-exact LOD.  Only the reductions leave the device.  Returns bulkscan_perms' keys: {"h2_null", "sigma2_e", "lod_max",
+    "lod_argmax" (0-based LOCUS, -1 with lod_max = -inf when nothing compares): m each; "max_perms": nperms x m; "thresholds":
+    len(signif_level) x m; "pvals_perm": m; "probs" [; "status"]}.  nperms = 0: thresholds and p-values NaN."""
+    Y, G, K, n, m, p = _host_arrays(Y, G, K)
+    cov, ncov, w, addIntercept = _host_covariates(Covar, weights, n, addIntercept)
+    probs = _probs(signif_level)
+    k, nperms = _multidf_perms_checks(n, p, k, nperms, ncov, addIntercept, probs.shape[0])
+    pidx = _perm_idx(perm_idx, n, nperms)
+    if pidx is not None and pidx.size and (pidx.min() < 0 or pidx.max() >= n):
+        raise BulkLMMError("bulkscan_multidf_perms: perm_idx entries must lie in 0 .. n - 1", -1)
+    o = _opts(L.BLMM_NULL_EXACT, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
+    ctx = ctx or default_context()  # after the argument checks: those must not need a GPU
+    st = L.blmm_status()
+    h2, s2, mx, pv = np.empty(m), np.empty(m), np.empty(m), np.empty(m)
+    arg = np.empty(m, dtype=np.int64)
+    mp = np.empty((max(nperms, 1), m), order="F")
+    thr = np.empty((probs.shape[0], m), order="F")
+    ctx.check(ctx.lib.blmm_bulkscan_multidf_perms(ctx.h, C.byref(o), _p(Y), n, m, _p(G), p, k, _p(cov), ncov, _p(K), _p(w), nperms,
+                                                  C.c_uint64(int(rndseed)), _p(pidx), _p(probs), probs.shape[0], _p(h2), _p(s2), _p(mx),
+                                                  _p(arg), _p(mp), _p(thr), _p(pv), C.byref(st)))
+    _raise_status(st)
+    out = {"h2_null": h2, "sigma2_e": s2, "lod_max": mx, "lod_argmax": arg, "max_perms": mp[:nperms], "thresholds": thr,
+           "pvals_perm": pv, "probs": probs}
+    if return_status:
+        out["status"] = st
+    return out
+
+
+def bulkscan_multidf_perms_dev(ctx: Context, Y, G, K, k: int, h2_out, sigma2_out, lod_max_out, lod_argmax_out, max_perms_out=None,
+                               thr_out=None, pval_out=None, *, nperms: int, seed: int = 0, perm_idx=None, signif_level=(0.10, 0.05),
+                               Covar=None, weights=None, addIntercept: bool = True, prior_variance: float = 0.0,
+                               prior_sample_size: float = 0.0, reml: bool = False, optim_interval: int = 1,
+                               decomp_scheme: str = "eigen", status: bool = False):
+    """blmm_bulkscan_multidf_perms_dev on torch tensors in bulkscan_perms_dev's layout: Y (m, n), G (p, n) with p = P k, K (n, n);
+    h2_out / sigma2_out / lod_max_out / pval_out (m,) float64, lod_argmax_out (m,) int64 (loci), max_perms_out (m, nperms),
+    thr_out (m, len(signif_level)), perm_idx (nperms, n) int32 or None (the library's generator with `seed`).  Enqueues on the
+    context's stream (status=True synchronises it)."""
+    m, n = Y.shape
+    p = G.shape[0]
+    ncov, addIntercept, st = _dev_args(Covar, addIntercept, status)
+    probs = _probs(signif_level)
+    k, nperms = _multidf_perms_checks(n, p, k, nperms, ncov, addIntercept, probs.shape[0])
+    o = _opts(L.BLMM_NULL_EXACT, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
+    ctx.check(ctx.lib.blmm_bulkscan_multidf_perms_dev(ctx.h, C.byref(o), Y.data_ptr(), n, m, G.data_ptr(), p, k, _dptr(Covar), ncov,
+                                                      K.data_ptr(), _dptr(weights), nperms, C.c_uint64(int(seed)), _dptr(perm_idx),
+                                                      _p(probs), probs.shape[0], h2_out.data_ptr(), sigma2_out.data_ptr(),
+                                                      lod_max_out.data_ptr(), lod_argmax_out.data_ptr(), _dptr(max_perms_out),
+                                                      _dptr(thr_out), _dptr(pval_out), C.byref(st) if status else None))
+    return st
+
+
 # ---- effects at chosen tests (blmm_bulkscan_effects) ---------------------------------------------------------------------------
 def _effects_checks(method: str, n: int, p: int, k, ncov: int, addIntercept: bool):
     """The library's refusals of blmm_bulkscan_effects that need no data (blmm_api.hip: effects_check), before any context."""

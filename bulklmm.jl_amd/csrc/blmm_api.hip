@@ -2338,6 +2338,8 @@ int blmm_scan_perms_f32(blmm_ctx* ctx, const blmm_opts* opts, const double* y, i
 // The permutation test of every trait (include/bulklmm_hip.h: blmm_bulkscan_perms): the bulk null fit, then trait chunks of
 // panel columns (kernels_bperm.hip) through the table kernel's reduce-in-epilogue instantiation -- its slot partials and
 // k_red_final give every column's maximum exactly as k_colmax on the stored column would -- and the per-trait summary.
+// blmm_bulkscan_multidf_perms is the same call with k > 0: loci of k adjacent columns, scanned by the k-df table / reducing scan
+// kernels (kernels_mdf.hip) on the uncentred marker rotation; k = 0 is the 1-df form everywhere below.
 struct BpermOut {
   double *h2, *sigma2, *lod_max; int64_t* lod_argmax; double *max_perms, *thr, *pval;
 };
@@ -2357,15 +2359,34 @@ static int bperm_check(blmm_ctx* ctx, const blmm_opts* opts, int64_t n, int64_t 
     return fail(ctx, BLMM_ERR_UNSUPPORTED, w + ": more than 8 null covariates (incl. intercept) are not supported");
   return BLMM_OK;
 }
+// ... of blmm_bulkscan_multidf_perms: bperm_check's, then blmm_bulkscan_multidf's on k and p (null-grid's limit on k: the scan is
+// the null-grid algebra) and on n
+static_assert(CTPL == BLMM_MULTIDF_MAX_COVARIATES, "bperm_check's covariate limit is the k-df kernels'");
+static int mdf_perms_check(blmm_ctx* ctx, const blmm_opts* opts, int64_t n, int64_t m, int64_t p, int64_t k, const double* Covar,
+                           int64_t ncov, int64_t nperms, const double* probs, int64_t nprobs, bool have_in, const BpermOut& o) {
+  int rc = bperm_check(ctx, opts, n, m, p, Covar, ncov, nperms, probs, nprobs, have_in, o, "bulkscan_multidf_perms");
+  if (rc) return rc;
+  if (k < 1 || p % k != 0) return fail(ctx, BLMM_ERR_DIM, "bulkscan_multidf_perms: the number of columns of G must be a multiple of k >= 1");
+  if (k > BLMM_MULTIDF_MAX_K_GRID) return fail(ctx, BLMM_ERR_UNSUPPORTED, "bulkscan_multidf_perms: takes 1 <= k <= 8");
+  if (n > 2048) return fail(ctx, BLMM_ERR_UNSUPPORTED, "more than 2048 individuals: the device eigensolver (tridiagonalisation + divide and conquer) stops at n = 2048");
+  return BLMM_OK;
+}
+
+// Slots of the reduction partials: two per 128 markers (the table kernel's tiles), or one per 64 loci of k columns (k_mdf_grid_red)
+static int bperm_nslot(int64_t p, int64_t k) { return k > 0 ? (int)((p / k + 63) / 64) : 2 * (int)((p + 127) / 128); }
 
 // Traits per chunk: per panel column its k-major panel (npad doubles), its reduction partials (nslot x 12 bytes), bin, maximum and
-// marker; per trait its row of marker norms, r0 and the panel coefficients.  Default budget 4 GiB of workspace.
-static int64_t bperm_chunk_traits(const blmm_ctx* ctx, int64_t npad, int64_t ldx, int64_t n, int64_t p, int64_t nperms) {
+// marker; per trait its row of marker norms (k > 0: its k (k + 1) / 2 factor entries per locus), r0 and the panel coefficients.
+// Default budget 4 GiB of workspace.  At most 65535 traits (a grid extent of launch_isx / launch_mdf_table / the summary) and, k > 0,
+// MDF_RED_MAX_COLS panel columns.
+static int64_t bperm_chunk_traits(const blmm_ctx* ctx, int64_t npad, int64_t ldx, int64_t n, int64_t p, int64_t nperms, int64_t k = 0) {
   const int64_t np1 = nperms + 1;
-  const int nslot = 2 * (int)((p + 127) / 128);
+  const int nslot = bperm_nslot(p, k);
   const double col_bytes = 8.0 * npad + 12.0 * nslot + 20.0 + 8.0 * (CMAX + 1);
-  const double trait_bytes = np1 * col_bytes + 8.0 * (double)ldx + 8.0 * n;
+  const double table_bytes = k > 0 ? 8.0 * (double)(k * (k + 1) / 2) * (double)(p / k) : 8.0 * (double)ldx;
+  const double trait_bytes = np1 * col_bytes + table_bytes + 8.0 * n;
   int64_t mt_max = ctx->tune.bulk_perm_cols > 0 ? ctx->tune.bulk_perm_cols / np1 : (int64_t)((double)(4ll << 30) / trait_bytes);
+  if (k > 0) mt_max = std::min<int64_t>(mt_max, MDF_RED_MAX_COLS / np1);
   return std::max<int64_t>(1, std::min<int64_t>(mt_max, 65535));
 }
 
@@ -2374,32 +2395,47 @@ struct BpermMerge { double* gmx = nullptr; int64_t* garg = nullptr; };
 
 // Chunks of whole traits of one rotation (P: the p markers and the m rotated traits; nm its null model; o.h2 the traits' h2): the
 // isx / panel / reduce-in-epilogue scan / k_red_final chain, then the per-trait summary into o (markers + row0).  mg (LOCO): every
-// chunk's column maxima also fold into the genome-wide buffer.
+// chunk's column maxima also fold into the genome-wide buffer.  k > 0: P.Xt is the uncentred rotation, the table is k_mdf_table's
+// factors at the chunk's own h2 values (its "grid"; bin[column] = trait, as for launch_isx), the scan k_mdf_grid_red, and every
+// index a locus.
 static int bperm_chunks(blmm_ctx* ctx, const Pipe& P, const NullModel& nm, int64_t m, int64_t p, const int32_t* perm, int64_t nperms,
-                        int64_t mt_max, const BpermProbs& pr, int64_t nprobs, const BpermOut& o, int64_t row0, const BpermMerge* mg) {
+                        int64_t mt_max, const BpermProbs& pr, int64_t nprobs, const BpermOut& o, int64_t row0, const BpermMerge* mg,
+                        int64_t k = 0) {
   int rc;
   const int64_t np1 = nperms + 1;
-  const int nslot = 2 * (int)((p + 127) / 128);
+  const int nslot = bperm_nslot(p, k);
+  const int64_t nloci = k > 0 ? p / k : p, ntab = k * (k + 1) / 2;
   const bool summary = o.lod_max || o.lod_argmax || o.max_perms || o.thr || o.pval;
   for (int64_t j0 = 0; j0 < m; j0 += mt_max) {
     const int64_t mt = std::min(mt_max, m - j0), ncols = mt * np1, ldp = round_up(ncols, 128), ldm = round_up(ncols, 64);
     if ((rc = ensure(ctx, ctx->panels, sizeof(double) * (size_t)P.npad * ldp)) ||
-        (rc = ensure(ctx, ctx->isx, sizeof(double) * (size_t)P.ldx * mt)) ||
+        (rc = k > 0 ? ensure(ctx, ctx->mdfT, sizeof(double) * (size_t)ntab * (size_t)nloci * mt)
+                    : ensure(ctx, ctx->isx, sizeof(double) * (size_t)P.ldx * mt)) ||
         (rc = ensure(ctx, ctx->redbuf, (sizeof(double) + sizeof(int)) * (size_t)nslot * (size_t)ldm)) ||
         (rc = ensure(ctx, ctx->bperm, (sizeof(double) + sizeof(int64_t) + sizeof(int)) * (size_t)ldp))) return rc;
     double* mx = ptr<double>(ctx->bperm);
     int64_t* arg = reinterpret_cast<int64_t*>(mx + ldp);
     int* bin = reinterpret_cast<int*>(arg + ldp);
     const double* h2c = o.h2 + j0;
-    if (p > 0 && (rc = launch_isx(ctx, nm, P.Xt, P.ldx, p, P.Z0, P.lam, h2c, (int)mt, ptr<double>(ctx->isx), P.ldx, P.stat))) return rc;
+    if (p > 0 && (rc = k > 0 ? launch_mdf_table(ctx, nm, P.Xt, P.ldx, nloci, (int)k, P.Z0, P.lam, h2c, (int)mt, ptr<double>(ctx->mdfT))
+                             : launch_isx(ctx, nm, P.Xt, P.ldx, p, P.Z0, P.lam, h2c, (int)mt, ptr<double>(ctx->isx), P.ldx, P.stat))) return rc;
     if ((rc = launch_bperm_panels(ctx, nm, P.Yt + j0, P.ldy, P.Z0, P.lam, h2c, mt, perm, nperms, ptr<double>(ctx->panels), ldp, bin, P.stat))) return rc;
     if (p > 0) {
       RedArgs r;
       r.pmax = ptr<double>(ctx->redbuf); r.parg = reinterpret_cast<int*>(r.pmax + (size_t)nslot * ldm); r.ldm = ldm;
-      ScanArgs a = scan_args(ctx, P, ptr<double>(ctx->panels), ldp, nullptr, 0, ncols);
-      a.isx = ptr<double>(ctx->isx); a.ld_isx = P.ldx; a.bin = bin;
-      a.Pv = nullptr; a.red = r;
-      if ((rc = launch_scan_table(ctx, a)) || (rc = launch_red_final(ctx, r, nslot, ncols, mx, arg))) return rc;
+      if (k > 0) {
+        MdfArgs a;
+        a.Xt = P.Xt; a.ldx = P.ldx; a.nloci = nloci; a.k = (int)k; a.n = P.n; a.m = ncols;
+        a.P = ptr<double>(ctx->panels); a.ldp = ldp; a.pstride = 0; a.c = P.c;
+        a.T = ptr<double>(ctx->mdfT); a.bin = bin; a.L = nullptr; a.ldL = 0; a.stat = P.stat;
+        rc = launch_mdf_scan_red(ctx, a, r);
+      } else {
+        ScanArgs a = scan_args(ctx, P, ptr<double>(ctx->panels), ldp, nullptr, 0, ncols);
+        a.isx = ptr<double>(ctx->isx); a.ld_isx = P.ldx; a.bin = bin;
+        a.Pv = nullptr; a.red = r;
+        rc = launch_scan_table(ctx, a);
+      }
+      if (rc || (rc = launch_red_final(ctx, r, nslot, ncols, mx, arg))) return rc;
     } else {                                    // no markers: every column's maximum is -inf at marker -1 (k_colmax's empty column)
       if ((rc = fill(ctx, mx, ncols, -INFINITY))) return rc;
       BLMM_HIP(hipMemsetAsync(arg, 0xff, sizeof(int64_t) * (size_t)ncols, ctx->stream));
@@ -2412,9 +2448,11 @@ static int bperm_chunks(blmm_ctx* ctx, const Pipe& P, const NullModel& nm, int64
 }
 
 static int bulk_perms_impl(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG, int64_t p,
-                           const double* dCovar, int64_t ncov, const double* dK, const double* dweights, int64_t nperms, uint64_t seed,
-                           const int32_t* dperm_idx, const double* probs, int64_t nprobs, const BpermOut& o, blmm_status* status) {
-  int rc = bperm_check(ctx, opts, n, m, p, dCovar, ncov, nperms, probs, nprobs, dY && dG && dK, o);
+                           int64_t k, const double* dCovar, int64_t ncov, const double* dK, const double* dweights, int64_t nperms,
+                           uint64_t seed, const int32_t* dperm_idx, const double* probs, int64_t nprobs, const BpermOut& o,
+                           blmm_status* status) {
+  int rc = k > 0 ? mdf_perms_check(ctx, opts, n, m, p, k, dCovar, ncov, nperms, probs, nprobs, dY && dG && dK, o)
+                 : bperm_check(ctx, opts, n, m, p, dCovar, ncov, nperms, probs, nprobs, dY && dG && dK, o);
   if (rc || (rc = enter_device(ctx))) return rc;
   BpermProbs pr;
   for (int t = 0; t < 64; ++t) pr.v[t] = t < nprobs ? probs[t] : 0.0;
@@ -2423,13 +2461,21 @@ static int bulk_perms_impl(blmm_ctx* ctx, const blmm_opts* opts, const double* d
   ctx->perm_ready = false;
   clear_last(ctx);                              // no matrix of this call (and the workspace it sat in is reused)
   // the traits are rotated as scan rotates its one (launch_rotate picks its kernel by the column count as well as by n)
-  if ((rc = prepare(ctx, opts, dY, n, 0, dG, p, dCovar, ncov, dK, dweights, 1, P, tm))) return rc;
+  // (k > 0: the markers are left to the uncentred rotation below, as blmm_bulkscan_multidf rotates them)
+  if ((rc = prepare(ctx, opts, dY, n, 0, dG, p, dCovar, ncov, dK, dweights, 1, P, tm, false, false, /*skip_markers*/ k > 0))) return rc;
   P.m = m; P.ldy = round_up(m > 0 ? m : 1, 128);
   if ((rc = ensure(ctx, ctx->Yt, sizeof(double) * (size_t)P.npad * P.ldy))) return rc;
   P.Yt = ptr<double>(ctx->Yt);
   if ((rc = launch_rotate_single(ctx, ptr<double>(ctx->Rp), P.ldr, P.n, P.npad, dY, m, P.Yt, P.ldy))) return rc;
   const NullModel nm = null_model(P, opts);
   if (m > 0 && (rc = launch_brent(ctx, nm, P.Yt, P.ldy, m, P.Z0, P.lam, o.h2, o.sigma2, nullptr, P.stat))) return rc;
+  if (k > 0 && p > 0 && m > 0) {
+    if ((rc = ensure(ctx, ctx->mdfR, sizeof(double) * (size_t)P.npad * P.ldr)) ||
+        (rc = ensure(ctx, ctx->Xt, sizeof(double) * (size_t)P.npad * P.ldx))) return rc;
+    if ((rc = launch_mdf_rawrot(ctx, ptr<double>(ctx->U), dweights, P.n, P.npad, P.ldr, ptr<double>(ctx->mdfR)))) return rc;
+    P.Xt = ptr<double>(ctx->Xt);
+    if ((rc = launch_rotate(ctx, ptr<double>(ctx->mdfR), P.ldr, P.n, P.npad, dG, p, P.Xt, P.ldx, P.ldx))) return rc;
+  }
   tm.mark();
   const int32_t* perm = dperm_idx;
   if (m > 0 && nperms > 0 && !perm) {
@@ -2437,8 +2483,8 @@ static int bulk_perms_impl(blmm_ctx* ctx, const blmm_opts* opts, const double* d
     ctx->perm_ready = false;                    // consumed here, not by a later launch_perm_panel
     perm = ptr<int32_t>(ctx->perm);
   }
-  const int64_t mt_max = bperm_chunk_traits(ctx, P.npad, P.ldx, n, p, nperms);
-  if ((rc = bperm_chunks(ctx, P, nm, m, p, perm, nperms, mt_max, pr, nprobs, o, 0, nullptr))) return rc;
+  const int64_t mt_max = bperm_chunk_traits(ctx, P.npad, P.ldx, n, p, nperms, k);
+  if ((rc = bperm_chunks(ctx, P, nm, m, p, perm, nperms, mt_max, pr, nprobs, o, 0, nullptr, k))) return rc;
   tm.mark();
   return end_call(ctx, P, status, &tm);
 }
@@ -2450,22 +2496,24 @@ int blmm_bulkscan_perms_dev(blmm_ctx* ctx, const blmm_opts* opts, const double* 
                             double* dthr_out, double* dpval_out, blmm_status* status) {
   if (!ctx) return BLMM_ERR_INVALID;
   const BpermOut o{dh2_out, dsigma2_out, dlod_max_out, dlod_argmax_out, dmax_perms_out, dthr_out, dpval_out};
-  return bulk_perms_impl(ctx, opts, dY, n, m, dG, p, dCovar, ncov, dK, dweights, nperms, seed, dperm_idx, probs, nprobs, o, status);
+  return bulk_perms_impl(ctx, opts, dY, n, m, dG, p, 0, dCovar, ncov, dK, dweights, nperms, seed, dperm_idx, probs, nprobs, o, status);
 }
 
-int blmm_bulkscan_perms(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, int64_t n, int64_t m, const double* G, int64_t p,
-                        const double* Covar, int64_t ncov, const double* K, const double* weights, int64_t nperms, uint64_t seed,
-                        const int32_t* perm_idx, const double* probs, int64_t nprobs, double* h2_out, double* sigma2_out,
-                        double* lod_max_out, int64_t* lod_argmax_out, double* max_perms_out, double* thr_out, double* pval_out,
-                        blmm_status* status) {
-  if (!ctx) return BLMM_ERR_INVALID;
+// The host forms of blmm_bulkscan_perms (k = 0) and blmm_bulkscan_multidf_perms (k: the call's own argument, checked here)
+static int bulk_perms_host(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, int64_t n, int64_t m, const double* G, int64_t p,
+                           int64_t k, bool mdf, const double* Covar, int64_t ncov, const double* K, const double* weights, int64_t nperms,
+                           uint64_t seed, const int32_t* perm_idx, const double* probs, int64_t nprobs, double* h2_out,
+                           double* sigma2_out, double* lod_max_out, int64_t* lod_argmax_out, double* max_perms_out, double* thr_out,
+                           double* pval_out, blmm_status* status) {
   const BpermOut ho{h2_out, sigma2_out, lod_max_out, lod_argmax_out, max_perms_out, thr_out, pval_out};
-  int rc = bperm_check(ctx, opts, n, m, p, Covar, ncov, nperms, probs, nprobs, Y && G && K, ho);
+  int rc = mdf ? mdf_perms_check(ctx, opts, n, m, p, k, Covar, ncov, nperms, probs, nprobs, Y && G && K, ho)
+               : bperm_check(ctx, opts, n, m, p, Covar, ncov, nperms, probs, nprobs, Y && G && K, ho);
   if (rc) return rc;
   // caller-supplied permutations are indices into the trait's n entries: checked here, before a kernel reads through them
   if (perm_idx && nperms > 0)
     for (int64_t e = 0; e < n * nperms; ++e)
-      if (perm_idx[e] < 0 || perm_idx[e] >= n) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_perms: perm_idx entries must lie in 0 .. n - 1");
+      if (perm_idx[e] < 0 || perm_idx[e] >= n)
+        return fail(ctx, BLMM_ERR_INVALID, std::string(mdf ? "bulkscan_multidf_perms" : "bulkscan_perms") + ": perm_idx entries must lie in 0 .. n - 1");
   HostCall hc(ctx);
   // device outputs in outL: h2, sigma2, lod_max, lod_argmax (m each), pval (m), thresholds (nprobs x m), max_perms (nperms x m)
   const size_t mm = (size_t)m;
@@ -2476,12 +2524,48 @@ int blmm_bulkscan_perms(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, i
   HostCall::In in;
   const int32_t* dperm;
   if ((rc = hc.inputs(Y, n, m, G, p, K, Covar, ncov, weights, false, &in)) || (rc = up_perm_idx(hc, perm_idx, n, nperms, &dperm)) ||
-      (rc = bulk_perms_impl(ctx, opts, in.Y, n, m, in.G, p, in.Cov, in.ncov, in.K, in.W, nperms, seed, dperm, probs, nprobs, o, status))) return rc;
+      (rc = bulk_perms_impl(ctx, opts, in.Y, n, m, in.G, p, k, in.Cov, in.ncov, in.K, in.W, nperms, seed, dperm, probs, nprobs, o, status))) return rc;
   if ((rc = hc.down(h2_out, o.h2, sizeof(double) * mm)) || (rc = hc.down(sigma2_out, o.sigma2, sizeof(double) * mm)) ||
       (rc = hc.down(lod_max_out, o.lod_max, sizeof(double) * mm)) || (rc = hc.down(lod_argmax_out, o.lod_argmax, sizeof(int64_t) * mm)) ||
       (rc = hc.down(pval_out, o.pval, sizeof(double) * mm)) || (rc = hc.down(thr_out, o.thr, sizeof(double) * mm * nprobs))) return rc;
   if (max_perms_out && (rc = copy_to_host(ctx, max_perms_out, o.max_perms, sizeof(double) * mm * nperms))) return rc;
   return (rc = hc.finish()) ? rc : check_sticky(ctx);
+}
+
+int blmm_bulkscan_perms(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, int64_t n, int64_t m, const double* G, int64_t p,
+                        const double* Covar, int64_t ncov, const double* K, const double* weights, int64_t nperms, uint64_t seed,
+                        const int32_t* perm_idx, const double* probs, int64_t nprobs, double* h2_out, double* sigma2_out,
+                        double* lod_max_out, int64_t* lod_argmax_out, double* max_perms_out, double* thr_out, double* pval_out,
+                        blmm_status* status) {
+  if (!ctx) return BLMM_ERR_INVALID;
+  return bulk_perms_host(ctx, opts, Y, n, m, G, p, 0, false, Covar, ncov, K, weights, nperms, seed, perm_idx, probs, nprobs, h2_out,
+                         sigma2_out, lod_max_out, lod_argmax_out, max_perms_out, thr_out, pval_out, status);
+}
+
+// The k-df permutation test (include/bulklmm_hip.h: blmm_bulkscan_multidf_perms).  A pending -log10 p request does not apply to this
+// call: disarmed, as by every entry point that writes no matrix.
+int blmm_bulkscan_multidf_perms_dev(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG,
+                                    int64_t p, int64_t k, const double* dCovar, int64_t ncov, const double* dK, const double* dweights,
+                                    int64_t nperms, uint64_t seed, const int32_t* dperm_idx, const double* probs, int64_t nprobs,
+                                    double* dh2_out, double* dsigma2_out, double* dlod_max_out, int64_t* dlod_argmax_out,
+                                    double* dmax_perms_out, double* dthr_out, double* dpval_out, blmm_status* status) {
+  if (!ctx) return BLMM_ERR_INVALID;
+  (void)pv_take(ctx);
+  const BpermOut o{dh2_out, dsigma2_out, dlod_max_out, dlod_argmax_out, dmax_perms_out, dthr_out, dpval_out};
+  // (checked here as in the host form: k < 1 must be refused, not read as the 1-df form)
+  if (int rc = mdf_perms_check(ctx, opts, n, m, p, k, dCovar, ncov, nperms, probs, nprobs, dY && dG && dK, o)) return rc;
+  return bulk_perms_impl(ctx, opts, dY, n, m, dG, p, k, dCovar, ncov, dK, dweights, nperms, seed, dperm_idx, probs, nprobs, o, status);
+}
+
+int blmm_bulkscan_multidf_perms(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, int64_t n, int64_t m, const double* G, int64_t p,
+                                int64_t k, const double* Covar, int64_t ncov, const double* K, const double* weights, int64_t nperms,
+                                uint64_t seed, const int32_t* perm_idx, const double* probs, int64_t nprobs, double* h2_out,
+                                double* sigma2_out, double* lod_max_out, int64_t* lod_argmax_out, double* max_perms_out, double* thr_out,
+                                double* pval_out, blmm_status* status) {
+  if (!ctx) return BLMM_ERR_INVALID;
+  (void)pv_take(ctx);
+  return bulk_perms_host(ctx, opts, Y, n, m, G, p, k, true, Covar, ncov, K, weights, nperms, seed, perm_idx, probs, nprobs, h2_out,
+                         sigma2_out, lod_max_out, lod_argmax_out, max_perms_out, thr_out, pval_out, status);
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -544,6 +544,10 @@ int launch_mdf_rawrot(blmm_ctx* ctx, const double* U, const double* wd, int n, i
 int launch_mdf_table(blmm_ctx* ctx, const NullModel& nm, const double* Xt, int64_t ldx, int64_t nloci, int k, const double* Z0,
                      const double* lam, const double* grid_dev, int ngrid, double* T);
 int launch_mdf_scan(blmm_ctx* ctx, const MdfArgs& a, bool exact);
+// blmm_bulkscan_multidf_perms: the null-grid scan reduced in its epilogue to slot partials (r.pmax / r.parg / r.ldm, ceil(nloci / 64)
+// slots, finished by launch_red_final); a.L unused.  At most MDF_RED_MAX_COLS columns (a.m) a launch: 65535 grid rows of 4 x 8 columns
+constexpr int64_t MDF_RED_MAX_COLS = 65535ll * 32;
+int launch_mdf_scan_red(blmm_ctx* ctx, const MdfArgs& a, const RedArgs& r);
 int launch_mdf_qr(blmm_ctx* ctx, const NullModel& nm, const double* Yt, int64_t ldy, const double* Xt, int64_t ldx, int64_t nloci, int k,
                   const double* Z0, const double* lam, const double* h2, const int* list, double* L, int64_t ldL, int64_t* stat);
    // k_bperm_summary sorts a trait's maxima in LDS (128 KB)

@@ -18,6 +18,10 @@
 //   null-grid  (weights shared per grid bin): k_mdf_table forms, per (bin g, locus l), T = L^-1 (packed k(k+1)/2, the rank rule
 //              applied) from the bin's Gram; k_mdf_grid contracts b = X_l' panel0 for every (locus, trait) and its epilogue is
 //              z = T[bin_j, l] b, R^2 = |z|^2.
+//   permutations (blmm_bulkscan_multidf_perms): the null-grid kernels with the chunk's own h2 values as the "grid" and
+//              bin[column] = the trait of the chunk, i.e. the null-grid algebra at every trait's exact heritability; the columns
+//              are kernels_bperm.hip's panel columns (trait x permutation), and k_mdf_grid_red reduces every column to slot
+//              partials (maximum, locus) in its epilogue instead of writing L.
 //   null-exact (per-trait weights): k_mdf_exact accumulates b, P (from products x_a x_b formed in registers) and, one covariate
 //              per pass, u_q -- folded into S at once -- then factors S per (locus, trait) in its epilogue.
 //   guard      (null-exact, c >= 2, traits launch_illcond_flag listed: nearly collinear weighted covariates at h2 -> 1):
@@ -254,6 +258,84 @@ __global__ void __launch_bounds__(256) k_mdf_grid(MdfArgs a) {
   if (nnan) atomicAdd((unsigned long long*)&a.stat[ST_NAN_LOD], (unsigned long long)nnan);
 }
 
+// ---- null-grid scan, reduced in the epilogue (blmm_bulkscan_multidf_perms) ------------------------------------------------------
+// k_mdf_grid's contraction and z = T b over the panel columns of a trait chunk; nothing goes to L.  Every column's 64 LODs of the wave are
+// reduced to (maximum, locus) -- candidates are (value, locus) pairs under k_colmax's order (larger value, then lower locus), a NaN
+// or a lane beyond nloci is no candidate, so the result does not depend on the order of the exchanges: four DPP steps inside the
+// 16-lane rows, then the rows across 16 and 32 lanes -- and lane 0 writes the partial of (slot = blockIdx.x, column) for k_red_final.
+// A slot without a candidate holds (-inf, -1).  NaN LODs are counted (ST_NAN_LOD) in the UNPERMUTED columns only (the first column
+// of each bin): the count is that of the data's own scan, whatever nperms is.
+template <int CTRL>
+__device__ __forceinline__ int mdf_dpp_movi(int x) { return __builtin_amdgcn_update_dpp(x, x, CTRL, 0xf, 0xf, false); }
+__device__ __forceinline__ void mdf_red_comb(double& best, int& bi, double ob, int oi) {
+  if (ob > best || (ob == best && oi >= 0 && (bi < 0 || oi < bi))) { best = ob; bi = oi; }
+}
+template <int K, int TJ>
+__global__ void __launch_bounds__(256) k_mdf_grid_red(MdfArgs a, double* pmax, int* parg, int64_t ldm) {
+  constexpr int NP = K * (K + 1) / 2;
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t j0 = ((int64_t)blockIdx.y * 4 + wv) * TJ;
+  if (j0 >= a.m) return;                                     // the whole wave
+  const int64_t l = (int64_t)blockIdx.x * 64 + lane;
+  const int64_t lc = l < a.nloci ? l : a.nloci - 1;
+  const double* __restrict__ xp = a.Xt + lc * K;
+  const double* __restrict__ ap = a.P + j0;                 // the panel columns j0 .. j0 + TJ - 1 (padding columns are zero: j0 + TJ <= ldp)
+  double acc[TJ][K];
+#pragma unroll
+  for (int t = 0; t < TJ; ++t)
+#pragma unroll
+    for (int q = 0; q < K; ++q) acc[t][q] = 0.0;
+  for (int i = 0; i < a.n; ++i) {                            // k_mdf_grid's loop, statement for statement
+    double x[K], av[TJ];
+#pragma unroll
+    for (int q = 0; q < K; ++q) x[q] = xp[(int64_t)i * a.ldx + q];
+#pragma unroll
+    for (int t = 0; t < TJ; ++t) av[t] = ap[(int64_t)i * a.ldp + t];
+#pragma unroll
+    for (int t = 0; t < TJ; ++t)
+#pragma unroll
+      for (int q = 0; q < K; ++q) acc[t][q] = fma(x[q], av[t], acc[t][q]);
+  }
+  const double scale = -0.5 * (double)a.n;
+  const bool valid = l < a.nloci;
+  int nnan = 0;
+#pragma unroll
+  for (int t = 0; t < TJ; ++t) {
+    const int64_t j = j0 + t;
+    if (j >= a.m) break;                                     // wave-uniform
+    const int bj = a.bin[j];
+    const bool orig = j == 0 || a.bin[j - 1] != bj;          // the trait itself: the first column of its bin
+    const double* Tp = a.T + ((int64_t)bj * a.nloci + lc) * NP;
+    double r2 = 0.0;
+#pragma unroll
+    for (int q = 0; q < K; ++q) {
+      double z = 0.0;
+#pragma unroll
+      for (int r = 0; r <= q; ++r) z = fma(Tp[q * (q + 1) / 2 + r], acc[t][r], z);
+      r2 = fma(z, z, r2);
+    }
+    int now = 0;
+    const double lod = mdf_lod(r2, scale, valid, &now);
+    nnan += orig ? now : 0;
+    const bool cand = valid && lod == lod;
+    double best = cand ? lod : -INFINITY;
+    int bi = cand ? lane : -1;
+    { const double ob = blmm_dpp_mov<0xB1>(best); const int oi = mdf_dpp_movi<0xB1>(bi); mdf_red_comb(best, bi, ob, oi); }     // lane ^ 1
+    { const double ob = blmm_dpp_mov<0x4E>(best); const int oi = mdf_dpp_movi<0x4E>(bi); mdf_red_comb(best, bi, ob, oi); }     // lane ^ 2
+    { const double ob = blmm_dpp_mov<0x141>(best); const int oi = mdf_dpp_movi<0x141>(bi); mdf_red_comb(best, bi, ob, oi); }   // row_half_mirror
+    { const double ob = blmm_dpp_mov<0x140>(best); const int oi = mdf_dpp_movi<0x140>(bi); mdf_red_comb(best, bi, ob, oi); }   // row_mirror
+    { const double ob = __shfl_xor(best, 16, 64); const int oi = __shfl_xor(bi, 16, 64); mdf_red_comb(best, bi, ob, oi); }
+    { const double ob = __shfl_xor(best, 32, 64); const int oi = __shfl_xor(bi, 32, 64); mdf_red_comb(best, bi, ob, oi); }
+    if (lane == 0) {
+      const int64_t at = (int64_t)blockIdx.x * ldm + j;
+      pmax[at] = best;
+      parg[at] = bi < 0 ? -1 : (int)(blockIdx.x * 64 + bi);
+    }
+  }
+  if (nnan) atomicAdd((unsigned long long*)&a.stat[ST_NAN_LOD], (unsigned long long)nnan);
+}
+
 // ---- null-exact scan ---------------------------------------------------------------------------------------------------------
 template <int K, int TJ>
 __global__ void __launch_bounds__(256) k_mdf_exact(MdfArgs a) {
@@ -475,6 +557,24 @@ int launch_mdf_scan(blmm_ctx* ctx, const MdfArgs& a, bool exact) {
   }
 #undef SG
 #undef SE
+  KCHECK();
+  return BLMM_OK;
+}
+
+// The reducing null-grid scan: r.pmax / r.parg [slot = locus / 64][r.ldm] (ceil(nloci / 64) slots), a.L is not touched.  The same
+// (K, TJ) pairs as the grid form; a.m (panel columns) is bounded by the grid's y extent: MDF_RED_MAX_COLS.
+int launch_mdf_scan_red(blmm_ctx* ctx, const MdfArgs& a, const RedArgs& r) {
+  if (a.nloci <= 0 || a.m <= 0) return BLMM_OK;
+  if (a.m > MDF_RED_MAX_COLS) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_multidf_perms: too many panel columns in one chunk");
+  const unsigned gx = (unsigned)((a.nloci + 63) / 64);
+#define SR(K) do { constexpr int TJ = mdf_tj_grid<K>(); \
+    hipLaunchKernelGGL((k_mdf_grid_red<K, TJ>), dim3(gx, (unsigned)((a.m + 4 * TJ - 1) / (4 * TJ))), dim3(256), 0, ctx->stream, a, r.pmax, r.parg, r.ldm); } while (0)
+  switch (a.k) {
+    case 1: SR(1); break; case 2: SR(2); break; case 3: SR(3); break; case 4: SR(4); break;
+    case 5: SR(5); break; case 6: SR(6); break; case 7: SR(7); break; case 8: SR(8); break;
+    default: return fail(ctx, BLMM_ERR_UNSUPPORTED, "bulkscan_multidf_perms: takes 1 <= k <= 8");
+  }
+#undef SR
   KCHECK();
   return BLMM_OK;
 }

@@ -11,7 +11,7 @@
 # every `ccall`'s symbol, return type and argument tuple (arity and types) against the prototype in include/bulklmm_hip.h.
 module BulkLMMHIP
 
-export bulkscan_cond, bulkscan_effects, bulkscan_multidf, calcKinship_loco, bulkscan_loco, bulkscan_loco_reduced, bulkscan_loco_perms, bulkscan_perms, bulkscan_reduced, bulkscan_reduced_async!, synchronize, DeviceLOD, lod_columns, set_tuning, calcKinship, bulkscan, bulkscan_null, bulkscan_null_grid, bulkscan_alt_grid, bulkscan_alt_exact, scan, bulkscan_multi, lod2log10p, get_thresholds,
+export bulkscan_cond, bulkscan_effects, bulkscan_multidf, bulkscan_multidf_perms, calcKinship_loco, bulkscan_loco, bulkscan_loco_reduced, bulkscan_loco_perms, bulkscan_perms, bulkscan_reduced, bulkscan_reduced_async!, synchronize, DeviceLOD, lod_columns, set_tuning, calcKinship, bulkscan, bulkscan_null, bulkscan_null_grid, bulkscan_alt_grid, bulkscan_alt_exact, scan, bulkscan_multi, lod2log10p, get_thresholds,
        lod_threshold, lod_colmax, pinned_matrix, host_register, host_unregister
 
 const libblmm = get(ENV, "BULKLMM_HIP_LIB", joinpath(@__DIR__, "..", "csrc", "libbulklmm_hip.so"))
@@ -726,6 +726,38 @@ function bulkscan_perms(Y::Array{Float64, 2}, G::Array{Float64, 2}, Covar::Union
          Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{BlmmStatus}),
         context(), o, Y, n, m, G, p, ptr_or_null(Covar), ncov, K, ptr_or_null(weights), nperms, UInt64(rndseed), C_NULL, probs,
         length(probs), h2, s2, mx, arg, mp, thr, pv, st))
+    raise_status(st)
+    return (h2_null = h2, sigma2_e = s2, lod_max = mx, lod_argmax = arg .+ 1, max_perms = mp[1:nperms, :],
+            thresholds = thr, pvals_perm = pv)
+end
+
+# Permutation thresholds of the k-degree-of-freedom scan (blmm_bulkscan_multidf_perms): bulkscan_perms with bulkscan_multidf's loci
+# (locus l = columns (l - 1) k + 1 .. l k of G, 1 <= k <= 8, the rank rule at each trait's own weights).  The null fit and the
+# permutation set are bulkscan_perms'; lod_argmax is a 1-based LOCUS here (0 = no comparable LOD).
+function bulkscan_multidf_perms(Y::Array{Float64, 2}, G::Array{Float64, 2}, Covar::Union{Nothing, Array{Float64, 2}}, K::Array{Float64, 2},
+                                k::Integer; nperms::Int64 = 1024, rndseed::Int64 = 0, signif_level::Array{Float64, 1} = [0.10, 0.05],
+                                weights::Union{Missing, Array{Float64, 1}} = missing, prior_variance::Float64 = 0.0,
+                                prior_sample_size::Float64 = 0.0, addIntercept::Bool = true, reml::Bool = false,
+                                optim_interval::Int64 = 1, decomp_scheme::String = "eigen")
+    n, m = size(Y); p = size(G, 2)
+    (size(G, 1) != n || size(K, 1) != n || size(K, 2) != n || (Covar !== nothing && size(Covar, 1) != n)) && error("Dimension mismatch.")
+    (weights !== missing && length(weights) != n) && error("Dimension mismatch.")
+    nperms < 0 && error("The required number of permutations must be a positive integer.")
+    (k < 1 || p % k != 0) && error("bulkscan_multidf_perms: the number of columns of G must be a multiple of k >= 1")
+    check_n(n)
+    o = BlmmOpts(NULL_EXACT, reml, addIntercept, decomp(decomp_scheme), optim_interval, 0, prior_variance, prior_sample_size)
+    probs = 1.0 .- signif_level
+    h2 = Array{Float64, 1}(undef, m); s2 = similar(h2); mx = similar(h2); pv = similar(h2)
+    arg = Array{Int64, 1}(undef, m)
+    mp = Array{Float64, 2}(undef, max(nperms, 1), m); thr = Array{Float64, 2}(undef, length(probs), m)
+    st = BlmmStatus()
+    ncov = Covar === nothing ? 0 : size(Covar, 2)
+    GC.@preserve Y G Covar K weights probs h2 s2 mx arg mp thr pv check(ccall((:blmm_bulkscan_multidf_perms, libblmm), Cint,
+        (Ptr{Cvoid}, Ref{BlmmOpts}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64},
+         Ptr{Float64}, Int64, UInt64, Ptr{Int32}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{BlmmStatus}),
+        context(), o, Y, n, m, G, p, Int64(k), ptr_or_null(Covar), ncov, K, ptr_or_null(weights), nperms, UInt64(rndseed), C_NULL,
+        probs, length(probs), h2, s2, mx, arg, mp, thr, pv, st))
     raise_status(st)
     return (h2_null = h2, sigma2_e = s2, lod_max = mx, lod_argmax = arg .+ 1, max_perms = mp[1:nperms, :],
             thresholds = thr, pvals_perm = pv)

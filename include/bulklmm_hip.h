@@ -32,7 +32,8 @@ extern "C" {
                             blmm_last_lod_columns / blmm_last_dims, blmm_bulkscan_reduced[_dev] (no L at all), blmm_tuning,
                             blmm_bulkscan_reduced_async + BLMM_RINFO_* (stream-ordered, flagged traits re-scanned on the device);
                             205 (0.2.2): blmm_status.n_h2_boundary / n_h2_multimodal / n_illcond_rescan (appended), BLMM_FLAG_H2_AUDIT;
-                            201: lowrank_shared, readers, blmm_scan_alt; 200: lowrank_fallback, BLMM_STREAM_NULL, multi-GPU */
+                            201: lowrank_shared, readers, blmm_scan_alt; 200: lowrank_fallback, BLMM_STREAM_NULL, multi-GPU;
+                            added since without a new number: blmm_bulkscan_multidf_perms[_dev] */
 
 typedef struct blmm_ctx blmm_ctx;
 
@@ -561,6 +562,52 @@ int blmm_bulkscan_multidf_dev(blmm_ctx* ctx, const blmm_opts* opts, const double
                               int64_t p, int64_t k, const double* dCovar, int64_t ncov, const double* dK, const double* dweights,
                               const double* h2_grid, int64_t ngrid, double* dL_out, int64_t ldL, double* dh2_out,
                               blmm_status* status);
+
+/* ---- permutation thresholds of the k-degree-of-freedom scan: blmm_bulkscan_perms with blmm_bulkscan_multidf's loci -----------
+ * Arguments and outputs are blmm_bulkscan_perms', plus k placed as in blmm_bulkscan_multidf (p = P k; locus l is the columns
+ * l k .. l k + k - 1 of G).
+ * Null model: h2_out and sigma2_out are blmm_bulkscan_perms' for the same inputs and options, bit for bit (the same design, eigen
+ *   phase, trait rotation and Brent search; the null model does not involve G).  opts->method is ignored, as there.
+ * Statistic: for trait j, s = sqrt(|makeweights(h2_j)|), Z~ = s .* Z0, r0 = s .* (y0_j - Z0 beta_j) (the reweighted null residual);
+ *   permutation b gives v_b = r0[perm_b], and v_0 = r0.  With Q the span of the accepted residuals of the locus's weighted columns
+ *   on span(Z~),
+ *     L_b[l] = -(n/2) log10(1 - |P_Q (I - P_Z~) v_b|^2 / |v_b|^2)
+ *   -- the k-df form of scan_perms_lite (src/scan.jl:485-557): the permuted vector is normalised by its own norm and the markers are
+ *   residualised on the weighted covariates.  Rank rule: blmm_bulkscan_multidf's (BLMM_MULTIDF_TAU, in column order), at the
+ *   trait's own weights.  At b = 0 this is blmm_bulkscan_multidf's null-exact LOD.  1 - R^2 = 0 gives +Inf, R^2 > 1 or NaN gives
+ *   NaN; a constant locus has LOD 0 in every permutation (the rank rule drops it -- not the zero-norm error of blmm_bulkscan_perms);
+ *   a trait with r0 = 0 is counted in n_zero_norm.  n_nan_lod counts the NaN LODs of the UNPERMUTED columns only (the number
+ *   blmm_bulkscan_multidf would report for the data, whatever nperms is); a NaN in a permuted copy is never that copy's maximum and
+ *   is not counted.
+ * Outputs: lod_max_out, lod_argmax_out (a 0-based LOCUS index), max_perms_out (nperms x m), thr_out (nprobs x m) and pval_out follow
+ *   blmm_bulkscan_perms' rules: ties go to the lowest index, NaN is never a maximum, a trait with no comparable entry (P = 0
+ *   included) gets -inf and -1, and with nperms = 0 thresholds and p-values are NaN.
+ * Permutations: ONE set for every trait -- perm_idx, or the library's generator from `seed`: the set blmm_bulkscan_perms draws for
+ *   that seed.
+ * Limits: 1 <= k <= BLMM_MULTIDF_MAX_K_GRID (the scan is the null-grid algebra at every trait's exact heritability: the factor
+ *   table of blmm_bulkscan_multidf's null-grid form with the chunk's h2 values as its grid, one row per trait shared by the trait's
+ *   nperms + 1 columns), at most BLMM_MULTIDF_MAX_COVARIATES null covariates, nperms 0 .. 16384, nprobs 0 .. 64, n <= 2048.
+ * Refused before anything is uploaded: nperms < 0 (BLMM_ERR_NPERMS); NULL required buffers, bad levels and, in the host form,
+ *   perm_idx entries outside 0 .. n - 1 (BLMM_ERR_INVALID); k < 1 or p not a multiple of k (BLMM_ERR_DIM); k above the limit, too
+ *   many covariates or permutations, n > 2048 (BLMM_ERR_UNSUPPORTED).
+ * No conditioning guard (blmm_bulkscan_perms has none either): the factor table forms Z0'WZ0 and factors it by Cholesky, so traits
+ *   with several nearly collinear weighted covariates at h2 -> 1 carry the accuracy of normal equations, not that of
+ *   blmm_bulkscan_multidf's orthogonalised null-exact re-scan.
+ * The call leaves no resident matrix (blmm_last_* see none, as after blmm_bulkscan_perms) and drops a pending
+ * blmm_set_log10p_output request.  The P x m x (nperms + 1) LOD tensor is never written: the scan kernel reduces every panel
+ * column to per-64-loci (maximum, locus) partials in its epilogue.  Trait chunks as blmm_bulkscan_perms (tuning key
+ * "bulk_perm_cols"; results do not depend on it), the budget counting the chunk's factor table, 8 k (k + 1) / 2 P bytes per trait.
+ * The _dev form: device pointers (probs host), ordered on the context's stream; with a status it synchronises. */
+int blmm_bulkscan_multidf_perms(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, int64_t n, int64_t m, const double* G, int64_t p,
+                                int64_t k, const double* Covar, int64_t ncov, const double* K, const double* weights, int64_t nperms,
+                                uint64_t seed, const int32_t* perm_idx, const double* probs, int64_t nprobs, double* h2_out,
+                                double* sigma2_out, double* lod_max_out, int64_t* lod_argmax_out, double* max_perms_out, double* thr_out,
+                                double* pval_out, blmm_status* status);
+int blmm_bulkscan_multidf_perms_dev(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG,
+                                    int64_t p, int64_t k, const double* dCovar, int64_t ncov, const double* dK, const double* dweights,
+                                    int64_t nperms, uint64_t seed, const int32_t* dperm_idx, const double* probs, int64_t nprobs,
+                                    double* dh2_out, double* dsigma2_out, double* dlod_max_out, int64_t* dlod_argmax_out,
+                                    double* dmax_perms_out, double* dthr_out, double* dpval_out, blmm_status* status);
 
 /* ---- conditional bulkscan: every trait scanned with its OWN loci in the null model (secondary QTL given the peak) -----------------
  * Inputs as blmm_bulkscan_multidf with k = 1 (Y n x m, G n x p, Covar / add_intercept, K, weights, h2_grid; opts: null-grid or
