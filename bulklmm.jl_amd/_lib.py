@@ -34,6 +34,7 @@ EXPORTS = [
     "blmm_bulkscan_loco_reduced", "blmm_bulkscan_loco_reduced_dev", "blmm_bulkscan_loco_perms", "blmm_bulkscan_loco_perms_dev",
     "blmm_bulkscan_multidf", "blmm_bulkscan_multidf_dev", "blmm_bulkscan_effects", "blmm_bulkscan_effects_dev",
     "blmm_bulkscan_cond", "blmm_bulkscan_cond_dev", "blmm_bulkscan_multidf_perms", "blmm_bulkscan_multidf_perms_dev",
+    "blmm_bulkscan_multidf_reduced", "blmm_bulkscan_multidf_reduced_dev",
 ]
 
 BLMM_NULL_EXACT, BLMM_NULL_GRID, BLMM_ALT_GRID = 0, 1, 2
@@ -225,6 +226,8 @@ def load():
     # opts, Y, n, m, G, p, k, Covar, ncov, K, weights, h2_grid, ngrid, L [, ldL], h2, status
     lib.blmm_bulkscan_multidf.argtypes = [vp, op, vp, i64, i64, vp, i64, i64, vp, i64, vp, vp, vp, i64, vp, vp, sp]
     lib.blmm_bulkscan_multidf_dev.argtypes = [vp, op, vp, i64, i64, vp, i64, i64, vp, i64, vp, vp, vp, i64, vp, i64, vp, sp]
+    lib.blmm_bulkscan_multidf_reduced.argtypes = [vp, op, vp, i64, i64, vp, i64, i64, vp, i64, vp, vp, vp, i64, rp, vp, sp]
+    lib.blmm_bulkscan_multidf_reduced_dev.argtypes = [vp, op, vp, i64, i64, vp, i64, i64, vp, i64, vp, vp, vp, i64, rp, vp, sp]
     # blmm_bulkscan_perms' arguments with k behind p
     lib.blmm_bulkscan_multidf_perms.argtypes = [vp, op, vp, i64, i64, vp, i64, i64, vp, i64, vp, vp, i64, C.c_uint64, vp, vp, i64,
                                                 vp, vp, vp, vp, vp, vp, vp, sp]

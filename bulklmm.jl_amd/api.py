@@ -1479,6 +1479,62 @@ def bulkscan_multidf_dev(ctx: Context, Y, G, K, k: int, L_out, h2_out, *, method
     return st
 
 
+def _reduced_cap(threshold, cap):
+    if threshold is not None and int(cap) < 1:
+        raise BulkLMMError("bulkscan_multidf_reduced: `threshold` needs a positive `cap`", -1)
+
+
+def bulkscan_multidf_reduced(Y, G, K, k: int, Covar=None, *, method: str = "null-grid", h2_grid=None, threshold: Optional[float] = None,
+                             cap: int = 1 << 20, addIntercept: bool = True, weights=None, prior_variance: float = 1.0,
+                             prior_sample_size: float = 0.0, reml: bool = False, optim_interval: int = 1, decomp_scheme: str = "eigen",
+                             ctx: Optional[Context] = None, return_status: bool = False) -> dict:
+    """bulkscan_multidf WITHOUT the P x m matrix (blmm_bulkscan_multidf_reduced): per trait the peak LOD and its LOCUS and --
+    `threshold` given -- every (locus, trait, LOD) with LOD > threshold, out of the k-df scan kernels' epilogues; bit-identical to
+    lod_colmax / lod_threshold on bulkscan_multidf(...)["L"].  Arguments and refusals are bulkscan_multidf's; `cap` as in
+    bulkscan_reduced.  Returns {"max_lod": m, "argmax": m (0-based locus, -1: no comparable entry), "h2_null_list": m [, "triplets":
+    (locus, trait, lod) sorted by (trait, locus)], "route": 1 | 3 (traits the conditioning guard flagged were re-scanned)}."""
+    Y, G, K, n, m, p = _host_arrays(Y, G, K)
+    cov, ncov, w, addIntercept = _host_covariates(Covar, weights, n, addIntercept)
+    k = _multidf_checks(method, n, p, k, ncov, addIntercept)
+    _reduced_cap(threshold, cap)
+    meth = _METHODS[method]
+    grid, ngrid = _grid(meth, h2_grid)
+    o = _opts(meth, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
+    ctx = ctx or default_context()  # after the argument checks: those must not need a GPU
+    h2 = np.empty(m)
+
+    def call(r, st):
+        return ctx.lib.blmm_bulkscan_multidf_reduced(ctx.h, C.byref(o), _p(Y), n, m, _p(G), p, k, _p(cov), ncov, _p(K), _p(w), _p(grid),
+                                                     ngrid, r, _p(h2), st)
+    return _reduced_host(ctx, m, threshold, cap, call, {}, h2, return_status)
+
+
+def bulkscan_multidf_reduced_dev(ctx: Context, Y, G, K, k: int, max_out, argmax_out, h2_out, *, method: str = "null-grid", h2_grid=None,
+                                 Covar=None, weights=None, addIntercept: bool = True, prior_variance: float = 1.0,
+                                 prior_sample_size: float = 0.0, reml: bool = False, optim_interval: int = 1,
+                                 decomp_scheme: str = "eigen", threshold: Optional[float] = None, trip_i=None, trip_j=None,
+                                 trip_lod=None, trip_count=None, status: bool = False):
+    """blmm_bulkscan_multidf_reduced_dev on torch tensors (layouts as bulkscan_multidf_dev): max_out (m, float64) and argmax_out
+    (m, int64), either may be None; threshold given: trip_i / trip_j (int32, cap), trip_lod (float64, cap), trip_count (int64, 1).
+    Synchronises the stream."""
+    m, n = Y.shape
+    p = G.shape[0]
+    ncov, addIntercept, st = _dev_args(Covar, addIntercept, status)
+    k = _multidf_checks(method, n, p, k, ncov, addIntercept)
+    want = threshold is not None
+    _reduced_cap(threshold, trip_i.numel() if want and trip_i is not None else 0)
+    meth = _METHODS[method]
+    grid, ngrid = _grid(meth, h2_grid)
+    o = _opts(meth, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
+    r = L.blmm_reduced(_dptr(max_out), _dptr(argmax_out), 1 if want else 0, float(threshold) if want else 0.0,
+                       int(trip_i.numel()) if want else 0, _dptr(trip_i) if want else None, _dptr(trip_j) if want else None,
+                       _dptr(trip_lod) if want else None, _dptr(trip_count) if want else None)
+    ctx.check(ctx.lib.blmm_bulkscan_multidf_reduced_dev(ctx.h, C.byref(o), Y.data_ptr(), n, m, G.data_ptr(), p, k, _dptr(Covar), ncov,
+                                                        K.data_ptr(), _dptr(weights), _p(grid), ngrid, C.byref(r), h2_out.data_ptr(),
+                                                        C.byref(st) if status else None))
+    return st
+
+
 # ---- permutation thresholds of the k-degree-of-freedom scan (blmm_bulkscan_multidf_perms) --------------------------------------
 def _multidf_perms_checks(n: int, p: int, k, nperms: int, ncov: int, addIntercept: bool, nprobs: int):
     """The library's refusals of blmm_bulkscan_multidf_perms that need no data (blmm_api.hip: mdf_perms_check), before any context:
@@ -1612,7 +1668,7 @@ def bulkscan_effects(Y, G, K, Covar=None, *, k: int = 1, locus=None, trait=None,
         raise BulkLMMError("bulkscan_effects: give both locus and trait, or neither (every trait's peak, k = 1)", -1)
     if locus is None:
         if k != 1:
-            raise BulkLMMError("bulkscan_effects: locus and trait are required for k > 1 (there is no reduced k-df scan)", -1)
+            raise BulkLMMError("bulkscan_effects: locus and trait are required for k > 1 (bulkscan_multidf_reduced gives every trait's peak locus)", -1)
         peaks = bulkscan_reduced(Y, G, K, Covar, method=method, h2_grid=h2_grid, addIntercept=addIntercept, weights=weights,
                                  prior_variance=prior_variance, prior_sample_size=prior_sample_size, reml=reml,
                                  optim_interval=optim_interval, decomp_scheme=decomp_scheme, ctx=ctx)

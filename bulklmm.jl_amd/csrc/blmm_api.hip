@@ -857,7 +857,7 @@ void blmm_destroy(blmm_ctx* ctx) {
                     &ctx->tmpA, &ctx->tmpB, &ctx->tmpC, &ctx->perm, &ctx->r0, &ctx->altbuf, &ctx->logtab, &ctx->lraw,
                     &ctx->wbQ, &ctx->wbW, &ctx->wbRk, &ctx->lrT, &ctx->lrC, &ctx->lrL, &ctx->lrFlag, &ctx->lrPart, &ctx->lrPerm, &ctx->lrDen0, &ctx->eigW, &ctx->xf32, &ctx->pf32, &ctx->brSt, &ctx->brList, &ctx->illList, &ctx->qrSlab, &ctx->lodtab, &ctx->dynFac, &ctx->pvtab, &ctx->outP, &ctx->redbuf, &ctx->redtrip, &ctx->altC, &ctx->rf32, &ctx->btG, &ctx->redflag, &ctx->bperm,
                     &ctx->locoK, &ctx->locoPart, &ctx->locoChr, &ctx->locoStat, &ctx->locoKs, &ctx->locoV, &ctx->locoLraw,
-                    &ctx->locoCmx, &ctx->locoCarg, &ctx->locoPerm, &ctx->mdfR, &ctx->mdfT,
+                    &ctx->locoCmx, &ctx->locoCarg, &ctx->locoPerm, &ctx->mdfR, &ctx->mdfT, &ctx->mdfScr,
                     &ctx->effX, &ctx->effIdx, &ctx->effWork, &ctx->effOut, &ctx->effSlab, &ctx->condIdx, &ctx->condWork};
   for (DevBuf* b : bufs) if (b->p) hipFree(b->p);
   for (auto& s : ctx->evsets) for (auto& e : s.e) (void)hipEventDestroy(e);
@@ -995,6 +995,7 @@ static const struct { const char* key; int kind; size_t off; double lo, hi; } kT
   {"eigen_solver", 1, offsetof(blmm::Tuning, eigen_solver), 0, 2},
   {"f32_rotation", 1, offsetof(blmm::Tuning, f32_rotation), 0, 1},
   {"bulk_perm_cols", 1, offsetof(blmm::Tuning, bulk_perm_cols), 0, 2147483647.0},
+  {"mdf_red_chunk", 1, offsetof(blmm::Tuning, mdf_red_chunk), 0, 2147483647.0},
 };
 int blmm_set_tuning(blmm_ctx* ctx, const char* key, double value) {
   if (!ctx) return BLMM_ERR_INVALID;
@@ -2993,15 +2994,51 @@ static int multidf_check(blmm_ctx* ctx, const blmm_opts* opts, int64_t n, int64_
   return BLMM_OK;
 }
 
+// The triplet buffers of a blmm_reduced, as reduced_check asks for them
+static int multidf_reduced_check(blmm_ctx* ctx, const blmm_reduced* out) {
+  if (!out) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_multidf_reduced: NULL buffer");
+  if (out->cap < 0 || (out->cap > 0 && (!out->ti || !out->tj || !out->tlod)) || (out->want_triplets && !out->count))
+    return fail(ctx, BLMM_ERR_INVALID, "bulkscan_multidf_reduced: triplet buffers");
+  return BLMM_OK;
+}
+
+// The traits the conditioning guard listed (blmm_bulkscan_multidf_reduced, null-exact, c >= 2), behind the reducing scan and
+// k_red_final: a chunk of the list at a time, k_mdf_qr recomputes the traits' columns into a scratch of that many columns and
+// k_mdf_flag_red reduces them over the (-inf, -1) the scan left for them and appends their triplets.  Waits for the stream once, for
+// the length of the list.
+static int multidf_reduced_flagged(blmm_ctx* ctx, const Pipe& P, const NullModel& nm, int64_t nloci, int k, const double* dh2,
+                                   const RedArgs& r, const blmm_reduced* red) {
+  int64_t cnt = 0;
+  BLMM_HIP(hipMemcpyAsync(&cnt, P.stat + ST_ILLCOND, sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));
+  BLMM_HIP(hipStreamSynchronize(ctx->stream));
+  if (cnt <= 0) return BLMM_OK;
+  ctx->last_reduced_route = 3;
+  int64_t chunk = ctx->tune.mdf_red_chunk > 0 ? ctx->tune.mdf_red_chunk : (int64_t)(64ll << 20) / (int64_t)(sizeof(double) * (size_t)nloci);
+  chunk = std::min(std::max<int64_t>(chunk, 1), cnt);
+  int rc = ensure(ctx, ctx->mdfScr, sizeof(double) * (size_t)nloci * (size_t)chunk);
+  if (rc) return rc;
+  double* scr = ptr<double>(ctx->mdfScr);
+  for (int64_t item0 = 0; item0 < cnt; item0 += chunk) {
+    const int64_t nitem = std::min(chunk, cnt - item0);
+    if ((rc = launch_mdf_qr(ctx, nm, P.Yt, P.ldy, P.Xt, P.ldx, nloci, k, P.Z0, P.lam, dh2, ptr<int>(ctx->illList), nullptr, 0, P.stat,
+                            scr, item0, nitem)) ||
+        (rc = launch_mdf_flag_red(ctx, scr, nloci, ptr<int>(ctx->illList), P.stat, item0, nitem, red->colmax, red->argmax, r))) return rc;
+  }
+  return BLMM_OK;
+}
+
+// red != nullptr: blmm_bulkscan_multidf_reduced -- `red` (device pointers) instead of dL_out / ldL, no P x m matrix anywhere
 static int multidf_dev_impl(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG, int64_t p,
                             int64_t k, const double* dCovar, int64_t ncov, const double* dK, const double* dweights,
                             const double* h2_grid_host, int64_t ngrid, double* dL_out, int64_t ldL, double* dh2_out,
-                            blmm_status* status, const PvReq& pvreq) {
+                            blmm_status* status, const PvReq& pvreq, const blmm_reduced* red = nullptr) {
   int rc = multidf_check(ctx, opts, n, m, p, k, dCovar, ncov);
   if (rc) return rc;
   const int64_t nloci = p / k;
-  if (!dY || !dG || !dK || !dL_out || !dh2_out) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_multidf: NULL buffer");
-  if (ldL < nloci) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_multidf: ldL < p / k");
+  if (!dY || !dG || !dK || (!red && !dL_out) || !dh2_out)
+    return fail(ctx, BLMM_ERR_INVALID, red ? "bulkscan_multidf_reduced: NULL buffer" : "bulkscan_multidf: NULL buffer");
+  if (red && (rc = multidf_reduced_check(ctx, red))) return rc;
+  if (!red && ldL < nloci) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_multidf: ldL < p / k");
   const bool exact = opts->method == BLMM_NULL_EXACT;
   if ((rc = enter_device(ctx))) return rc;
   Timer tm(ctx);
@@ -3016,6 +3053,10 @@ static int multidf_dev_impl(blmm_ctx* ctx, const blmm_opts* opts, const double* 
   const NullModel nm = null_model(P, opts);
   PvCall pvc(ctx, pvreq);
   if ((rc = pvc.resolve(nloci, m))) return rc;   // always the column pass over the finished L (fused stays false)
+  // the reduced form's state: one slot per 64 loci (k_mdf_grid_red / k_mdf_exact_red), finished by k_red_final; *count zeroed
+  RedArgs r;
+  const int nslot = (int)((nloci + 63) / 64);
+  if (red && (rc = red_state(ctx, red, std::max(nslot, 1), m, &r))) return rc;
   if (m == 0) { tm.mark(); tm.mark(); tm.mark(); return end_call(ctx, P, status, &tm); }
   if (nloci == 0) {
     if (exact) {
@@ -3024,6 +3065,7 @@ static int multidf_dev_impl(blmm_ctx* ctx, const blmm_opts* opts, const double* 
       if ((rc = ensure(ctx, ctx->h2idx, sizeof(int) * (size_t)m))) return rc;
       if ((rc = launch_loglik_grid(ctx, nm, P.Yt, P.ldy, m, P.Z0, P.lam, dgrid, (int)ngrid, nullptr, ptr<int>(ctx->h2idx), dh2_out, P.stat))) return rc;
     }
+    if (red && (rc = launch_red_final(ctx, r, 0, m, red->colmax, red->argmax))) return rc;   // no locus: (-inf, -1)
     tm.mark(); tm.mark(); tm.mark();
     return end_call(ctx, P, status, &tm);
   }
@@ -3044,12 +3086,24 @@ static int multidf_dev_impl(blmm_ctx* ctx, const blmm_opts* opts, const double* 
     if ((rc = launch_panels(ctx, nm, P.Yt, P.ldy, m, P.Z0, P.lam, dh2_out, 1, ptr<double>(ctx->panels), ldp, P.stat))) return rc;
     tm.mark();
     a.P = ptr<double>(ctx->panels);
+    if (red) {
+      // the guard runs AHEAD of the scan: its flags tell the epilogue which traits to leave to the re-scan
+      if (P.c >= 2) {
+        if ((rc = ensure(ctx, ctx->illList, sizeof(int) * (size_t)m)) || (rc = ensure(ctx, ctx->redflag, sizeof(int) * (size_t)m))) return rc;
+        r.flags = ptr<int>(ctx->redflag);
+        BLMM_HIP(hipMemsetAsync(r.flags, 0, sizeof(int) * (size_t)m, ctx->stream));
+        if ((rc = launch_illcond_flag(ctx, nm, m, P.Z0, P.lam, dh2_out, ptr<int>(ctx->illList), P.stat, r.flags))) return rc;
+      }
+      if ((rc = launch_mdf_scan_traits_red(ctx, a, r, true)) || (rc = launch_red_final(ctx, r, nslot, m, red->colmax, red->argmax))) return rc;
+      if (P.c >= 2 && (rc = multidf_reduced_flagged(ctx, P, nm, nloci, (int)k, dh2_out, r, red))) return rc;
+    } else {
     if ((rc = launch_mdf_scan(ctx, a, true))) return rc;
     // conditioning guard (c >= 2): the flagged traits' columns again, orthogonalised
     if (P.c >= 2) {
       if ((rc = ensure(ctx, ctx->illList, sizeof(int) * (size_t)m))) return rc;
       if ((rc = launch_illcond_flag(ctx, nm, m, P.Z0, P.lam, dh2_out, ptr<int>(ctx->illList), P.stat))) return rc;
       if ((rc = launch_mdf_qr(ctx, nm, P.Yt, P.ldy, P.Xt, P.ldx, nloci, (int)k, P.Z0, P.lam, dh2_out, ptr<int>(ctx->illList), dL_out, ldL, P.stat))) return rc;
+    }
     }
     tm.mark();
   } else {
@@ -3063,10 +3117,12 @@ static int multidf_dev_impl(blmm_ctx* ctx, const blmm_opts* opts, const double* 
     if ((rc = launch_mdf_table(ctx, nm, P.Xt, P.ldx, nloci, (int)k, P.Z0, P.lam, dgrid, (int)ngrid, ptr<double>(ctx->mdfT)))) return rc;
     tm.mark();
     a.P = ptr<double>(ctx->panels); a.T = ptr<double>(ctx->mdfT); a.bin = ptr<int>(ctx->h2idx);
-    if ((rc = launch_mdf_scan(ctx, a, false))) return rc;
+    if (red) {
+      if ((rc = launch_mdf_scan_traits_red(ctx, a, r, false)) || (rc = launch_red_final(ctx, r, nslot, m, red->colmax, red->argmax))) return rc;
+    } else if ((rc = launch_mdf_scan(ctx, a, false))) return rc;
     tm.mark();
   }
-  if ((rc = pvc.finish(nloci, m, dL_out, ldL))) return rc;
+  if (!red && (rc = pvc.finish(nloci, m, dL_out, ldL))) return rc;
   return end_call(ctx, P, status, &tm);
 }
 
@@ -3104,6 +3160,70 @@ int blmm_bulkscan_multidf(blmm_ctx* ctx, const blmm_opts* opts, const double* Y,
   if (m > 0 && (rc = copy_to_host(ctx, h2_out, ctx->outH2.p, sizeof(double) * (size_t)m))) return rc;
   if ((rc = hc.finish())) return rc;
   return check_sticky(ctx);
+}
+
+// The k-df scan without the matrix (include/bulklmm_hip.h: blmm_bulkscan_multidf_reduced).  `out` holds DEVICE pointers here.  The
+// call writes no matrix, so a pending -log10 p request is refused (and consumed); it waits for the stream before it returns.
+static const char* const kMdfRedPv = "bulkscan_multidf_reduced: a blmm_set_log10p_output request is pending (the reduced call writes no matrix)";
+static int multidf_reduced_run(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG, int64_t p,
+                               int64_t k, const double* dCovar, int64_t ncov, const double* dK, const double* dweights,
+                               const double* h2_grid, int64_t ngrid, const blmm_reduced* out, double* dh2_out, blmm_status* status) {
+  ctx->red_cur = RedArgs();
+  ctx->last_reduced_route = 1;              // 3: traits the conditioning guard flagged were re-scanned (multidf_reduced_flagged)
+  int rc = multidf_dev_impl(ctx, opts, dY, n, m, dG, p, k, dCovar, ncov, dK, dweights, h2_grid, ngrid, nullptr, 0, dh2_out, status, PvReq(), out);
+  if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+  clear_last(ctx);                          // no matrix of this call: an earlier one is not served as its result
+  BLMM_HIP(hipStreamSynchronize(ctx->stream));
+  return check_sticky(ctx);
+}
+
+int blmm_bulkscan_multidf_reduced_dev(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG,
+                                      int64_t p, int64_t k, const double* dCovar, int64_t ncov, const double* dK, const double* dweights,
+                                      const double* h2_grid, int64_t ngrid, const blmm_reduced* out, double* dh2_out,
+                                      blmm_status* status) {
+  if (!ctx) return BLMM_ERR_INVALID;
+  if (pv_take(ctx).armed) return fail(ctx, BLMM_ERR_INVALID, kMdfRedPv);
+  return multidf_reduced_run(ctx, opts, dY, n, m, dG, p, k, dCovar, ncov, dK, dweights, h2_grid, ngrid, out, dh2_out, status);
+}
+
+// host-pointer form: `out` holds HOST pointers; the small results come back, nothing P x m exists
+int blmm_bulkscan_multidf_reduced(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, int64_t n, int64_t m, const double* G, int64_t p,
+                                  int64_t k, const double* Covar, int64_t ncov, const double* K, const double* weights,
+                                  const double* h2_grid, int64_t ngrid, const blmm_reduced* out, double* h2_out, blmm_status* status) {
+  if (!ctx) return BLMM_ERR_INVALID;
+  if (pv_take(ctx).armed) return fail(ctx, BLMM_ERR_INVALID, kMdfRedPv);
+  int rc = multidf_check(ctx, opts, n, m, p, k, Covar, ncov);
+  if (rc) return rc;
+  if (!Y || !G || !K || !h2_out) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_multidf_reduced: NULL buffer");
+  if ((rc = multidf_reduced_check(ctx, out))) return rc;
+  HostCall hc(ctx);
+  const size_t cap = out->cap > 0 ? out->cap : 1, mm = m > 0 ? m : 1;
+  // device side of `out`: maxima / arg-maxima (tmpA / tmpB), triplets + count (redtrip), h2 (outH2), as blmm_bulkscan_reduced
+  if ((rc = hc.begin()) || (rc = ensure(ctx, ctx->tmpA, sizeof(double) * mm)) || (rc = ensure(ctx, ctx->tmpB, sizeof(int64_t) * mm)) ||
+      (rc = ensure(ctx, ctx->redtrip, (sizeof(double) + 2 * sizeof(int32_t)) * cap + 64)) || (rc = ensure(ctx, ctx->outH2, sizeof(double) * mm)))
+    return rc;
+  blmm_reduced d = *out;
+  d.colmax = (out->colmax || out->argmax) ? ptr<double>(ctx->tmpA) : nullptr;
+  d.argmax = out->argmax ? ptr<int64_t>(ctx->tmpB) : nullptr;
+  d.count = ptr<int64_t>(ctx->redtrip);
+  d.tlod = reinterpret_cast<double*>(d.count + 8);
+  d.ti = reinterpret_cast<int32_t*>(d.tlod + cap);
+  d.tj = d.ti + cap;
+  HostCall::In in;
+  if ((rc = hc.inputs(Y, n, m, G, p, K, Covar, ncov, weights, /*defer*/ true, &in)) ||
+      (rc = multidf_reduced_run(ctx, opts, in.Y, n, m, in.G, p, k, in.Cov, in.ncov, in.K, in.W, h2_grid, ngrid, &d, ptr<double>(ctx->outH2), status)))
+    return rc;
+  if (m > 0 && ((rc = hc.down(out->colmax, d.colmax, sizeof(double) * m)) || (rc = hc.down(out->argmax, d.argmax, sizeof(int64_t) * m)) ||
+                (rc = hc.down(h2_out, ctx->outH2.p, sizeof(double) * m)))) return rc;
+  if (out->want_triplets) {
+    // the count first: only what it says is copied back
+    if ((rc = hc.down(out->count, d.count, sizeof(int64_t)))) return rc;
+    BLMM_HIP(hipStreamSynchronize(ctx->stream));
+    const size_t got = *out->count < out->cap ? *out->count : out->cap;
+    if ((rc = hc.down(out->tlod, d.tlod, sizeof(double) * got)) || (rc = hc.down(out->ti, d.ti, sizeof(int32_t) * got)) ||
+        (rc = hc.down(out->tj, d.tj, sizeof(int32_t) * got))) return rc;
+  }
+  return (rc = hc.finish()) ? rc : check_sticky(ctx);
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -60,6 +60,7 @@ struct Tuning {
   int lr_split = -1;            // -1: split the h2 search into two panel regions from 8192 traits on; 0 / 1: never / always
   int f32_rotation = 1;         // fp32 permutation path (blmm_scan_perms_f32, c <= 3): 1 = rotate G on the fp32 matrix cores straight into k_scan_f32's operand layout; 0 = fp64 rotation + conversion (round 3)
   int eigen_solver = 0;         // 0: by n (fast path + Jacobi up to 124, tridiagonalisation + divide and conquer beyond); 1: Jacobi; 2: divide and conquer
+  int mdf_red_chunk = 0;        // blmm_bulkscan_multidf_reduced: flagged traits re-scanned per chunk of the scratch; 0: from a 64 MiB budget
   int bulk_perm_cols = 0;       // blmm_bulkscan_perms: largest trait chunk in panel columns (traits x (nperms + 1)); 0: from the memory budget
 };
 
@@ -112,6 +113,7 @@ struct blmm_ctx {
       locoCmx, locoCarg,   // blmm_bulkscan_loco_reduced: the per-chromosome maxima / arg-maxima when the caller's tables are not on the device
       locoPerm,            // blmm_bulkscan_loco_perms: the genome-wide (nperms + 1) x m column maxima and their global markers
       mdfR, mdfT,          // blmm_bulkscan_multidf: the uncentred rotation and the null-grid factor table (kernels_mdf.hip)
+      mdfScr,              // blmm_bulkscan_multidf_reduced: the flagged traits' columns, a chunk of the guard's list wide
       condIdx, condWork,   // blmm_bulkscan_cond (kernels_cond.hip): the host form's index table; kept columns, counts, guard flags, info counters
       effX, effIdx, effWork, effOut, effSlab;   // blmm_bulkscan_effects (kernels_effects.hip): the rotated markers column-major, the host form's
                                                 // test lists, the sort's counters + permutation, the host form's outputs, the waves' slab
@@ -548,8 +550,16 @@ int launch_mdf_scan(blmm_ctx* ctx, const MdfArgs& a, bool exact);
 // slots, finished by launch_red_final); a.L unused.  At most MDF_RED_MAX_COLS columns (a.m) a launch: 65535 grid rows of 4 x 8 columns
 constexpr int64_t MDF_RED_MAX_COLS = 65535ll * 32;
 int launch_mdf_scan_red(blmm_ctx* ctx, const MdfArgs& a, const RedArgs& r);
+// blmm_bulkscan_multidf_reduced: the traits' own scan reduced in its epilogue (r: partials as above, triplets, r.flags: the traits the
+// conditioning guard flagged -- skipped here)
+int launch_mdf_scan_traits_red(blmm_ctx* ctx, const MdfArgs& a, const RedArgs& r, bool exact);
+// scr != nullptr: the listed traits item0 .. item0 + nitem - 1 into columns 0 .. of the compact scratch scr (ld nloci), L untouched
 int launch_mdf_qr(blmm_ctx* ctx, const NullModel& nm, const double* Yt, int64_t ldy, const double* Xt, int64_t ldx, int64_t nloci, int k,
-                  const double* Z0, const double* lam, const double* h2, const int* list, double* L, int64_t ldL, int64_t* stat);
+                  const double* Z0, const double* lam, const double* h2, const int* list, double* L, int64_t ldL, int64_t* stat,
+                  double* scr = nullptr, int64_t item0 = 0, int64_t nitem = 0);
+// ... and that scratch reduced into mx / arg (at the traits' indices; either may be null) and r's triplets
+int launch_mdf_flag_red(blmm_ctx* ctx, const double* scr, int64_t nloci, const int* list, const int64_t* stat, int64_t item0,
+                        int64_t nitem, double* mx, int64_t* arg, const RedArgs& r);
    // k_bperm_summary sorts a trait's maxima in LDS (128 KB)
 
 // kernels_cond.hip: blmm_bulkscan_cond, every trait scanned with its own conditioning loci in the null design

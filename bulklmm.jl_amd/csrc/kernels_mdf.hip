@@ -24,6 +24,9 @@
 //              partials (maximum, locus) in its epilogue instead of writing L.
 //   null-exact (per-trait weights): k_mdf_exact accumulates b, P (from products x_a x_b formed in registers) and, one covariate
 //              per pass, u_q -- folded into S at once -- then factors S per (locus, trait) in its epilogue.
+//   reduced    (blmm_bulkscan_multidf_reduced): the traits' own columns through k_mdf_grid_red<.., SCAN> / k_mdf_exact_red -- slot
+//              partials for k_red_final and the LOD > thr triplets, no L; flagged traits through k_mdf_qr's compact scratch and
+//              k_mdf_flag_red.
 //   guard      (null-exact, c >= 2, traits launch_illcond_flag listed: nearly collinear weighted covariates at h2 -> 1):
 //              k_mdf_qr recomputes their columns with an orthonormal basis of span(Z~) from Gram-Schmidt with re-orthogonalisation
 //              and explicit residuals (ortho_basis.h).
@@ -265,13 +268,42 @@ __global__ void __launch_bounds__(256) k_mdf_grid(MdfArgs a) {
 // 16-lane rows, then the rows across 16 and 32 lanes -- and lane 0 writes the partial of (slot = blockIdx.x, column) for k_red_final.
 // A slot without a candidate holds (-inf, -1).  NaN LODs are counted (ST_NAN_LOD) in the UNPERMUTED columns only (the first column
 // of each bin): the count is that of the data's own scan, whatever nperms is.
+//
+// SCAN (blmm_bulkscan_multidf_reduced): the columns are the traits themselves, bin[j] their grid bins -- every column's NaNs count,
+// and with r.want_trip every LOD > r.thr is appended as a (locus, trait, LOD) triplet, one wave-aggregated atomic reserving the
+// wave's slots (as k_threshold and the 1-df epilogue, kernels_scan.hip: red_row).  r is read by the SCAN instantiations only; it
+// comes last so that the permutation instantiations keep their kernel-argument offsets, instruction for instruction.
 template <int CTRL>
 __device__ __forceinline__ int mdf_dpp_movi(int x) { return __builtin_amdgcn_update_dpp(x, x, CTRL, 0xf, 0xf, false); }
 __device__ __forceinline__ void mdf_red_comb(double& best, int& bi, double ob, int oi) {
   if (ob > best || (ob == best && oi >= 0 && (bi < 0 || oi < bi))) { best = ob; bi = oi; }
 }
-template <int K, int TJ>
-__global__ void __launch_bounds__(256) k_mdf_grid_red(MdfArgs a, double* pmax, int* parg, int64_t ldm) {
+// every lane's candidate -> the wave's best, in all lanes
+__device__ __forceinline__ void mdf_red_wave(double& best, int& bi) {
+  { const double ob = blmm_dpp_mov<0xB1>(best); const int oi = mdf_dpp_movi<0xB1>(bi); mdf_red_comb(best, bi, ob, oi); }     // lane ^ 1
+  { const double ob = blmm_dpp_mov<0x4E>(best); const int oi = mdf_dpp_movi<0x4E>(bi); mdf_red_comb(best, bi, ob, oi); }     // lane ^ 2
+  { const double ob = blmm_dpp_mov<0x141>(best); const int oi = mdf_dpp_movi<0x141>(bi); mdf_red_comb(best, bi, ob, oi); }   // row_half_mirror
+  { const double ob = blmm_dpp_mov<0x140>(best); const int oi = mdf_dpp_movi<0x140>(bi); mdf_red_comb(best, bi, ob, oi); }   // row_mirror
+  { const double ob = __shfl_xor(best, 16, 64); const int oi = __shfl_xor(bi, 16, 64); mdf_red_comb(best, bi, ob, oi); }
+  { const double ob = __shfl_xor(best, 32, 64); const int oi = __shfl_xor(bi, 32, 64); mdf_red_comb(best, bi, ob, oi); }
+}
+// the wave's 64 LODs of trait j (lane = locus blockIdx.x * 64 + lane; `valid`: the locus exists)
+__device__ __forceinline__ void mdf_trip_append(const RedArgs& r, double lod, bool valid, int lane, int64_t j) {
+  const bool hit = valid && lod > r.thr;                       // a NaN never passes
+  const unsigned long long mask = __ballot(hit);
+  if (mask == 0ull) return;
+  const int leader = (int)__builtin_ctzll(mask);
+  unsigned long long base = 0;
+  if (lane == leader) base = atomicAdd(r.cnt, (unsigned long long)__builtin_popcountll(mask));
+  const unsigned int blo = __builtin_amdgcn_readlane((unsigned int)base, leader);
+  const unsigned int bhi = __builtin_amdgcn_readlane((unsigned int)(base >> 32), leader);
+  if (hit) {
+    const unsigned long long slot = (((unsigned long long)bhi << 32) | blo) + (unsigned long long)__builtin_popcountll(mask & ((1ull << lane) - 1ull));
+    if ((int64_t)slot < r.cap) { r.ti[slot] = (int32_t)(blockIdx.x * 64 + lane); r.tj[slot] = (int32_t)j; r.tl[slot] = lod; }
+  }
+}
+template <int K, int TJ, bool SCAN = false>
+__global__ void __launch_bounds__(256) k_mdf_grid_red(MdfArgs a, double* pmax, int* parg, int64_t ldm, RedArgs r) {
   constexpr int NP = K * (K + 1) / 2;
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -305,7 +337,7 @@ __global__ void __launch_bounds__(256) k_mdf_grid_red(MdfArgs a, double* pmax, i
     const int64_t j = j0 + t;
     if (j >= a.m) break;                                     // wave-uniform
     const int bj = a.bin[j];
-    const bool orig = j == 0 || a.bin[j - 1] != bj;          // the trait itself: the first column of its bin
+    const bool orig = SCAN || j == 0 || a.bin[j - 1] != bj;  // the trait itself: the first column of its bin (SCAN: every column)
     const double* Tp = a.T + ((int64_t)bj * a.nloci + lc) * NP;
     double r2 = 0.0;
 #pragma unroll
@@ -331,6 +363,9 @@ __global__ void __launch_bounds__(256) k_mdf_grid_red(MdfArgs a, double* pmax, i
       const int64_t at = (int64_t)blockIdx.x * ldm + j;
       pmax[at] = best;
       parg[at] = bi < 0 ? -1 : (int)(blockIdx.x * 64 + bi);
+    }
+    if constexpr (SCAN) {
+      if (r.want_trip) mdf_trip_append(r, lod, valid, lane, j);   // kernel argument: a scalar branch
     }
   }
   if (nnan) atomicAdd((unsigned long long*)&a.stat[ST_NAN_LOD], (unsigned long long)nnan);
@@ -420,19 +455,123 @@ __global__ void __launch_bounds__(256) k_mdf_exact(MdfArgs a) {
   if (nnan) atomicAdd((unsigned long long*)&a.stat[ST_NAN_LOD], (unsigned long long)nnan);
 }
 
+// ---- null-exact scan, reduced in the epilogue (blmm_bulkscan_multidf_reduced) -----------------------------------------------------
+// k_mdf_exact's contraction and factorisation repeated statement for statement (the LODs carry its bits; shared as a device function
+// the two passes scheduled differently in k_mdf_exact itself, which stays as it was); the store is replaced by
+// k_mdf_grid_red's SCAN epilogue.  A trait the conditioning guard flagged (r.flags, written before this kernel runs) keeps the
+// partial (-inf, -1), appends no triplet and counts no NaN: k_mdf_qr's reduced form and k_mdf_flag_red supply all three.
+template <int K, int TJ>
+__global__ void __launch_bounds__(256) k_mdf_exact_red(MdfArgs a, RedArgs r) {
+  constexpr int NP = K * (K + 1) / 2;
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t j0 = ((int64_t)blockIdx.y * 4 + wv) * TJ;
+  if (j0 >= a.m) return;
+  const int64_t l = (int64_t)blockIdx.x * 64 + lane;
+  const int64_t lc = l < a.nloci ? l : a.nloci - 1;
+  const double* __restrict__ xp = a.Xt + lc * K;
+  const double* __restrict__ a0 = a.P + j0;
+  const double* __restrict__ a1 = a.P + a.pstride + j0;
+  double b[TJ][K], S[TJ][NP], d0[TJ][K];
+#pragma unroll
+  for (int t = 0; t < TJ; ++t) {
+#pragma unroll
+    for (int q = 0; q < K; ++q) b[t][q] = 0.0;
+#pragma unroll
+    for (int q = 0; q < NP; ++q) S[t][q] = 0.0;
+  }
+  // pass 0: numerators b and the weighted Gram P of the locus columns
+  for (int i = 0; i < a.n; ++i) {
+    double x[K], xx[NP], v0[TJ], v1[TJ];
+#pragma unroll
+    for (int q = 0; q < K; ++q) x[q] = xp[(int64_t)i * a.ldx + q];
+#pragma unroll
+    for (int q = 0; q < K; ++q)
+#pragma unroll
+      for (int r = 0; r <= q; ++r) xx[q * (q + 1) / 2 + r] = x[q] * x[r];
+#pragma unroll
+    for (int t = 0; t < TJ; ++t) { v0[t] = a0[(int64_t)i * a.ldp + t]; v1[t] = a1[(int64_t)i * a.ldp + t]; }
+#pragma unroll
+    for (int t = 0; t < TJ; ++t) {
+#pragma unroll
+      for (int q = 0; q < K; ++q) b[t][q] = fma(x[q], v0[t], b[t][q]);
+#pragma unroll
+      for (int q = 0; q < NP; ++q) S[t][q] = fma(xx[q], v1[t], S[t][q]);
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < TJ; ++t)
+#pragma unroll
+    for (int q = 0; q < K; ++q) d0[t][q] = S[t][q * (q + 1) / 2 + q];
+  // one pass per covariate: u_q = X_l' panel(2+q), S -= u_q u_q'
+  for (int cq = 0; cq < a.c; ++cq) {
+    const double* __restrict__ aq = a.P + (int64_t)(2 + cq) * a.pstride + j0;
+    double u[TJ][K];
+#pragma unroll
+    for (int t = 0; t < TJ; ++t)
+#pragma unroll
+      for (int q = 0; q < K; ++q) u[t][q] = 0.0;
+    for (int i = 0; i < a.n; ++i) {
+      double x[K], v[TJ];
+#pragma unroll
+      for (int q = 0; q < K; ++q) x[q] = xp[(int64_t)i * a.ldx + q];
+#pragma unroll
+      for (int t = 0; t < TJ; ++t) v[t] = aq[(int64_t)i * a.ldp + t];
+#pragma unroll
+      for (int t = 0; t < TJ; ++t)
+#pragma unroll
+        for (int q = 0; q < K; ++q) u[t][q] = fma(x[q], v[t], u[t][q]);
+    }
+#pragma unroll
+    for (int t = 0; t < TJ; ++t)
+#pragma unroll
+      for (int q = 0; q < K; ++q)
+#pragma unroll
+        for (int r = 0; r <= q; ++r) S[t][q * (q + 1) / 2 + r] = fma(-u[t][q], u[t][r], S[t][q * (q + 1) / 2 + r]);
+  }
+  const double scale = -0.5 * (double)a.n;
+  const bool valid = l < a.nloci;
+  int nnan = 0;
+#pragma unroll
+  for (int t = 0; t < TJ; ++t) {
+    const int64_t j = j0 + t;
+    if (j >= a.m) break;                                     // wave-uniform
+    const int64_t at = (int64_t)blockIdx.x * r.ldm + j;
+    if (r.flags && r.flags[j] != 0) {                        // wave-uniform
+      if (lane == 0) { r.pmax[at] = -INFINITY; r.parg[at] = -1; }
+      continue;
+    }
+    mdf_chol<K>(S[t], d0[t]);
+    const double lod = mdf_lod(mdf_r2<K>(S[t], b[t]), scale, valid, &nnan);
+    const bool cand = valid && lod == lod;
+    double best = cand ? lod : -INFINITY;
+    int bi = cand ? lane : -1;
+    mdf_red_wave(best, bi);
+    if (lane == 0) {
+      r.pmax[at] = best;
+      r.parg[at] = bi < 0 ? -1 : (int)(blockIdx.x * 64 + bi);
+    }
+    if (r.want_trip) mdf_trip_append(r, lod, valid, lane, j);   // kernel argument: a scalar branch
+  }
+  if (nnan) atomicAdd((unsigned long long*)&a.stat[ST_NAN_LOD], (unsigned long long)nnan);
+}
+
 // ---- the conditioning guard's re-scan of listed traits (null-exact, c >= 2) ------------------------------------------------------
 // One workgroup per listed trait at a time (grid-stride over the device count stat[ST_ILLCOND]); buf: (c + 2) n doubles (weights'
 // square roots, the orthonormal basis, the unit trait residual), in LDS or in a per-workgroup slab of global memory.
-template <int K>
+// RED (blmm_bulkscan_multidf_reduced): there is no L.  The listed traits item0 .. item0 + nitem - 1 go to the columns 0 .. nitem - 1
+// of a compact scratch (L, ld ldL) for k_mdf_flag_red, and every NaN counts: k_mdf_exact_red counted none for a flagged trait.
+template <int K, bool RED = false>
 __global__ void __launch_bounds__(256) k_mdf_qr(int n, int c, const double* __restrict__ Yt, int64_t ldy,
                                                 const double* __restrict__ Xt, int64_t ldx, int64_t nloci,
                                                 const double* __restrict__ Z0, const double* __restrict__ lam,
                                                 const double* __restrict__ h2v, const int* __restrict__ list, double* slab,
-                                                double* __restrict__ L, int64_t ldL, int64_t* stat) {
+                                                double* __restrict__ L, int64_t ldL, int64_t* stat, int64_t item0, int64_t nitem) {
   constexpr int NP = K * (K + 1) / 2;
   extern __shared__ __attribute__((aligned(16))) double sh[];
   __shared__ double s_red[4];
-  const int64_t cnt = stat[ST_ILLCOND];
+  int64_t cnt = stat[ST_ILLCOND];
+  if (RED && cnt > item0 + nitem) cnt = item0 + nitem;
   if (cnt <= 0) return;
   double* buf = slab ? slab + (size_t)blockIdx.x * (size_t)(c + 2) * n : sh;
   double* Sw = buf;
@@ -440,8 +579,9 @@ __global__ void __launch_bounds__(256) k_mdf_qr(int n, int c, const double* __re
   double* yb = buf + (size_t)(1 + c) * n;
   const double scale = -0.5 * (double)n;
   int nnan = 0;
-  for (int64_t item = blockIdx.x; item < cnt; item += gridDim.x) {
+  for (int64_t item = (RED ? item0 : 0) + blockIdx.x; item < cnt; item += gridDim.x) {
     const int64_t j = list[item];
+    double* __restrict__ col = L + (RED ? item - item0 : j) * ldL;
     const double nn = weighted_basis<256, 1, true>(n, c, h2v[j], lam, [&](int q, int k) { return Z0[(size_t)q * n + k]; },
                                                    Yt + j, ldy, Sw, Qb, yb, s_red);
     const double inv = 1.0 / sqrt(nn);
@@ -507,11 +647,51 @@ __global__ void __launch_bounds__(256) k_mdf_qr(int n, int c, const double* __re
       // adds its own NaN and takes back the scan's
       int now = 0;
       const double lod = mdf_lod(mdf_r2<K>(S, bb), scale, true, &now);
-      nnan += now - (isnan(L[j * ldL + l]) ? 1 : 0);
-      L[j * ldL + l] = lod;
+      nnan += RED ? now : now - (isnan(col[l]) ? 1 : 0);
+      col[l] = lod;
     }
   }
   if (nnan) atomicAdd((unsigned long long*)&stat[ST_NAN_LOD], (unsigned long long)(long long)nnan);   // (two's complement: may be < 0)
+}
+
+// ---- the flagged traits' scratch columns -> their maxima and triplets (blmm_bulkscan_multidf_reduced) ----------------------------
+// One wave per column of k_mdf_qr's scratch (column e = listed trait item0 + e); k_colmax's rule into mx / arg (either may be null)
+// at the TRAIT's index and k_threshold's append with the trait's index, written over what k_red_final left for a flagged trait.
+__global__ void __launch_bounds__(256) k_mdf_flag_red(const double* __restrict__ S, int64_t nloci, const int* __restrict__ list,
+                                                      const int64_t* __restrict__ stat, int64_t item0, int64_t nitem,
+                                                      double* __restrict__ mx, int64_t* __restrict__ arg, RedArgs r) {
+  const int lane = threadIdx.x & 63;
+  const int64_t e = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t left = stat[ST_ILLCOND] - item0;
+  if (e >= nitem || e >= left) return;                       // the whole wave
+  const int64_t j = list[item0 + e];
+  const double* col = S + e * nloci;
+  double best = -INFINITY;
+  int64_t bi = -1;
+  for (int64_t i0 = 0; i0 < nloci; i0 += 64) {
+    const int64_t i = i0 + lane;
+    const double v = i < nloci ? col[i] : -INFINITY;
+    if (v > best) { best = v; bi = i; }
+    if (r.want_trip) {
+      const bool hit = v > r.thr;
+      const unsigned long long mask = __ballot(hit);
+      if (mask == 0ull) continue;
+      unsigned long long base = 0;
+      if (lane == (int)__builtin_ctzll(mask)) base = atomicAdd(r.cnt, (unsigned long long)__builtin_popcountll(mask));
+      base = __shfl(base, (int)__builtin_ctzll(mask), 64);
+      if (hit) {
+        const unsigned long long slot = base + (unsigned long long)__builtin_popcountll(mask & ((1ull << lane) - 1ull));
+        if ((int64_t)slot < r.cap) { r.ti[slot] = (int32_t)i; r.tj[slot] = (int32_t)j; r.tl[slot] = v; }
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double ob = __shfl_xor(best, o, 64);
+    const int64_t oi = __shfl_xor(bi, o, 64);
+    if (ob > best || (ob == best && oi >= 0 && (bi < 0 || oi < bi))) { best = ob; bi = oi; }
+  }
+  if (lane == 0) { if (mx) mx[j] = best; if (arg) arg[j] = bi; }
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------------------------------
@@ -568,7 +748,7 @@ int launch_mdf_scan_red(blmm_ctx* ctx, const MdfArgs& a, const RedArgs& r) {
   if (a.m > MDF_RED_MAX_COLS) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_multidf_perms: too many panel columns in one chunk");
   const unsigned gx = (unsigned)((a.nloci + 63) / 64);
 #define SR(K) do { constexpr int TJ = mdf_tj_grid<K>(); \
-    hipLaunchKernelGGL((k_mdf_grid_red<K, TJ>), dim3(gx, (unsigned)((a.m + 4 * TJ - 1) / (4 * TJ))), dim3(256), 0, ctx->stream, a, r.pmax, r.parg, r.ldm); } while (0)
+    hipLaunchKernelGGL((k_mdf_grid_red<K, TJ>), dim3(gx, (unsigned)((a.m + 4 * TJ - 1) / (4 * TJ))), dim3(256), 0, ctx->stream, a, r.pmax, r.parg, r.ldm, r); } while (0)
   switch (a.k) {
     case 1: SR(1); break; case 2: SR(2); break; case 3: SR(3); break; case 4: SR(4); break;
     case 5: SR(5); break; case 6: SR(6); break; case 7: SR(7); break; case 8: SR(8); break;
@@ -579,18 +759,62 @@ int launch_mdf_scan_red(blmm_ctx* ctx, const MdfArgs& a, const RedArgs& r) {
   return BLMM_OK;
 }
 
+// The reducing scan of the traits themselves (blmm_bulkscan_multidf_reduced): k_mdf_grid_red's SCAN instantiations, or
+// k_mdf_exact_red; partials as launch_mdf_scan_red, triplets behind r.cnt, r.flags (null-exact) the guard's flags.
+int launch_mdf_scan_traits_red(blmm_ctx* ctx, const MdfArgs& a, const RedArgs& r, bool exact) {
+  if (a.nloci <= 0 || a.m <= 0) return BLMM_OK;
+  const unsigned gx = (unsigned)((a.nloci + 63) / 64);
+#define GY(TJ) \
+    const int64_t gy = (a.m + 4 * TJ - 1) / (4 * TJ); \
+    if (gy > 65535) return fail(ctx, BLMM_ERR_UNSUPPORTED, "bulkscan_multidf_reduced: more than " + std::to_string(65535ll * 4 * TJ) + " traits in one call")
+#define SG(K) do { constexpr int TJ = mdf_tj_grid<K>(); GY(TJ); \
+    hipLaunchKernelGGL((k_mdf_grid_red<K, TJ, true>), dim3(gx, (unsigned)gy), dim3(256), 0, ctx->stream, a, r.pmax, r.parg, r.ldm, r); } while (0)
+#define SE(K) do { constexpr int TJ = mdf_tj_exact<K>(); GY(TJ); \
+    hipLaunchKernelGGL((k_mdf_exact_red<K, TJ>), dim3(gx, (unsigned)gy), dim3(256), 0, ctx->stream, a, r); } while (0)
+  if (exact) {
+    switch (a.k) {
+      case 1: SE(1); break; case 2: SE(2); break; case 3: SE(3); break; case 4: SE(4); break;
+      default: return fail(ctx, BLMM_ERR_UNSUPPORTED, "bulkscan_multidf: null-exact takes 1 <= k <= 4");
+    }
+  } else {
+    switch (a.k) {
+      case 1: SG(1); break; case 2: SG(2); break; case 3: SG(3); break; case 4: SG(4); break;
+      case 5: SG(5); break; case 6: SG(6); break; case 7: SG(7); break; case 8: SG(8); break;
+      default: return fail(ctx, BLMM_ERR_UNSUPPORTED, "bulkscan_multidf: null-grid takes 1 <= k <= 8");
+    }
+  }
+#undef SG
+#undef SE
+#undef GY
+  KCHECK();
+  return BLMM_OK;
+}
+
+// scr != nullptr (the reduced form): the listed traits item0 .. item0 + nitem - 1 into the compact scratch scr (ld nloci) instead of L
 int launch_mdf_qr(blmm_ctx* ctx, const NullModel& nm, const double* Yt, int64_t ldy, const double* Xt, int64_t ldx, int64_t nloci, int k,
-                  const double* Z0, const double* lam, const double* h2, const int* list, double* L, int64_t ldL, int64_t* stat) {
+                  const double* Z0, const double* lam, const double* h2, const int* list, double* L, int64_t ldL, int64_t* stat,
+                  double* scr, int64_t item0, int64_t nitem) {
   if (nloci <= 0 || nm.c < 2) return BLMM_OK;
   size_t lds; double* slab; unsigned grid;
   if (int rc = qr_workspace(ctx, nm.c, nm.n, &lds, &slab, &grid)) return rc;
-#define QR(K) do { if (lds > 48 * 1024) BLMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mdf_qr<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    hipLaunchKernelGGL(k_mdf_qr<K>, dim3(grid), dim3(256), lds, ctx->stream, nm.n, nm.c, Yt, ldy, Xt, ldx, nloci, Z0, lam, h2, list, slab, L, ldL, stat); } while (0)
+#define QR1(K, RED, OUT, LD) do { if (lds > 48 * 1024) BLMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mdf_qr<K, RED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+    hipLaunchKernelGGL((k_mdf_qr<K, RED>), dim3(grid), dim3(256), lds, ctx->stream, nm.n, nm.c, Yt, ldy, Xt, ldx, nloci, Z0, lam, h2, list, slab, OUT, LD, stat, item0, nitem); } while (0)
+#define QR(K) do { if (scr) QR1(K, true, scr, nloci); else QR1(K, false, L, ldL); } while (0)
   switch (k) {
     case 1: QR(1); break; case 2: QR(2); break; case 3: QR(3); break; case 4: QR(4); break;
     default: return fail(ctx, BLMM_ERR_UNSUPPORTED, "bulkscan_multidf: null-exact takes 1 <= k <= 4");
   }
 #undef QR
+#undef QR1
+  KCHECK();
+  return BLMM_OK;
+}
+
+int launch_mdf_flag_red(blmm_ctx* ctx, const double* scr, int64_t nloci, const int* list, const int64_t* stat, int64_t item0,
+                        int64_t nitem, double* mx, int64_t* arg, const RedArgs& r) {
+  if (nitem <= 0) return BLMM_OK;
+  hipLaunchKernelGGL(k_mdf_flag_red, dim3((unsigned)((nitem + 3) / 4)), dim3(256), 0, ctx->stream, scr, nloci, list, stat, item0, nitem,
+                     mx, arg, r);
   KCHECK();
   return BLMM_OK;
 }

@@ -11,7 +11,7 @@
 # every `ccall`'s symbol, return type and argument tuple (arity and types) against the prototype in include/bulklmm_hip.h.
 module BulkLMMHIP
 
-export bulkscan_cond, bulkscan_effects, bulkscan_multidf, bulkscan_multidf_perms, calcKinship_loco, bulkscan_loco, bulkscan_loco_reduced, bulkscan_loco_perms, bulkscan_perms, bulkscan_reduced, bulkscan_reduced_async!, synchronize, DeviceLOD, lod_columns, set_tuning, calcKinship, bulkscan, bulkscan_null, bulkscan_null_grid, bulkscan_alt_grid, bulkscan_alt_exact, scan, bulkscan_multi, lod2log10p, get_thresholds,
+export bulkscan_cond, bulkscan_effects, bulkscan_multidf, bulkscan_multidf_perms, bulkscan_multidf_reduced, bulkscan_multidf_reduced_dev!, calcKinship_loco, bulkscan_loco, bulkscan_loco_reduced, bulkscan_loco_perms, bulkscan_perms, bulkscan_reduced, bulkscan_reduced_async!, synchronize, DeviceLOD, lod_columns, set_tuning, calcKinship, bulkscan, bulkscan_null, bulkscan_null_grid, bulkscan_alt_grid, bulkscan_alt_exact, scan, bulkscan_multi, lod2log10p, get_thresholds,
        lod_threshold, lod_colmax, pinned_matrix, host_register, host_unregister
 
 const libblmm = get(ENV, "BULKLMM_HIP_LIB", joinpath(@__DIR__, "..", "csrc", "libbulklmm_hip.so"))
@@ -401,6 +401,75 @@ function bulkscan_multidf(Y::Array{Float64, 2}, G::Array{Float64, 2}, Covar::Arr
         return merge(res, (log10Pvals_mat = _last_log10p((P, m), chisq_df), Chisq_df = chisq_df))
     end
     return res
+end
+
+# ---- bulkscan_multidf WITHOUT the matrix (blmm_bulkscan_multidf_reduced): per trait the peak LOD and its LOCUS and, `threshold`
+# given, every (locus, trait, LOD) with LOD > threshold, out of the k-df scan kernels' epilogues; the P x m matrix is never written.
+# The same values as the column maxima / the threshold filter of bulkscan_multidf's L, bit for bit.  Keywords as bulkscan_multidf.
+function bulkscan_multidf_reduced(Y::Array{Float64, 2}, G::Array{Float64, 2}, K::Array{Float64, 2}, k::Integer; kwargs...)
+    return bulkscan_multidf_reduced(Y, G, ones(size(Y, 1), 1), K, k; kwargs..., addIntercept = false)
+end
+function bulkscan_multidf_reduced(Y::Array{Float64, 2}, G::Array{Float64, 2}, Covar::Array{Float64, 2}, K::Array{Float64, 2}, k::Integer;
+                                  method::String = "null-grid", h2_grid::Array{Float64, 1} = collect(0.0:0.1:0.9),
+                                  threshold::Union{Nothing, Float64} = nothing, cap::Int64 = 1048576, addIntercept::Bool = true,
+                                  weights::Union{Missing, Array{Float64, 1}} = missing, prior_variance::Float64 = 1.0,
+                                  prior_sample_size::Float64 = 0.0, reml::Bool = false, optim_interval::Int64 = 1,
+                                  decomp_scheme::String = "eigen")
+    (n, m) = size(Y); p = size(G, 2)
+    (size(G, 1) != n || size(K, 1) != n || size(K, 2) != n || size(Covar, 1) != n) && error("Dimension mismatch.")
+    (weights !== missing && length(weights) != n) && error("Dimension mismatch.")
+    method in ("null-grid", "null-exact", "alt-grid") || error("Unknown method `$method`; choose null-exact, null-grid or alt-grid.")
+    (k < 1 || p % k != 0) && error("bulkscan_multidf: the number of columns of G must be a multiple of k >= 1")
+    (threshold !== nothing && cap < 1) && error("bulkscan_multidf_reduced: `threshold` needs a positive `cap`")
+    check_n(n)
+    meth = method == "null-exact" ? NULL_EXACT : method == "null-grid" ? NULL_GRID : ALT_GRID
+    o = BlmmOpts(meth, reml, addIntercept, decomp(decomp_scheme), optim_interval, 0, prior_variance, prior_sample_size)
+    mx = Vector{Float64}(undef, m); arg = Vector{Int64}(undef, m); h2 = Vector{Float64}(undef, m)
+    want = threshold !== nothing
+    st = BlmmStatus()
+    while true
+        c1 = max(cap, 1)
+        ii = Vector{Int32}(undef, c1); jj = Vector{Int32}(undef, c1); ll = Vector{Float64}(undef, c1); cnt = zeros(Int64, 1)
+        GC.@preserve Y G Covar K weights h2_grid mx arg h2 ii jj ll cnt begin
+            r = BlmmReduced(pointer(mx), pointer(arg), want ? 1 : 0, want ? threshold : 0.0, want ? cap : 0,
+                            pointer(ii), pointer(jj), pointer(ll), pointer(cnt))
+            check(ccall((:blmm_bulkscan_multidf_reduced, libblmm), Cint,
+                        (Ptr{Cvoid}, Ref{BlmmOpts}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64,
+                         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ref{BlmmReduced}, Ptr{Float64}, Ref{BlmmStatus}),
+                        context(), o, Y, n, m, G, p, Int64(k), Covar, size(Covar, 2), K, ptr_or_null(weights), h2_grid,
+                        length(h2_grid), r, h2, st))
+        end
+        if !want || cnt[1] <= cap
+            raise_status(st)
+            res = (max_lod = mx, argmax = arg .+ 1, h2_null_list = h2)   # argmax: 1-based locus, 0: no comparable entry
+            want || return res
+            nt = cnt[1]
+            ord = sortperm(collect(zip(jj[1:nt], ii[1:nt])))
+            return merge(res, (locus = Int.(ii[1:nt][ord]) .+ 1, trait = Int.(jj[1:nt][ord]) .+ 1, lod = ll[1:nt][ord]))
+        end
+        cap = cnt[1]
+    end
+end
+# ... on DEVICE buffers (`out` holds device pointers; 0-based loci / traits, as the C ABI); returns when the results are complete
+function bulkscan_multidf_reduced_dev!(dY::Ptr{Float64}, n::Int64, m::Int64, dG::Ptr{Float64}, p::Int64, k::Int64, dK::Ptr{Float64},
+                                       out::BlmmReduced, dh2::Ptr{Float64}; method::String = "null-grid",
+                                       h2_grid::Array{Float64, 1} = collect(0.0:0.1:0.9), dCovar::Ptr{Float64} = Ptr{Float64}(C_NULL),
+                                       ncov::Int64 = 0, dweights::Ptr{Float64} = Ptr{Float64}(C_NULL), addIntercept::Bool = true,
+                                       prior_variance::Float64 = 1.0, prior_sample_size::Float64 = 0.0, reml::Bool = false,
+                                       optim_interval::Int64 = 1, decomp_scheme::String = "eigen")
+    method in ("null-grid", "null-exact", "alt-grid") || error("Unknown method `$method`; choose null-exact, null-grid or alt-grid.")
+    check_n(n)
+    meth = method == "null-exact" ? NULL_EXACT : method == "null-grid" ? NULL_GRID : ALT_GRID
+    o = BlmmOpts(meth, reml, ncov == 0 ? true : addIntercept, decomp(decomp_scheme), optim_interval, 0, prior_variance, prior_sample_size)
+    st = BlmmStatus()
+    GC.@preserve h2_grid begin
+        check(ccall((:blmm_bulkscan_multidf_reduced_dev, libblmm), Cint,
+                    (Ptr{Cvoid}, Ref{BlmmOpts}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64,
+                     Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ref{BlmmReduced}, Ptr{Float64}, Ref{BlmmStatus}),
+                    context(), o, dY, n, m, dG, p, k, dCovar, ncov, dK, dweights, h2_grid, length(h2_grid), out, dh2, st))
+    end
+    raise_status(st)
+    return nothing
 end
 
 # ---- conditional bulkscan (blmm_bulkscan_cond): column j of L is the scan of trait j with the null design [Covar G[:, cond[j, :]]].

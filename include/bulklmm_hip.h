@@ -33,7 +33,7 @@ extern "C" {
                             blmm_bulkscan_reduced_async + BLMM_RINFO_* (stream-ordered, flagged traits re-scanned on the device);
                             205 (0.2.2): blmm_status.n_h2_boundary / n_h2_multimodal / n_illcond_rescan (appended), BLMM_FLAG_H2_AUDIT;
                             201: lowrank_shared, readers, blmm_scan_alt; 200: lowrank_fallback, BLMM_STREAM_NULL, multi-GPU;
-                            added since without a new number: blmm_bulkscan_multidf_perms[_dev] */
+                            added since without a new number: blmm_bulkscan_multidf_perms[_dev], blmm_bulkscan_multidf_reduced[_dev] */
 
 typedef struct blmm_ctx blmm_ctx;
 
@@ -160,6 +160,8 @@ int blmm_synchronize(blmm_ctx* ctx);
  *                            cores as well; 0 = fp64 rotation, converted (0.2.2)
  *   "bulk_perm_cols"  0      blmm_bulkscan_perms: largest trait chunk in panel columns (0: sized by the workspace budget); results do
  *                            not depend on it
+ *   "mdf_red_chunk"   0      blmm_bulkscan_multidf_reduced: flagged traits re-scanned per chunk of the scratch (0: a 64 MiB scratch);
+ *                            results do not depend on it
  *   "defaults"               (set only) every key back to its default
  * Every setting gives results within the library's stated tolerances; they exist for tests and for A/B measurements. */
 int blmm_set_tuning(blmm_ctx* ctx, const char* key, double value);
@@ -562,6 +564,29 @@ int blmm_bulkscan_multidf_dev(blmm_ctx* ctx, const blmm_opts* opts, const double
                               int64_t p, int64_t k, const double* dCovar, int64_t ncov, const double* dK, const double* dweights,
                               const double* h2_grid, int64_t ngrid, double* dL_out, int64_t ldL, double* dh2_out,
                               blmm_status* status);
+
+/* ---- the k-degree-of-freedom scan WITHOUT the matrix: blmm_bulkscan_reduced's outputs for blmm_bulkscan_multidf's loci ----------
+ * Arguments are blmm_bulkscan_multidf's with `out` (blmm_reduced; HOST pointers for the host form, DEVICE pointers for _dev) in
+ * place of L_out / ldL; limits and refusals are blmm_bulkscan_multidf's, with its messages.  With P = p / k and L the matrix
+ * blmm_bulkscan_multidf_dev writes for the same inputs and tuning:
+ *   colmax[j] = max_l L[l, j]; argmax[j] = the lowest such LOCUS (0-based), -1 with colmax = -inf when the column has no comparable
+ *   entry (P = 0, all NaN); a NaN is never the maximum, +Inf can be.  want_triplets: every (l, j) with L[l, j] > thr as (ti = locus,
+ *   tj = trait, tlod), order unspecified; *count is exact also beyond cap, and then cap genuine, distinct triplets are stored.
+ * Bit-identical to blmm_lod_colmax_dev / blmm_lod_threshold_dev on that L; h2_out is blmm_bulkscan_multidf's bit for bit and the
+ * status counters (n_nan_lod: the NaNs of the matrix that is never written; n_illcond_rescan) equal its own.
+ * No P x m buffer exists in any route: the scan kernels reduce every trait's 64 loci of a wave to a (maximum, locus) partial in their
+ * epilogues (k_mdf_grid_red, k_mdf_exact_red), k_red_final finishes the maxima; null-exact traits the conditioning guard flags
+ * (c >= 2) are left out there and recomputed by k_mdf_qr into a scratch of a chunk of the flagged list (64 MiB; tuning key
+ * "mdf_red_chunk": flagged traits per chunk, results do not depend on it), reduced with the same rules.  blmm_last_reduced_route:
+ * 1, or 3 when flagged traits were re-scanned.  blmm_last_dims reports no resident matrix afterwards.  A pending
+ * blmm_set_log10p_output request is refused with BLMM_ERR_INVALID and consumed.  Both forms return when the results are complete. */
+int blmm_bulkscan_multidf_reduced(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, int64_t n, int64_t m, const double* G, int64_t p,
+                                  int64_t k, const double* Covar, int64_t ncov, const double* K, const double* weights,
+                                  const double* h2_grid, int64_t ngrid, const blmm_reduced* out, double* h2_out, blmm_status* status);
+int blmm_bulkscan_multidf_reduced_dev(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG,
+                                      int64_t p, int64_t k, const double* dCovar, int64_t ncov, const double* dK, const double* dweights,
+                                      const double* h2_grid, int64_t ngrid, const blmm_reduced* out, double* dh2_out,
+                                      blmm_status* status);
 
 /* ---- permutation thresholds of the k-degree-of-freedom scan: blmm_bulkscan_perms with blmm_bulkscan_multidf's loci -----------
  * Arguments and outputs are blmm_bulkscan_perms', plus k placed as in blmm_bulkscan_multidf (p = P k; locus l is the columns
