@@ -14,7 +14,7 @@ from .api import (BulkLMMError, Context, MultiContext, bulkscan_multi, host_regi
                   bulkscan_perms, bulkscan_perms_dev, calcKinship_loco, bulkscan_loco, bulkscan_loco_dev, chromosome_runs,
                   bulkscan_loco_reduced, bulkscan_loco_reduced_dev, bulkscan_loco_perms, bulkscan_loco_perms_dev,
                   bulkscan_multidf, bulkscan_multidf_dev, bulkscan_effects, bulkscan_effects_dev,
-                  bulkscan_cond, bulkscan_cond_dev, bulkscan_multidf_perms, bulkscan_multidf_perms_dev,
+                  bulkscan_cond, bulkscan_cond_dev, bulkscan_stepwise, bulkscan_stepwise_dev, bulkscan_multidf_perms, bulkscan_multidf_perms_dev,
                   bulkscan_multidf_reduced, bulkscan_multidf_reduced_dev)
 
 __all__ = ["BulkLMMError", "Context", "MultiContext", "bulkscan_multi", "default_context", "calcKinship", "bulkscan", "bulkscan_null", "bulkscan_null_grid",
@@ -26,5 +26,5 @@ __all__ = ["BulkLMMError", "Context", "MultiContext", "bulkscan_multi", "default
            "bulkscan_perms", "bulkscan_perms_dev", "calcKinship_loco", "bulkscan_loco", "bulkscan_loco_dev", "chromosome_runs",
            "bulkscan_loco_reduced", "bulkscan_loco_reduced_dev", "bulkscan_loco_perms", "bulkscan_loco_perms_dev",
            "bulkscan_multidf", "bulkscan_multidf_dev", "bulkscan_effects", "bulkscan_effects_dev",
-           "bulkscan_cond", "bulkscan_cond_dev", "bulkscan_multidf_perms", "bulkscan_multidf_perms_dev",
+           "bulkscan_cond", "bulkscan_cond_dev", "bulkscan_stepwise", "bulkscan_stepwise_dev", "bulkscan_multidf_perms", "bulkscan_multidf_perms_dev",
            "bulkscan_multidf_reduced", "bulkscan_multidf_reduced_dev"]

@@ -34,7 +34,7 @@ EXPORTS = [
     "blmm_bulkscan_loco_reduced", "blmm_bulkscan_loco_reduced_dev", "blmm_bulkscan_loco_perms", "blmm_bulkscan_loco_perms_dev",
     "blmm_bulkscan_multidf", "blmm_bulkscan_multidf_dev", "blmm_bulkscan_effects", "blmm_bulkscan_effects_dev",
     "blmm_bulkscan_cond", "blmm_bulkscan_cond_dev", "blmm_bulkscan_multidf_perms", "blmm_bulkscan_multidf_perms_dev",
-    "blmm_bulkscan_multidf_reduced", "blmm_bulkscan_multidf_reduced_dev",
+    "blmm_bulkscan_multidf_reduced", "blmm_bulkscan_multidf_reduced_dev", "blmm_bulkscan_stepwise", "blmm_bulkscan_stepwise_dev",
 ]
 
 BLMM_NULL_EXACT, BLMM_NULL_GRID, BLMM_ALT_GRID = 0, 1, 2
@@ -48,6 +48,7 @@ BLMM_MULTIDF_MAX_K_GRID, BLMM_MULTIDF_MAX_K_EXACT, BLMM_MULTIDF_MAX_COVARIATES =
 BLMM_EFFECTS_MAX_K = 8  # blmm_bulkscan_effects, both methods
 # blmm_bulkscan_cond (include/bulklmm_hip.h: BLMM_COND_*)
 BLMM_COND_TAU, BLMM_COND_MAX_LOCI, BLMM_COND_INFO_LEN = BLMM_MULTIDF_TAU, 4, 4
+BLMM_STEP_INFO_LEN = 8  # blmm_bulkscan_stepwise's info block
 BLMM_GATHER_NONE, BLMM_GATHER_HOST_SHARDS, BLMM_GATHER_ALLGATHER = 0, 1, 2
 # blmm_bulkscan_reduced_async's info block (include/bulklmm_hip.h: BLMM_RINFO_*)
 BLMM_RINFO_LEN = 9
@@ -235,6 +236,9 @@ def load():
                                                     vp, vp, vp, vp, vp, vp, vp, sp]
     lib.blmm_bulkscan_cond.argtypes = [vp, op, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, vp, vp, vp, sp]
     lib.blmm_bulkscan_cond_dev.argtypes = [vp, op, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, sp]
+    # opts, Y, n, m, G, p, Covar, ncov, K, weights, h2_grid, ngrid, max_loci, threshold, loci, lod, argmax, h2, nloci, sinfo, status
+    lib.blmm_bulkscan_stepwise.argtypes = [vp, op, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, i64, i64, C.c_double, vp, vp, vp, vp, vp, vp, sp]
+    lib.blmm_bulkscan_stepwise_dev.argtypes = lib.blmm_bulkscan_stepwise.argtypes
     # opts, Y, n, m, G, p, k, Covar, ncov, K, weights, h2_grid, ngrid, locus, trait, ntests, beta, se, sigma2, lod, accepted, h2, status
     lib.blmm_bulkscan_effects.argtypes = [vp, op, vp, i64, i64, vp, i64, i64, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, sp]
     lib.blmm_bulkscan_effects_dev.argtypes = lib.blmm_bulkscan_effects.argtypes

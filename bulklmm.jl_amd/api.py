@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import operator
 import warnings
 from typing import NamedTuple, Optional
 
@@ -1826,4 +1827,89 @@ def bulkscan_cond_dev(ctx: Context, Y, G, K, cond, L_out, h2_out, *, cinfo_out=N
         ctx.check(ctx.lib.blmm_bulkscan_cond_dev(ctx.h, C.byref(o), Y.data_ptr(), n, m, G.data_ptr(), p, _dptr(Covar), ncov, K.data_ptr(),
                                                  _dptr(weights), _p(grid), ngrid, _dptr(cond) if s > 0 else None, s, L_out.data_ptr(),
                                                  _ld(L_out, p), h2_out.data_ptr(), _dptr(cinfo_out), C.byref(st) if status else None))
+    return st
+
+
+# ---- forward selection (blmm_bulkscan_stepwise) ----------------------------------------------------------------------------------
+def _stepwise_checks(method: str, n: int, max_loci, threshold, ncov: int, addIntercept: bool):
+    """The library's refusals of blmm_bulkscan_stepwise that need no data (blmm_api.hip: stepwise_check), in its order."""
+    try:
+        S = operator.index(max_loci)
+    except TypeError:
+        raise BulkLMMError("bulkscan_stepwise: max_loci must be an integer", -1) from None
+    if S < 1:
+        raise BulkLMMError("bulkscan_stepwise: max_loci must be at least 1", -1)
+    if S > L.BLMM_COND_MAX_LOCI:
+        raise BulkLMMError("bulkscan_stepwise: at most 4 loci per trait", -10)
+    if _null_covariates(ncov, addIntercept) + S > L.BLMM_MULTIDF_MAX_COVARIATES:
+        raise BulkLMMError("bulkscan_stepwise: more than 8 null-design columns (covariates incl. intercept + max_loci) are not supported", -10)
+    if not float(threshold) >= 0.0:
+        raise BulkLMMError("bulkscan_stepwise: the threshold must be a number >= 0", -1)
+    _cond_checks(method, n, S, ncov, addIntercept)
+    return S
+
+
+def bulkscan_stepwise(Y, G, K, Covar=None, *, max_loci: int = 4, threshold: float, method: str = "null-grid", h2_grid=None,
+                      addIntercept: bool = True, weights=None, prior_variance: float = 1.0, prior_sample_size: float = 0.0,
+                      reml: bool = False, optim_interval: int = 1, decomp_scheme: str = "eigen", return_status: bool = False,
+                      ctx: Optional[Context] = None) -> dict:
+    """Forward selection of up to `max_loci` loci per trait (blmm_bulkscan_stepwise): round t scans every trait still active with
+    the loci it has so far in its null model -- bit for bit bulkscan_cond with the table of the round, reduced to the column
+    maxima -- and a trait whose peak LOD is above `threshold` (strictly) takes the peak marker as its next locus.  One upload, one
+    eigen phase, no p x m matrix; from round 1 on only the active traits are scanned.
+    Returns {"loci": (m, S) int64, -1 beyond a trait's loci (bulkscan_cond takes it as `cond`), "lod", "argmax", "h2": (m, S + 1),
+    NaN / -1 / NaN for the rounds a trait was not active in, "nloci": (m,), "rounds", "active": (S + 1,) traits per round,
+    "n_rule_zero", "n_cond_traits" [, "status"]}."""
+    Y, G, K, n, m, p = _host_arrays(Y, G, K)
+    cov, ncov, w, addIntercept = _host_covariates(Covar, weights, n, addIntercept)
+    S = _stepwise_checks(method, n, max_loci, threshold, ncov, addIntercept)
+    meth = _METHODS[method]
+    grid, ngrid = _grid(meth, h2_grid)
+    o = _opts(meth, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
+    ctx = ctx or default_context()  # after the argument checks: those must not need a GPU
+    loci = np.empty((m, S), dtype=np.int64)
+    lod = np.empty((m, S + 1), dtype=np.float64)
+    arg = np.empty((m, S + 1), dtype=np.int64)
+    h2 = np.empty((m, S + 1), dtype=np.float64)
+    nloci = np.empty(m, dtype=np.int64)
+    info = np.zeros(L.BLMM_STEP_INFO_LEN, dtype=np.int64)
+    st = L.blmm_status()
+    ctx.check(ctx.lib.blmm_bulkscan_stepwise(ctx.h, C.byref(o), _p(Y), n, m, _p(G), p, _p(cov), ncov, _p(K), _p(w), _p(grid), ngrid,
+                                             S, float(threshold), _p(loci), _p(lod), _p(arg), _p(h2), _p(nloci), _p(info), C.byref(st)))
+    _raise_status(st)
+    out = {"loci": loci, "lod": lod, "argmax": arg, "h2": h2, "nloci": nloci, "rounds": int(info[0]),
+           "active": info[3:4 + S].copy(), "n_rule_zero": int(info[2]), "n_cond_traits": int(info[1])}
+    if return_status:
+        out["status"] = st
+    return out
+
+
+def bulkscan_stepwise_dev(ctx: Context, Y, G, K, loci_out, lod_out, argmax_out, h2_out, nloci_out, *, threshold: float, sinfo_out=None,
+                          method: str = "null-grid", h2_grid=None, Covar=None, weights=None, addIntercept: bool = True,
+                          prior_variance: float = 1.0, prior_sample_size: float = 0.0, reml: bool = False, optim_interval: int = 1,
+                          decomp_scheme: str = "eigen", status: bool = False):
+    """blmm_bulkscan_stepwise_dev on torch tensors in bulkscan_dev's layout: Y (m, n), G (p, n), K (n, n); loci_out (m, S) int64 --
+    its width is max_loci --, lod_out / argmax_out / h2_out (m, S + 1) (float64 / int64 / float64), nloci_out (m) int64, sinfo_out (8)
+    int64 or None, all contiguous.  Enqueues on the context's stream and waits for it between the rounds; without `status` the
+    results are valid after ctx.synchronize()."""
+    m, n = Y.shape
+    p = G.shape[0]
+    ncov, addIntercept, st = _dev_args(Covar, addIntercept, status)
+    if loci_out.dim() != 2:
+        raise BulkLMMError("bulkscan_stepwise: loci_out must be a contiguous (m, max_loci) int64 tensor", -2)
+    S = _stepwise_checks(method, n, int(loci_out.shape[1]), threshold, ncov, addIntercept)   # the library's refusals first, in its order
+    if loci_out.shape[0] != m or not loci_out.is_contiguous() or loci_out.element_size() != 8:
+        raise BulkLMMError("bulkscan_stepwise: loci_out must be a contiguous (m, max_loci) int64 tensor", -2)
+    for t in (lod_out, argmax_out, h2_out):
+        if tuple(t.shape) != (m, S + 1) or not t.is_contiguous() or t.element_size() != 8:
+            raise BulkLMMError("bulkscan_stepwise: lod_out, argmax_out and h2_out must be contiguous (m, max_loci + 1) 8-byte tensors", -2)
+    if nloci_out.numel() != m or nloci_out.element_size() != 8:
+        raise BulkLMMError("bulkscan_stepwise: nloci_out must hold m int64 values", -2)
+    meth = _METHODS[method]
+    grid, ngrid = _grid(meth, h2_grid)
+    o = _opts(meth, reml, addIntercept, decomp_scheme, optim_interval, prior_variance, prior_sample_size)
+    ctx.check(ctx.lib.blmm_bulkscan_stepwise_dev(ctx.h, C.byref(o), Y.data_ptr(), n, m, G.data_ptr(), p, _dptr(Covar), ncov, K.data_ptr(),
+                                                 _dptr(weights), _p(grid), ngrid, S, float(threshold), loci_out.data_ptr(),
+                                                 lod_out.data_ptr(), argmax_out.data_ptr(), h2_out.data_ptr(), nloci_out.data_ptr(),
+                                                 _dptr(sinfo_out), C.byref(st) if status else None))
     return st

@@ -858,7 +858,8 @@ void blmm_destroy(blmm_ctx* ctx) {
                     &ctx->wbQ, &ctx->wbW, &ctx->wbRk, &ctx->lrT, &ctx->lrC, &ctx->lrL, &ctx->lrFlag, &ctx->lrPart, &ctx->lrPerm, &ctx->lrDen0, &ctx->eigW, &ctx->xf32, &ctx->pf32, &ctx->brSt, &ctx->brList, &ctx->illList, &ctx->qrSlab, &ctx->lodtab, &ctx->dynFac, &ctx->pvtab, &ctx->outP, &ctx->redbuf, &ctx->redtrip, &ctx->altC, &ctx->rf32, &ctx->btG, &ctx->redflag, &ctx->bperm,
                     &ctx->locoK, &ctx->locoPart, &ctx->locoChr, &ctx->locoStat, &ctx->locoKs, &ctx->locoV, &ctx->locoLraw,
                     &ctx->locoCmx, &ctx->locoCarg, &ctx->locoPerm, &ctx->mdfR, &ctx->mdfT, &ctx->mdfScr,
-                    &ctx->effX, &ctx->effIdx, &ctx->effWork, &ctx->effOut, &ctx->effSlab, &ctx->condIdx, &ctx->condWork};
+                    &ctx->effX, &ctx->effIdx, &ctx->effWork, &ctx->effOut, &ctx->effSlab, &ctx->condIdx, &ctx->condWork,
+                    &ctx->stepWork, &ctx->stepOut, &ctx->condScr};
   for (DevBuf* b : bufs) if (b->p) hipFree(b->p);
   for (auto& s : ctx->evsets) for (auto& e : s.e) (void)hipEventDestroy(e);
   if (ctx->side) { (void)hipStreamSynchronize(ctx->side); (void)hipStreamDestroy(ctx->side); }
@@ -996,6 +997,7 @@ static const struct { const char* key; int kind; size_t off; double lo, hi; } kT
   {"f32_rotation", 1, offsetof(blmm::Tuning, f32_rotation), 0, 1},
   {"bulk_perm_cols", 1, offsetof(blmm::Tuning, bulk_perm_cols), 0, 2147483647.0},
   {"mdf_red_chunk", 1, offsetof(blmm::Tuning, mdf_red_chunk), 0, 2147483647.0},
+  {"cond_red_chunk", 1, offsetof(blmm::Tuning, cond_red_chunk), 0, 2147483647.0},
 };
 int blmm_set_tuning(blmm_ctx* ctx, const char* key, double value) {
   if (!ctx) return BLMM_ERR_INVALID;
@@ -3359,6 +3361,173 @@ int blmm_bulkscan_cond(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, in
   if ((rc = hc.down(cinfo_out, ctx->condWork.p, sizeof(int64_t) * BLMM_COND_INFO_LEN))) return rc;
   if ((rc = hc.finish())) return rc;
   return check_sticky(ctx);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Forward selection of up to max_loci loci per trait (include/bulklmm_hip.h: blmm_bulkscan_stepwise): the rounds of
+// blmm_bulkscan_cond on one upload, one eigen phase and one pair of rotations, every round reduced to its column maxima in the scan's
+// epilogue (no p x m buffer) and run on the traits still active.  Refusals first, in the same order in both forms.
+static int stepwise_check(blmm_ctx* ctx, const blmm_opts* opts, int64_t n, int64_t m, int64_t p, int64_t S, double thr, const double* Covar,
+                          int64_t ncov) {
+  int rc = check_opts(ctx, opts);
+  if (rc) return rc;
+  if (S < 1) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_stepwise: max_loci must be at least 1");
+  if (S > BLMM_COND_MAX_LOCI) return fail(ctx, BLMM_ERR_UNSUPPORTED, "bulkscan_stepwise: at most 4 loci per trait");
+  if (ncov >= 0 && null_cov(opts, Covar, ncov).c + S > BLMM_MULTIDF_MAX_COVARIATES)
+    return fail(ctx, BLMM_ERR_UNSUPPORTED, "bulkscan_stepwise: more than 8 null-design columns (covariates incl. intercept + max_loci) are not supported");
+  if (!(thr >= 0.0)) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_stepwise: the threshold must be a number >= 0");
+  return cond_check(ctx, opts, n, m, p, S, Covar, ncov);
+}
+static const char* const kStepPv = "bulkscan_stepwise: a blmm_set_log10p_output request is pending (the call writes no matrix)";
+
+// The guard's list of one round (columns of the active list), behind the reducing scan and k_red_final: k_cond_qr<RED> recomputes a
+// chunk of the listed columns into the scratch and k_mdf_flag_red reduces them over the (-inf, -1) the scan left.  The length of the
+// list stays on the device: every chunk the round's nact columns could fill is launched, and the kernels of a chunk beyond the list
+// return at once, so the round waits for the stream only once (for the next round's size).
+static int stepwise_flagged(blmm_ctx* ctx, const NullModel& nm, const CondArgs& a, double* mx, int64_t* arg) {
+  int64_t chunk = ctx->tune.cond_red_chunk > 0 ? ctx->tune.cond_red_chunk : (int64_t)(64ll << 20) / (int64_t)(sizeof(double) * (size_t)a.p);
+  chunk = std::min(std::max<int64_t>(chunk, 1), a.m);
+  int rc = ensure(ctx, ctx->condScr, sizeof(double) * (size_t)a.p * (size_t)chunk);
+  if (rc) return rc;
+  double* scr = ptr<double>(ctx->condScr);
+  for (int64_t item0 = 0; item0 < a.m; item0 += chunk) {
+    const int64_t nitem = std::min(chunk, a.m - item0);
+    if ((rc = launch_cond_qr(ctx, nm, a, ptr<int>(ctx->illList), nullptr, 0, scr, item0, nitem)) ||
+        (rc = launch_mdf_flag_red(ctx, scr, a.p, ptr<int>(ctx->illList), a.stat, item0, nitem, mx, arg, RedArgs()))) return rc;
+  }
+  return BLMM_OK;
+}
+
+static int stepwise_dev_impl(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG, int64_t p,
+                             const double* dCovar, int64_t ncov, const double* dK, const double* dweights, const double* h2_grid_host,
+                             int64_t ngrid, int64_t S, double thr, int64_t* dloci, double* dlod, int64_t* darg, double* dh2,
+                             int64_t* dnloci, int64_t* dsinfo, blmm_status* status) {
+  int rc = stepwise_check(ctx, opts, n, m, p, S, thr, dCovar, ncov);
+  if (rc) return rc;
+  if (!dY || !dG || !dK || !dloci || !dlod || !darg || !dh2 || !dnloci) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_stepwise: NULL buffer");
+  const bool exact = opts->method == BLMM_NULL_EXACT;
+  if ((rc = enter_device(ctx))) return rc;
+  Timer tm(ctx);
+  Pipe P;
+  double* dgrid = nullptr;
+  if (!exact && (rc = grid_to_device(ctx, h2_grid_host, ngrid, &dgrid))) return rc;
+  // blmm_bulkscan_cond's front, once
+  const bool g_in_flight = ctx->up_pending || ctx->in_wait;
+  if ((rc = prepare(ctx, opts, dY, n, m, dG, p, dCovar, ncov, dK, dweights, 1, P, tm, false, false, /*skip_markers*/ true))) return rc;
+  if (g_in_flight) BLMM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_in, 0));
+  const NullModel nm = null_model(P, opts);
+  // work areas.  condWork as blmm_bulkscan_cond's (per COLUMN here); stepWork: 8 counters, then per column the round's arg-maximum,
+  // h2 and maximum, then the two lists
+  const size_t mm = (size_t)(m > 0 ? m : 1);
+  if ((rc = ensure(ctx, ctx->condWork, sizeof(int64_t) * COND_NINFO + sizeof(int) * mm * (size_t)(S + 2))) ||
+      (rc = ensure(ctx, ctx->stepWork, sizeof(int64_t) * 8 + (sizeof(int64_t) + 2 * sizeof(double) + 2 * sizeof(int)) * mm))) return rc;
+  int64_t* info = ptr<int64_t>(ctx->condWork);
+  int64_t* w = ptr<int64_t>(ctx->stepWork);
+  int64_t* argc = w + 8;
+  double* h2c = reinterpret_cast<double*>(argc + mm);
+  double* mxc = h2c + mm;
+  int* lists[2] = {reinterpret_cast<int*>(mxc + mm), reinterpret_cast<int*>(mxc + mm) + mm};
+  BLMM_HIP(hipMemsetAsync(info, 0, sizeof(int64_t) * COND_NINFO, ctx->stream));
+  BLMM_HIP(hipMemsetAsync(w, 0, sizeof(int64_t) * 8, ctx->stream));
+  StepArgs st;
+  st.S = (int)S; st.m = m; st.thr = thr; st.loci = dloci; st.lod = dlod; st.arg = darg; st.h2 = dh2; st.nloci = dnloci; st.w = w;
+  StepRounds sr = {};
+  if ((rc = launch_step_init(ctx, st))) return rc;
+  CondArgs a;
+  a.n = P.n; a.c = P.c; a.s = (int)S; a.npad = P.npad; a.m = m; a.p = p;
+  a.Xt = nullptr; a.ldx = P.ldx; a.Yt = P.Yt; a.ldy = P.ldy; a.Z0 = P.Z0; a.lam = P.lam; a.cond = dloci;
+  a.kept = reinterpret_cast<int*>(info + COND_NINFO); a.nk = a.kept + mm * (size_t)S; a.flag = a.nk + mm;
+  a.info = info; a.h2 = h2c; a.stat = P.stat;
+  const int ct = P.c + (int)S;
+  const int nslot = 2 * (int)((p + 127) / 128);
+  RedArgs r;
+  if (m > 0 && p > 0) {
+    if ((rc = ensure(ctx, ctx->mdfR, sizeof(double) * (size_t)P.npad * P.ldr)) ||
+        (rc = ensure(ctx, ctx->Xt, sizeof(double) * (size_t)P.npad * P.ldx))) return rc;
+    if ((rc = launch_mdf_rawrot(ctx, ptr<double>(ctx->U), dweights, P.n, P.npad, P.ldr, ptr<double>(ctx->mdfR)))) return rc;
+    P.Xt = ptr<double>(ctx->Xt);
+    if ((rc = launch_rotate(ctx, ptr<double>(ctx->mdfR), P.ldr, P.n, P.npad, dG, p, P.Xt, P.ldx, P.ldx))) return rc;
+    a.Xt = P.Xt;
+    r.ldm = round_up(m, 64);
+    if ((rc = ensure(ctx, ctx->redbuf, (sizeof(double) + sizeof(int)) * (size_t)nslot * (size_t)r.ldm)) ||
+        (rc = ensure(ctx, ctx->panels, sizeof(double) * (size_t)(2 + ct) * P.npad * P.ldy)) ||
+        (rc = ensure(ctx, ctx->illList, sizeof(int) * mm))) return rc;
+    r.pmax = ptr<double>(ctx->redbuf); r.parg = reinterpret_cast<int*>(r.pmax + (size_t)nslot * r.ldm);
+  }
+  // the rounds: every one on the list the round before left; the design is c + S columns wide in all of them (absent loci are zero
+  // panels), which is what blmm_bulkscan_cond runs at s = S
+  int64_t nact = m;
+  for (int t = 0; t <= (int)S && nact > 0; ++t) {
+    sr.nact[t] = nact; sr.rounds = t + 1;
+    a.m = nact; a.act = t == 0 ? nullptr : lists[t & 1];
+    if ((rc = launch_cond_null(ctx, nm, a, exact ? nullptr : dgrid, (int)ngrid))) return rc;
+    if (t == 0) tm.mark();
+    if (p > 0) {
+      const int64_t ldp = round_up(nact, 128);
+      if ((rc = launch_cond_panels(ctx, nm, a, ptr<double>(ctx->panels), ldp, ctx->tune.illcond_rho, ptr<int>(ctx->illList)))) return rc;
+      if (t == 0) tm.mark();
+      ScanArgs sa = scan_args(ctx, P, ptr<double>(ctx->panels), ldp, nullptr, 0, nact);
+      sa.c = ct; sa.Pv = nullptr; sa.red = r; sa.cflag = a.flag; sa.cinfo = info;
+      if ((rc = launch_scan_cond(ctx, sa, ct))) return rc;
+    } else if (t == 0) tm.mark();
+    if ((rc = launch_red_final(ctx, r, p > 0 ? nslot : 0, nact, mxc, argc))) return rc;
+    if (p > 0 && P.c + t >= 2 && (rc = stepwise_flagged(ctx, nm, a, mxc, argc))) return rc;   // a design of >= 2 columns exists
+    if ((rc = launch_step_update(ctx, st, t, nact, a.act, lists[(t + 1) & 1], mxc, argc, h2c, P.stat))) return rc;
+    if (t == (int)S) break;
+    BLMM_HIP(hipMemcpyAsync(&nact, w, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    BLMM_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  if (m == 0) { tm.mark(); tm.mark(); }
+  tm.mark();
+  if ((rc = launch_step_finish(ctx, st, sr, info, P.stat, dsinfo))) return rc;
+  return end_call(ctx, P, status, &tm);
+}
+
+int blmm_bulkscan_stepwise_dev(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG, int64_t p,
+                               const double* dCovar, int64_t ncov, const double* dK, const double* dweights, const double* h2_grid,
+                               int64_t ngrid, int64_t max_loci, double threshold, int64_t* dloci_out, double* dlod_out,
+                               int64_t* dargmax_out, double* dh2_out, int64_t* dnloci_out, int64_t* dsinfo_out, blmm_status* status) {
+  if (!ctx) return BLMM_ERR_INVALID;
+  if (pv_take(ctx).armed) return fail(ctx, BLMM_ERR_INVALID, kStepPv);
+  ctx->red_cur = RedArgs();
+  int rc = stepwise_dev_impl(ctx, opts, dY, n, m, dG, p, dCovar, ncov, dK, dweights, h2_grid, ngrid, max_loci, threshold, dloci_out,
+                             dlod_out, dargmax_out, dh2_out, dnloci_out, dsinfo_out, status);
+  if (rc) return rc;
+  clear_last(ctx);                          // no matrix of this call: an earlier one is not served as its result
+  return BLMM_OK;
+}
+
+int blmm_bulkscan_stepwise(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, int64_t n, int64_t m, const double* G, int64_t p,
+                           const double* Covar, int64_t ncov, const double* K, const double* weights, const double* h2_grid,
+                           int64_t ngrid, int64_t max_loci, double threshold, int64_t* loci_out, double* lod_out, int64_t* argmax_out,
+                           double* h2_out, int64_t* nloci_out, int64_t* sinfo_out, blmm_status* status) {
+  if (!ctx) return BLMM_ERR_INVALID;
+  if (pv_take(ctx).armed) return fail(ctx, BLMM_ERR_INVALID, kStepPv);
+  int rc = stepwise_check(ctx, opts, n, m, p, max_loci, threshold, Covar, ncov);
+  if (rc) return rc;
+  if (!Y || !G || !K || !loci_out || !lod_out || !argmax_out || !h2_out || !nloci_out) return fail(ctx, BLMM_ERR_INVALID, "bulkscan_stepwise: NULL buffer");
+  HostCall hc(ctx);
+  // device side of the outputs: int64 loci (S m), argmax ((S + 1) m), nloci (m), sinfo; double lod, h2 ((S + 1) m each)
+  const size_t mm = (size_t)(m > 0 ? m : 1), S = (size_t)max_loci, um = (size_t)m;
+  if ((rc = hc.begin()) || (rc = ensure(ctx, ctx->stepOut, sizeof(int64_t) * (mm * (2 * S + 2) + BLMM_STEP_INFO_LEN) + sizeof(double) * 2 * (S + 1) * mm)))
+    return rc;
+  int64_t* dloci = ptr<int64_t>(ctx->stepOut);
+  int64_t* darg = dloci + S * mm;
+  int64_t* dnloci = darg + (S + 1) * mm;
+  int64_t* dsinfo = dnloci + mm;
+  double* dlod = reinterpret_cast<double*>(dsinfo + BLMM_STEP_INFO_LEN);
+  double* dh2 = dlod + (S + 1) * mm;
+  HostCall::In d;
+  if ((rc = hc.inputs(Y, n, m, G, p, K, Covar, ncov, weights, /*defer*/ true, &d))) return rc;
+  ctx->red_cur = RedArgs();
+  if ((rc = stepwise_dev_impl(ctx, opts, d.Y, n, m, d.G, p, d.Cov, d.ncov, d.K, d.W, h2_grid, ngrid, max_loci, threshold, dloci, dlod,
+                              darg, dh2, dnloci, dsinfo, status))) return rc;
+  clear_last(ctx);
+  if (m > 0 && ((rc = hc.down(loci_out, dloci, sizeof(int64_t) * S * um)) || (rc = hc.down(lod_out, dlod, sizeof(double) * (S + 1) * um)) ||
+                (rc = hc.down(argmax_out, darg, sizeof(int64_t) * (S + 1) * um)) || (rc = hc.down(h2_out, dh2, sizeof(double) * (S + 1) * um)) ||
+                (rc = hc.down(nloci_out, dnloci, sizeof(int64_t) * um)))) return rc;
+  if ((rc = hc.down(sinfo_out, dsinfo, sizeof(int64_t) * BLMM_STEP_INFO_LEN))) return rc;
+  return (rc = hc.finish()) ? rc : check_sticky(ctx);
 }
 
 // ---------------------------------------------------------------------------------------------------

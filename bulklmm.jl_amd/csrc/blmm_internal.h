@@ -61,6 +61,7 @@ struct Tuning {
   int f32_rotation = 1;         // fp32 permutation path (blmm_scan_perms_f32, c <= 3): 1 = rotate G on the fp32 matrix cores straight into k_scan_f32's operand layout; 0 = fp64 rotation + conversion (round 3)
   int eigen_solver = 0;         // 0: by n (fast path + Jacobi up to 124, tridiagonalisation + divide and conquer beyond); 1: Jacobi; 2: divide and conquer
   int mdf_red_chunk = 0;        // blmm_bulkscan_multidf_reduced: flagged traits re-scanned per chunk of the scratch; 0: from a 64 MiB budget
+  int cond_red_chunk = 0;       // blmm_bulkscan_stepwise: the same for the conditional scan's flagged traits
   int bulk_perm_cols = 0;       // blmm_bulkscan_perms: largest trait chunk in panel columns (traits x (nperms + 1)); 0: from the memory budget
 };
 
@@ -115,6 +116,7 @@ struct blmm_ctx {
       mdfR, mdfT,          // blmm_bulkscan_multidf: the uncentred rotation and the null-grid factor table (kernels_mdf.hip)
       mdfScr,              // blmm_bulkscan_multidf_reduced: the flagged traits' columns, a chunk of the guard's list wide
       condIdx, condWork,   // blmm_bulkscan_cond (kernels_cond.hip): the host form's index table; kept columns, counts, guard flags, info counters
+      stepWork, stepOut, condScr,   // blmm_bulkscan_stepwise: per-column results, the two lists, counters; the host form's tables; the flagged columns
       effX, effIdx, effWork, effOut, effSlab;   // blmm_bulkscan_effects (kernels_effects.hip): the rotated markers column-major, the host form's
                                                 // test lists, the sort's counters + permutation, the host form's outputs, the waves' slab
   // event sets: one per timed call since the last blmm_read_timings (grown on demand, reused afterwards)
@@ -576,12 +578,29 @@ struct CondArgs {
   int64_t* info;                       // COND_NINFO counters
   double* h2;
   int64_t* stat;
+  // blmm_bulkscan_stepwise: the active traits, ascending.  Non-null: a.m columns, column jj is trait act[jj] of Yt and cond, and
+  // kept / nk / flag / h2 (and the panels, the guard's list) are indexed by COLUMN.  nullptr: column jj is trait jj.
+  const int* act = nullptr;
 };
 // step 1 and the null model on D_j = [Z0, kept columns]: fitlmm (grid_dev == nullptr) or the first arg-max over the grid
 int launch_cond_null(blmm_ctx* ctx, const NullModel& nm, const CondArgs& a, const double* grid_dev, int ngrid);
 // k_panels' layout with 2 + c + s panels per trait (zero panels beyond 1 + c + r_j); flags the traits of the conditioning guard
 int launch_cond_panels(blmm_ctx* ctx, const NullModel& nm, const CondArgs& a, double* panels, int64_t ldp, double rho_min, int* list);
-int launch_cond_qr(blmm_ctx* ctx, const NullModel& nm, const CondArgs& a, const int* list, double* L, int64_t ldL);
+// scr != nullptr: the listed columns item0 .. item0 + nitem - 1 into columns 0 .. of the compact scratch scr (ld p), L untouched
+int launch_cond_qr(blmm_ctx* ctx, const NullModel& nm, const CondArgs& a, const int* list, double* L, int64_t ldL,
+                   double* scr = nullptr, int64_t item0 = 0, int64_t nitem = 0);
+// blmm_bulkscan_stepwise: the caller's tables (device) and four work counters: w[0] the next round's traits, w[1] the guard's
+// re-scans so far, w[2] round 0's n_zero_norm, w[3] traits with at least one locus
+struct StepArgs {
+  int S; int64_t m; double thr;
+  int64_t* loci; double* lod; int64_t* arg; double* h2; int64_t* nloci;
+  int64_t* w;
+};
+struct StepRounds { int64_t rounds; int64_t nact[5]; };
+int launch_step_init(blmm_ctx* ctx, const StepArgs& s);                      // NaN / -1 / NaN everywhere, no loci
+int launch_step_update(blmm_ctx* ctx, const StepArgs& s, int t, int64_t nact, const int* act, int* next, const double* mx,
+                       const int64_t* arg, const double* h2, int64_t* stat);
+int launch_step_finish(blmm_ctx* ctx, const StepArgs& s, const StepRounds& r, const int64_t* cinfo, int64_t* stat, int64_t* sinfo);
 
 // kernels_effects.hip: blmm_bulkscan_effects, coefficients and standard errors at a list of (locus, trait) tests
 struct EffArgs {

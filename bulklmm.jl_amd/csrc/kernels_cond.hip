@@ -16,6 +16,10 @@
 //   the scan       k_scan<.., COND> (kernels_scan.hip): the f64-MFMA contraction with 2 + CT accumulators and the rank-rule epilogue.
 //   k_cond_qr      the listed traits again with an orthonormal basis of span(sqrt(W) D_j) (Gram-Schmidt twice) and explicit
 //                  residuals (ortho_basis.h), the rank rule on the explicit norms.
+// blmm_bulkscan_stepwise runs the same kernels round after round on a compact list of active traits (CondArgs::act: panel column jj
+// is trait act[jj]; kept / nk / flag / h2 are per column), the scan in its reducing form, k_cond_qr<RED> into a compact scratch, and
+//   k_step_update  one workgroup: a round's (maximum, marker) per column -> the caller's tables, the trait's next locus, and the
+//                  next round's list in ascending trait order.
 #include "blmm_internal.h"
 #include "fastmath.h"
 #include "ortho_basis.h"
@@ -123,7 +127,7 @@ __global__ void __launch_bounds__(64) k_cond_null(NullModel nm, CondArgs a, cons
   const int n = a.n, c = a.c, s = a.s, lane = threadIdx.x;
   double* sY = sh;
   double* sX = sh + n;
-  const int64_t j = blockIdx.x;
+  const int64_t jj = blockIdx.x, j = a.act ? a.act[jj] : jj;   // column jj of the per-column arrays, trait j of Yt and cond
   // the trait's entries: valid ones in order; an index outside [-1, p) makes the whole trait NaN
   int idx[COND_SMAX], nv = 0;
   bool invalid = false;
@@ -142,8 +146,8 @@ __global__ void __launch_bounds__(64) k_cond_null(NullModel nm, CondArgs a, cons
   }
   if (invalid) {
     if (lane == 0) {
-      a.nk[j] = -1; a.flag[j] = 0; a.h2[j] = NAN;
-      for (int e = 0; e < s; ++e) a.kept[j * s + e] = -1;
+      a.nk[jj] = -1; a.flag[jj] = 0; a.h2[jj] = NAN;
+      for (int e = 0; e < s; ++e) a.kept[jj * s + e] = -1;
       atomicAdd((unsigned long long*)&a.info[4], 1ull);
     }
     return;
@@ -198,9 +202,9 @@ __global__ void __launch_bounds__(64) k_cond_null(NullModel nm, CondArgs a, cons
     __syncthreads();
   }
   if (lane == 0) {
-    a.nk[j] = r;
+    a.nk[jj] = r;
 #pragma unroll
-    for (int e = 0; e < COND_SMAX; ++e) if (e < s) a.kept[j * s + e] = (e < r) ? idx[e] : -1;
+    for (int e = 0; e < COND_SMAX; ++e) if (e < s) a.kept[jj * s + e] = (e < r) ? idx[e] : -1;
     if (nv > r) atomicAdd((unsigned long long*)&a.info[1], (unsigned long long)(nv - r));
     if (r >= 1) atomicAdd((unsigned long long*)&a.info[2], 1ull);
   }
@@ -228,7 +232,7 @@ __global__ void __launch_bounds__(64) k_cond_null(NullModel nm, CondArgs a, cons
     wave_count(&a.stat[ST_H2_BOUNDARY], lane == 0 && h2_on_boundary(best));
   }
   if (lane == 0) {
-    a.h2[j] = best;
+    a.h2[jj] = best;
     if (hit_max) atomicAdd((unsigned long long*)&a.stat[ST_BRENT_MAXIT], 1ull);
     if (nonpos) atomicAdd((unsigned long long*)&a.stat[ST_NONPOS_W], 1ull);
   }
@@ -261,6 +265,7 @@ __global__ void __launch_bounds__(256) k_cond_panels(NullModel nm, CondArgs a, d
     return;
   }
   const int ct = c + rj;
+  const int64_t yj = a.act ? a.act[j] : j;   // the column's trait in Yt
   int kc[COND_SMAX];
 #pragma unroll
   for (int e = 0; e < COND_SMAX; ++e) kc[e] = (e < rj && e < s) ? a.kept[j * s + e] : 0;
@@ -287,7 +292,7 @@ __global__ void __launch_bounds__(256) k_cond_panels(NullModel nm, CondArgs a, d
   for (int q = 0; q < CT; ++q) v[q] = 0.0;
   for (int k = 0; k < n; ++k) {
     const double w = fabs(1.0 / fma(delta, sLam[k], 1.0));
-    const double y = a.Yt[(int64_t)k * a.ldy + j];
+    const double y = a.Yt[(int64_t)k * a.ldy + yj];
     const double wy = w * y;
     syy = fma(wy, y, syy);
     double z[CT];
@@ -362,7 +367,7 @@ __global__ void __launch_bounds__(256) k_cond_panels(NullModel nm, CondArgs a, d
       w = fabs(1.0 / fma(delta, sLam[k], 1.0));
       double z[CT];
       row(z, k);
-      double res = a.Yt[(int64_t)k * a.ldy + j];
+      double res = a.Yt[(int64_t)k * a.ldy + yj];
 #pragma unroll
       for (int q = 0; q < CT; ++q) res = fma(-beta[q], z[q], res);
       p0 = w * res * isy;
@@ -384,11 +389,15 @@ __global__ void __launch_bounds__(256) k_cond_panels(NullModel nm, CondArgs a, d
 // ---- the guard's re-scan: ortho_basis.h's front on the per-trait design, one column per test ------------------------------------------
 constexpr int COND_CT = BLMM_MULTIDF_MAX_COVARIATES;
 // One workgroup per listed trait at a time; buf: (CTmax + 2) n doubles (sqrt weights, the orthonormal basis, the unit trait residual)
+// RED (blmm_bulkscan_stepwise): there is no L.  The listed columns item0 .. item0 + nitem - 1 go to the columns 0 .. nitem - 1 of a
+// compact scratch (L, ld ldL) for k_mdf_flag_red, as k_mdf_qr<K, RED> does it.
+template <bool RED>
 __global__ void __launch_bounds__(256) k_cond_qr(CondArgs a, int ctmax, const int* __restrict__ list, double* slab,
-                                                 double* __restrict__ L, int64_t ldL) {
+                                                 double* __restrict__ L, int64_t ldL, int64_t item0, int64_t nitem) {
   extern __shared__ __attribute__((aligned(16))) double sh[];
   __shared__ double s_red[4];
-  const int64_t cnt = a.stat[ST_ILLCOND];
+  int64_t cnt = a.stat[ST_ILLCOND];
+  if (RED && cnt > item0 + nitem) cnt = item0 + nitem;
   if (cnt <= 0) return;
   const int n = a.n, c = a.c, s = a.s;
   double* buf = slab ? slab + (size_t)blockIdx.x * (size_t)(ctmax + 2) * n : sh;
@@ -397,12 +406,14 @@ __global__ void __launch_bounds__(256) k_cond_qr(CondArgs a, int ctmax, const in
   double* yb = buf + (size_t)(1 + ctmax) * n;
   const double scale = -0.5 * (double)n;
   int nnan = 0, nrule = 0;
-  for (int64_t item = blockIdx.x; item < cnt; item += gridDim.x) {
+  for (int64_t item = (RED ? item0 : 0) + blockIdx.x; item < cnt; item += gridDim.x) {
     const int64_t j = list[item];
+    const int64_t yj = a.act ? a.act[j] : j;
+    double* __restrict__ out = L + (RED ? item - item0 : j) * ldL;
     const int ct = c + a.nk[j];
     const int* kj = a.kept + j * s;
     auto col = [&](int q, int k) { return q < c ? a.Z0[(size_t)q * n + k] : a.Xt[(int64_t)k * a.ldx + kj[q - c]]; };
-    const double nn = weighted_basis<256, 1>(n, ct, a.h2[j], a.lam, col, a.Yt + j, a.ldy, Sw, Qb, yb, s_red);
+    const double nn = weighted_basis<256, 1>(n, ct, a.h2[j], a.lam, col, a.Yt + yj, a.ldy, Sw, Qb, yb, s_red);
     const double inv = 1.0 / sqrt(nn);
     for (int k = threadIdx.x; k < n; k += 256) yb[k] *= inv;
     __syncthreads();
@@ -427,7 +438,7 @@ __global__ void __launch_bounds__(256) k_cond_qr(CondArgs a, int ctmax, const in
         lod = scale * log10(u1);
         if (!(u1 > 0.0)) { lod = (u1 == 0.0) ? INFINITY : NAN; nnan += (u1 == 0.0) ? 0 : 1; }
       }
-      L[j * ldL + i] = lod;
+      out[i] = lod;
     }
   }
   if (nnan) atomicAdd((unsigned long long*)&a.stat[ST_NAN_LOD], (unsigned long long)nnan);
@@ -463,13 +474,100 @@ int launch_cond_panels(blmm_ctx* ctx, const NullModel& nm, const CondArgs& a, do
   return BLMM_OK;
 }
 
-int launch_cond_qr(blmm_ctx* ctx, const NullModel& nm, const CondArgs& a, const int* list, double* L, int64_t ldL) {
+int launch_cond_qr(blmm_ctx* ctx, const NullModel& nm, const CondArgs& a, const int* list, double* L, int64_t ldL, double* scr,
+                   int64_t item0, int64_t nitem) {
   const int ctmax = a.c + a.s;
-  if (a.p <= 0 || ctmax < 2) return BLMM_OK;
+  if (a.p <= 0 || ctmax < 2 || (scr && nitem <= 0)) return BLMM_OK;
   size_t lds; double* slab; unsigned grid;
   if (int rc = qr_workspace(ctx, ctmax, nm.n, &lds, &slab, &grid)) return rc;
-  if (lds > 48 * 1024) BLMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cond_qr), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k_cond_qr, dim3(grid), dim3(256), lds, ctx->stream, a, ctmax, list, slab, L, ldL);
+#define QR(RED, OUT, LD) do { if (lds > 48 * 1024) BLMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cond_qr<RED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+    hipLaunchKernelGGL(k_cond_qr<RED>, dim3(grid), dim3(256), lds, ctx->stream, a, ctmax, list, slab, OUT, LD, item0, nitem); } while (0)
+  if (scr) QR(true, scr, a.p); else QR(false, L, ldL);
+#undef QR
+  KCHECK();
+  return BLMM_OK;
+}
+
+// ---- blmm_bulkscan_stepwise: the caller's tables and the active list between the rounds ----------------------------------------------
+__global__ void __launch_bounds__(256) k_step_init(StepArgs s) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= s.m) return;
+  for (int t = 0; t <= s.S; ++t) { s.lod[j * (s.S + 1) + t] = NAN; s.arg[j * (s.S + 1) + t] = -1; s.h2[j * (s.S + 1) + t] = NAN; }
+  for (int e = 0; e < s.S; ++e) s.loci[j * s.S + e] = -1;
+  s.nloci[j] = 0;
+}
+
+// One workgroup walks the round's nact columns (act == nullptr: column jj is trait jj) with a running offset, so the next list is
+// in ascending trait order whatever the launch.  Column jj's (mx, arg, h2) go to slot t of trait j's rows; a trait whose maximum is
+// above the threshold (strictly; never in round S) gets the marker as its locus t and stays on the list.  Then the work counters:
+// w[0] = the next round's traits; the guard's list length is added to w[1] and zeroed for the next round's k_cond_panels;
+// n_zero_norm stays what round 0 counted (w[2]).
+__global__ void __launch_bounds__(1024) k_step_update(StepArgs s, int t, int64_t nact, const int* __restrict__ act, int* __restrict__ next,
+                                                      const double* __restrict__ mx, const int64_t* __restrict__ arg,
+                                                      const double* __restrict__ h2, int64_t* __restrict__ stat) {
+  __shared__ int s_cnt[16];
+  __shared__ int64_t s_base;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (threadIdx.x == 0) s_base = 0;
+  __syncthreads();
+  for (int64_t j0 = 0; j0 < nact; j0 += 1024) {
+    const int64_t jj = j0 + threadIdx.x;
+    bool sel = false;
+    int64_t j = -1;
+    if (jj < nact) {
+      j = act ? act[jj] : jj;
+      const double v = mx[jj];
+      const int64_t ai = arg[jj];
+      s.lod[j * (s.S + 1) + t] = v; s.arg[j * (s.S + 1) + t] = ai; s.h2[j * (s.S + 1) + t] = h2[jj];
+      sel = t < s.S && v > s.thr;
+      if (sel) { s.loci[j * s.S + t] = ai; s.nloci[j] = t + 1; }
+    }
+    const unsigned long long b = __ballot(sel);
+    if (lane == 0) s_cnt[wave] = __builtin_popcountll(b);
+    __syncthreads();
+    int64_t at = s_base + __builtin_popcountll(b & ((1ull << lane) - 1ull));
+    int tot = 0;
+    for (int w = 0; w < 16; ++w) { at += w < wave ? s_cnt[w] : 0; tot += s_cnt[w]; }
+    if (sel) next[at] = (int)j;
+    __syncthreads();
+    if (threadIdx.x == 0) s_base += tot;
+    __syncthreads();
+  }
+  // Between the rounds the status block is not the caller's: ST_ILLCOND is zero and ST_ZERO_NORM is the current round's until
+  // k_step_finish puts the sums back.  A call that fails in between returns its error and no status, so nobody reads that state.
+  if (threadIdx.x == 0) {
+    s.w[0] = s_base;
+    s.w[1] += stat[ST_ILLCOND]; stat[ST_ILLCOND] = 0;
+    if (t == 0) { s.w[2] = stat[ST_ZERO_NORM]; s.w[3] = s_base; }
+    else stat[ST_ZERO_NORM] = s.w[2];
+  }
+}
+
+// the end of the call: the guard's count back into the status block, the caller's info block
+__global__ void k_step_finish(StepArgs s, StepRounds r, const int64_t* __restrict__ cinfo, int64_t* __restrict__ stat,
+                              int64_t* __restrict__ sinfo) {
+  stat[ST_ILLCOND] = s.w[1];
+  if (!sinfo) return;
+  sinfo[0] = r.rounds; sinfo[1] = s.w[3]; sinfo[2] = cinfo[0];
+  for (int t = 0; t < 5; ++t) sinfo[3 + t] = r.nact[t];
+}
+
+int launch_step_init(blmm_ctx* ctx, const StepArgs& s) {
+  if (s.m <= 0) return BLMM_OK;
+  hipLaunchKernelGGL(k_step_init, dim3((unsigned)((s.m + 255) / 256)), dim3(256), 0, ctx->stream, s);
+  KCHECK();
+  return BLMM_OK;
+}
+
+int launch_step_update(blmm_ctx* ctx, const StepArgs& s, int t, int64_t nact, const int* act, int* next, const double* mx,
+                       const int64_t* arg, const double* h2, int64_t* stat) {
+  hipLaunchKernelGGL(k_step_update, dim3(1), dim3(1024), 0, ctx->stream, s, t, nact, act, next, mx, arg, h2, stat);
+  KCHECK();
+  return BLMM_OK;
+}
+
+int launch_step_finish(blmm_ctx* ctx, const StepArgs& s, const StepRounds& r, const int64_t* cinfo, int64_t* stat, int64_t* sinfo) {
+  hipLaunchKernelGGL(k_step_finish, dim3(1), dim3(1), 0, ctx->stream, s, r, cinfo, stat, sinfo);
   KCHECK();
   return BLMM_OK;
 }

@@ -220,11 +220,12 @@ __device__ __forceinline__ void tile_of32(uint32_t id, uint32_t ntile_t, uint32_
 // the centring projection, so acc[1] is |x~_i|^2 itself.  The epilogue applies multidf's rank rule, |r_i|^2 <= MDF_TAU |x~_i|^2 ->
 // L = +0.0 (counted in a.cinfo[0]), and with MORE the panels beyond the first CFAST are contracted AFTER the main loop, three at
 // a time in the accumulators the in-loop panels have left (the rule needs Sxx unfolded).  Traits a.cflag marks are re-scanned by
-// k_cond_qr, which counts their NaNs and rule hits itself.
+// k_cond_qr, which counts their NaNs and rule hits itself.  With RED (blmm_bulkscan_stepwise) such a trait's partials stay at
+// (-inf, -1) for k_cond_qr's reduced form, as k_mdf_exact_red leaves a flagged trait.
 template <int NX, int MB, int NB, bool TABLE, int W2, bool PERM = false, bool MORE = false, bool PV = false, bool RED = false, bool COND = false>
 __global__ void __launch_bounds__(64 * W2 * W2, 2) k_scan(ScanArgs a, int ntile_i, int64_t nwg) {
   static_assert(!(RED && PV), "reduce-in-epilogue: no p-value output");
-  static_assert(!COND || (!TABLE && !PV && !RED && NX >= 1), "conditional scan: exact mode, L only");
+  static_assert(!COND || (!TABLE && !PV && NX >= 1), "conditional scan: exact mode, no p-value output");
   constexpr int NP = 1 + NX;  // A-side panels consumed
   constexpr int NT = 64 * W2 * W2;
   static_assert(!PERM || (TABLE && NX == 0), "permuted columns: table mode");
@@ -486,6 +487,12 @@ __global__ void __launch_bounds__(64 * W2 * W2, 2) k_scan(ScanArgs a, int ntile_
         for (int nb = 0; nb < NB; ++nb)
           if (rule[nb]) { out[nb] = 0.0; nrule += (counted && i0 + mslot<NB>(r, nb) < a.p) ? 1 : 0; }
       }
+      if constexpr (RED && COND) {
+        if (!counted) {                          // no candidate: a NaN never wins in red_row
+#pragma unroll
+          for (int nb = 0; nb < NB; ++nb) out[nb] = NAN;
+        }
+      }
       if constexpr (RED) red_row<NB>(a.red, trait, i0, r, lane, out, red_valid(a.p, i0, 16 * NB));
       else store_m<NB>(a.L + trait * a.ldL + i0, r, out, a.p - i0);
       if constexpr (PV) {
@@ -548,13 +555,17 @@ static int launch_scan_cond_t(blmm_ctx* ctx, const ScanArgs& a) {
   const int64_t nwg = ntile_t * ntile_i;
   if (nwg <= 0) return BLMM_OK;
   if (nwg > 0x7fffffffLL) return fail(ctx, BLMM_ERR_INVALID, "problem too large for one launch");
-  hipLaunchKernelGGL((k_scan<NX, MB, NB, false, W2, false, MORE, false, false, true>), dim3((unsigned)nwg), dim3(64 * W2 * W2), 0, ctx->stream, a, (int)ntile_i, nwg);
+  if (a.red.pmax)   // blmm_bulkscan_stepwise: slot partials (2 ceil(p / 128) slots, launch_red_final) instead of L
+    hipLaunchKernelGGL((k_scan<NX, MB, NB, false, W2, false, MORE, false, true, true>), dim3((unsigned)nwg), dim3(64 * W2 * W2), 0, ctx->stream, a, (int)ntile_i, nwg);
+  else
+    hipLaunchKernelGGL((k_scan<NX, MB, NB, false, W2, false, MORE, false, false, true>), dim3((unsigned)nwg), dim3(64 * W2 * W2), 0, ctx->stream, a, (int)ntile_i, nwg);
   KCHECK();
   return BLMM_OK;
 }
 
 int launch_scan_cond(blmm_ctx* ctx, const ScanArgs& a, int ct) {
-  if (!a.cflag || !a.cinfo || a.Pv || a.red.pmax || a.c != ct) return fail(ctx, BLMM_ERR_INVALID, "launch_scan_cond: bad arguments");
+  if (!a.cflag || !a.cinfo || a.Pv || (a.red.pmax ? a.red.want_trip != 0 : !a.L) || a.c != ct)
+    return fail(ctx, BLMM_ERR_INVALID, "launch_scan_cond: bad arguments");
   switch (ct) {
     case 1: return launch_scan_cond_t<2, 2, false>(ctx, a);
     case 2: return launch_scan_cond_t<3, 1, false>(ctx, a);

@@ -11,7 +11,7 @@
 # every `ccall`'s symbol, return type and argument tuple (arity and types) against the prototype in include/bulklmm_hip.h.
 module BulkLMMHIP
 
-export bulkscan_cond, bulkscan_effects, bulkscan_multidf, bulkscan_multidf_perms, bulkscan_multidf_reduced, bulkscan_multidf_reduced_dev!, calcKinship_loco, bulkscan_loco, bulkscan_loco_reduced, bulkscan_loco_perms, bulkscan_perms, bulkscan_reduced, bulkscan_reduced_async!, synchronize, DeviceLOD, lod_columns, set_tuning, calcKinship, bulkscan, bulkscan_null, bulkscan_null_grid, bulkscan_alt_grid, bulkscan_alt_exact, scan, bulkscan_multi, lod2log10p, get_thresholds,
+export bulkscan_cond, bulkscan_stepwise, bulkscan_stepwise_dev!, bulkscan_effects, bulkscan_multidf, bulkscan_multidf_perms, bulkscan_multidf_reduced, bulkscan_multidf_reduced_dev!, calcKinship_loco, bulkscan_loco, bulkscan_loco_reduced, bulkscan_loco_perms, bulkscan_perms, bulkscan_reduced, bulkscan_reduced_async!, synchronize, DeviceLOD, lod_columns, set_tuning, calcKinship, bulkscan, bulkscan_null, bulkscan_null_grid, bulkscan_alt_grid, bulkscan_alt_exact, scan, bulkscan_multi, lod2log10p, get_thresholds,
        lod_threshold, lod_colmax, pinned_matrix, host_register, host_unregister
 
 const libblmm = get(ENV, "BULKLMM_HIP_LIB", joinpath(@__DIR__, "..", "csrc", "libbulklmm_hip.so"))
@@ -529,6 +529,83 @@ function bulkscan_cond(Y::Array{Float64, 2}, G::Array{Float64, 2}, Covar::Array{
         return merge(res, (log10Pvals_mat = _last_log10p((p, m), chisq_df), Chisq_df = chisq_df))
     end
     return res
+end
+
+# blmm_bulkscan_stepwise's refusals that need no data (blmm_api.hip: stepwise_check, then cond_check), with its messages and in its order; c: the
+# columns of the null design without the loci
+function stepwise_checks(method::String, n::Int64, max_loci::Int64, threshold::Float64, c::Int64)
+    max_loci >= 1 || error("bulkscan_stepwise: max_loci must be at least 1")
+    max_loci <= 4 || error("bulkscan_stepwise: at most 4 loci per trait")
+    c + max_loci <= 8 || error("bulkscan_stepwise: more than 8 null-design columns (covariates incl. intercept + max_loci) are not supported")
+    threshold >= 0.0 || error("bulkscan_stepwise: the threshold must be a number >= 0")
+    method in ("null-grid", "null-exact", "alt-grid") || error("Unknown method `$method`; choose null-exact, null-grid or alt-grid.")
+    method == "alt-grid" && error("bulkscan_cond: alt-grid is not supported; use null-grid or null-exact")
+    check_n(n)
+    c + max_loci < n || error("Dimension mismatch.")
+    return nothing
+end
+
+# ---- forward selection (blmm_bulkscan_stepwise): up to max_loci loci per trait.  Round t scans the traits still active with the loci
+# they have so far in the null model (bulkscan_cond's column, reduced to its maximum); a trait whose peak LOD is above `threshold`
+# takes the peak marker as its next locus.  Returns loci (m x S, 1-based, 0 beyond a trait's loci: bulkscan_cond takes it as cond),
+# lod / argmax / h2 (m x (S + 1); NaN / 0 / NaN for the rounds a trait was not active in), nloci, rounds, active (traits per round),
+# n_rule_zero, n_cond_traits.
+function bulkscan_stepwise(Y::Array{Float64, 2}, G::Array{Float64, 2}, K::Array{Float64, 2}; kwargs...)
+    return bulkscan_stepwise(Y, G, ones(size(Y, 1), 1), K; kwargs..., addIntercept = false)
+end
+function bulkscan_stepwise(Y::Array{Float64, 2}, G::Array{Float64, 2}, Covar::Array{Float64, 2}, K::Array{Float64, 2};
+                           max_loci::Int64 = 4, threshold::Float64, method::String = "null-grid",
+                           h2_grid::Array{Float64, 1} = collect(0.0:0.1:0.9), addIntercept::Bool = true,
+                           weights::Union{Missing, Array{Float64, 1}} = missing, prior_variance::Float64 = 1.0,
+                           prior_sample_size::Float64 = 0.0, reml::Bool = false, optim_interval::Int64 = 1,
+                           decomp_scheme::String = "eigen")
+    (n, m) = size(Y); p = size(G, 2)
+    (size(G, 1) != n || size(K, 1) != n || size(K, 2) != n || size(Covar, 1) != n) && error("Dimension mismatch.")
+    (weights !== missing && length(weights) != n) && error("Dimension mismatch.")
+    stepwise_checks(method, n, max_loci, threshold, size(Covar, 2) + (addIntercept ? 1 : 0))
+    S = max_loci
+    meth = method == "null-exact" ? NULL_EXACT : NULL_GRID
+    o = BlmmOpts(meth, reml, addIntercept, decomp(decomp_scheme), optim_interval, 0, prior_variance, prior_sample_size)
+    loci = Array{Int64, 2}(undef, S, m)
+    lod = Array{Float64, 2}(undef, S + 1, m); arg = Array{Int64, 2}(undef, S + 1, m); h2 = Array{Float64, 2}(undef, S + 1, m)
+    nloci = Array{Int64, 1}(undef, m)
+    info = zeros(Int64, 8)
+    st = BlmmStatus()
+    GC.@preserve Y G Covar K weights h2_grid loci lod arg h2 nloci info begin
+        check(ccall((:blmm_bulkscan_stepwise, libblmm), Cint,
+                    (Ptr{Cvoid}, Ref{BlmmOpts}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64,
+                     Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Float64, Ptr{Int64}, Ptr{Float64}, Ptr{Int64},
+                     Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ref{BlmmStatus}),
+                    context(), o, Y, n, m, G, p, Covar, size(Covar, 2), K, ptr_or_null(weights), h2_grid,
+                    length(h2_grid), Int64(S), threshold, loci, lod, arg, h2, nloci, info, st))
+    end
+    raise_status(st)
+    return (loci = permutedims(loci) .+ 1, lod = permutedims(lod), argmax = permutedims(arg) .+ 1, h2 = permutedims(h2),
+            nloci = nloci, rounds = info[1], active = info[4:4 + S], n_rule_zero = info[3], n_cond_traits = info[2])
+end
+# ... on DEVICE buffers (0-based markers, -1 for none, as the C ABI): dloci S x m, dlod / dargmax / dh2 (S + 1) x m, dnloci m,
+# dsinfo 8 or C_NULL.  Returns when the results are complete.
+function bulkscan_stepwise_dev!(dY::Ptr{Float64}, n::Int64, m::Int64, dG::Ptr{Float64}, p::Int64, dK::Ptr{Float64}, max_loci::Int64,
+                                threshold::Float64, dloci::Ptr{Int64}, dlod::Ptr{Float64}, dargmax::Ptr{Int64}, dh2::Ptr{Float64},
+                                dnloci::Ptr{Int64}; dsinfo::Ptr{Int64} = Ptr{Int64}(C_NULL), method::String = "null-grid",
+                                h2_grid::Array{Float64, 1} = collect(0.0:0.1:0.9), dCovar::Ptr{Float64} = Ptr{Float64}(C_NULL),
+                                ncov::Int64 = 0, dweights::Ptr{Float64} = Ptr{Float64}(C_NULL), addIntercept::Bool = true,
+                                prior_variance::Float64 = 1.0, prior_sample_size::Float64 = 0.0, reml::Bool = false,
+                                optim_interval::Int64 = 1, decomp_scheme::String = "eigen")
+    stepwise_checks(method, n, max_loci, threshold, ncov == 0 ? 1 : ncov + (addIntercept ? 1 : 0))
+    meth = method == "null-exact" ? NULL_EXACT : NULL_GRID
+    o = BlmmOpts(meth, reml, ncov == 0 ? true : addIntercept, decomp(decomp_scheme), optim_interval, 0, prior_variance, prior_sample_size)
+    st = BlmmStatus()
+    GC.@preserve h2_grid begin
+        check(ccall((:blmm_bulkscan_stepwise_dev, libblmm), Cint,
+                    (Ptr{Cvoid}, Ref{BlmmOpts}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64,
+                     Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Float64, Ptr{Int64}, Ptr{Float64}, Ptr{Int64},
+                     Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ref{BlmmStatus}),
+                    context(), o, dY, n, m, dG, p, dCovar, ncov, dK, dweights, h2_grid, length(h2_grid), max_loci, threshold,
+                    dloci, dlod, dargmax, dh2, dnloci, dsinfo, st))
+    end
+    raise_status(st)
+    return nothing
 end
 
 # ---- effects at chosen tests (blmm_bulkscan_effects): coefficients and standard errors of the locus columns in the weighted

@@ -33,7 +33,8 @@ extern "C" {
                             blmm_bulkscan_reduced_async + BLMM_RINFO_* (stream-ordered, flagged traits re-scanned on the device);
                             205 (0.2.2): blmm_status.n_h2_boundary / n_h2_multimodal / n_illcond_rescan (appended), BLMM_FLAG_H2_AUDIT;
                             201: lowrank_shared, readers, blmm_scan_alt; 200: lowrank_fallback, BLMM_STREAM_NULL, multi-GPU;
-                            added since without a new number: blmm_bulkscan_multidf_perms[_dev], blmm_bulkscan_multidf_reduced[_dev] */
+                            added since without a new number: blmm_bulkscan_multidf_perms[_dev], blmm_bulkscan_multidf_reduced[_dev],
+                            blmm_bulkscan_stepwise[_dev] + BLMM_STEP_INFO_LEN, tuning key "cond_red_chunk" */
 
 typedef struct blmm_ctx blmm_ctx;
 
@@ -162,6 +163,9 @@ int blmm_synchronize(blmm_ctx* ctx);
  *                            not depend on it
  *   "mdf_red_chunk"   0      blmm_bulkscan_multidf_reduced: flagged traits re-scanned per chunk of the scratch (0: a 64 MiB scratch);
  *                            results do not depend on it
+ *   "cond_red_chunk"  0      blmm_bulkscan_stepwise: flagged traits re-scanned per chunk of the scratch (0: a 64 MiB scratch); results
+ *                            do not depend on it.  A round enqueues ceil(active traits / chunk) launch pairs whatever the guard
+ *                            lists (those beyond its list return at once), so small values are for tests only
  *   "defaults"               (set only) every key back to its default
  * Every setting gives results within the library's stated tolerances; they exist for tests and for A/B measurements. */
 int blmm_set_tuning(blmm_ctx* ctx, const char* key, double value);
@@ -674,6 +678,44 @@ int blmm_bulkscan_cond_dev(blmm_ctx* ctx, const blmm_opts* opts, const double* d
                            const double* dCovar, int64_t ncov, const double* dK, const double* dweights, const double* h2_grid,
                            int64_t ngrid, const int64_t* dcond, int64_t s, double* dL_out, int64_t ldL, double* dh2_out,
                            int64_t* dcinfo_out, blmm_status* status);
+
+/* ---- forward selection: up to max_loci loci per trait, one after the other, without the LOD matrix -------------------------------
+ * Inputs as blmm_bulkscan_cond without the table: the call builds it.  S = max_loci; rounds t = 0 .. S.  A_0 is every trait, T_0 the
+ * S x m table of -1 in blmm_bulkscan_cond's layout.  Round t is, for the traits of A_t and bit for bit,
+ *   R_t = blmm_bulkscan_cond(Y, G, K, Covar, weights, opts, h2_grid; cond = T_t, s = S),
+ *   (lod[t, j], argmax[t, j]) = blmm_lod_colmax of column j of R_t's L (the lowest marker wins a tie, NaN is never the maximum, a
+ *   column without a comparable entry gives -inf / -1),  h2[t, j] = R_t's h2[j].
+ * So round 0 is blmm_bulkscan_cond without loci (not blmm_bulkscan: null-exact h2 agrees to the search's tolerance only).
+ * Trait j is in A_{t+1} iff t < S and lod[t, j] > threshold (strictly: -inf fails), and then T_{t+1}[j, t] = argmax[t, j].  The call
+ * ends after the first round that leaves A empty, or after round S.  Upload, eigen phase and rotations happen once, no p x m
+ * buffer is allocated, and from round 1 on only the active traits are scanned; a trait's results do not depend on which other
+ * traits are active.
+ *   loci_out    S x m, loci_out[j S + a]: the final table (-1 beyond the trait's loci); can go straight to blmm_bulkscan_cond
+ *   lod_out, argmax_out, h2_out   (S + 1) x m, x[j (S + 1) + t]; NaN / -1 / NaN for the rounds in which j was not active
+ *   nloci_out   m: the loci selected for trait j
+ *   sinfo_out   int64[BLMM_STEP_INFO_LEN], may be NULL: [0] rounds run, [1] traits with at least one locus, [2] entries the rank
+ *               rule set to +0.0, summed over the rounds and their active traits, [3 + t] |A_t| for t = 0 .. 4 (0: round not run)
+ *   status      the eigen phase's fields once, the others summed over the rounds as blmm_bulkscan_loco sums its chromosomes;
+ *               n_nan_lod (the NaNs in the columns A_t of R_t's L, summed over t) and n_illcond_rescan count ACTIVE traits only;
+ *               n_zero_norm is round 0's, as blmm_bulkscan_cond reports it
+ * Refused before anything is uploaded, in this order in both forms: max_loci < 1 (BLMM_ERR_INVALID); max_loci > BLMM_COND_MAX_LOCI
+ * or c + max_loci > BLMM_MULTIDF_MAX_COVARIATES (BLMM_ERR_UNSUPPORTED); a threshold that is NaN or < 0 (BLMM_ERR_INVALID: below 0 a
+ * conditioning marker's own +0.0 could be selected again; +inf is allowed and gives one round); then blmm_bulkscan_cond's refusals
+ * (alt-grid, an unknown method, n > 2048, c + max_loci >= n); a NULL buffer other than sinfo_out / status.  A pending
+ * blmm_set_log10p_output request is refused with BLMM_ERR_INVALID and consumed (the call writes no matrix), and blmm_last_dims
+ * reports no matrix afterwards.
+ * The _dev form: device Y / G / Covar / weights and outputs, h2_grid on the host; enqueued on the context's stream.  It waits for
+ * the stream once per round but the last (the next round's launches are sized by |A_{t+1}|) and once more when a status is asked
+ * for; without a status the results are valid after blmm_synchronize. */
+#define BLMM_STEP_INFO_LEN 8
+int blmm_bulkscan_stepwise(blmm_ctx* ctx, const blmm_opts* opts, const double* Y, int64_t n, int64_t m, const double* G, int64_t p,
+                           const double* Covar, int64_t ncov, const double* K, const double* weights, const double* h2_grid,
+                           int64_t ngrid, int64_t max_loci, double threshold, int64_t* loci_out, double* lod_out, int64_t* argmax_out,
+                           double* h2_out, int64_t* nloci_out, int64_t* sinfo_out, blmm_status* status);
+int blmm_bulkscan_stepwise_dev(blmm_ctx* ctx, const blmm_opts* opts, const double* dY, int64_t n, int64_t m, const double* dG, int64_t p,
+                               const double* dCovar, int64_t ncov, const double* dK, const double* dweights, const double* h2_grid,
+                               int64_t ngrid, int64_t max_loci, double threshold, int64_t* dloci_out, double* dlod_out,
+                               int64_t* dargmax_out, double* dh2_out, int64_t* dnloci_out, int64_t* dsinfo_out, blmm_status* status);
 
 /* ---- effects at chosen tests: coefficients and standard errors where a scan found something ------------------------------------
  * Takes what blmm_bulkscan_multidf takes (opts: null-grid or null-exact, reml, the prior, add_intercept, optim_interval,
