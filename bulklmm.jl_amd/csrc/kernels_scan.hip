@@ -591,6 +591,23 @@ __device__ unsigned long long g_lr_diag[24];   // per class {sum of workgroup cy
 #ifdef LR_PHASE
 // per class (0: shared-weights tiles, 1: rank-R tiles) sums over the waves of {K loops, barrier wait, epilogue} cycles and the count
 __device__ unsigned long long g_lr_phase[8];
+// k_scan_lr3: sums over the waves of {head, phase-2 loops, conversions, phase-1 loop, epilogue} cycles and the count
+__device__ unsigned long long g_lr3_phase[8];
+#define LR3_MARK(i)                                              \
+  {                                                              \
+    __builtin_amdgcn_sched_barrier(0);                           \
+    const unsigned long long t_ = __builtin_amdgcn_s_memtime();  \
+    ph_c[i] += t_ - ph_t;                                        \
+    ph_t = t_;                                                   \
+    __builtin_amdgcn_sched_barrier(0);                           \
+  }
+#else
+#define LR3_MARK(i)
+#endif
+#ifdef LR_NOLOAD
+// k_scan_lr3's register-fed operands: values whose r^2 stays small, so that every LOD is inside the table's range as in a real run
+// (out-of-range outputs take the rare branch of the epilogue, which is far slower)
+__device__ __forceinline__ double lr3_regfed(double v) { asm volatile("" : "+v"(v)); return v; }
 #endif
 template <int C, int MB, int NB, bool PV = false, bool RED = false>
 __global__ void __launch_bounds__(256, 2) k_scan_lr(LrArgs la, int ntile_i, int64_t nwg) {
@@ -908,11 +925,19 @@ __global__ void __launch_bounds__(256, 2) k_scan_lr(LrArgs la, int ntile_i, int6
 // accumulates Sxx and s for four 16 x 16 blocks (64 VGPRs), converts them to 1 / (Sxx - u^2) (32 VGPRs) and lets them go; then
 // phase 1 accumulates num (64 VGPRs) beside the 64 of the reciprocals -- 128 accumulator registers at the peak where k_scan_lr
 // holds 192 -- and the epilogue is r^2 = num^2 * that reciprocal.  Same arithmetic per output, same bits.
+// There is no room for a second fragment set (161 of 168 VGPRs before any): both K loops hold ONE set and request each operand
+// again right behind the last MFMA that reads it (below).
+// Diagnostic builds (make EXTRA=-D...): LR_NOLOAD feeds the MFMAs from registers -- against the normal build, the operand latency
+// the loops leave exposed --, LR_PHASE sums per wave the cycles of head / phase-2 loops / conversions / phase-1 loop / epilogue.
 // ------------------------------------------------------------------------------------------------
 template <int C, bool PV, bool RED = false>
 __global__ void __launch_bounds__(256, 3) k_scan_lr3(LrArgs la, int ntile_i, int64_t nwg) {
   static_assert(!(RED && PV), "reduce-in-epilogue: no p-value output");
   const ScanArgs& a = la.s;
+#ifdef LR_PHASE
+  unsigned long long ph_c[5] = {0, 0, 0, 0, 0};
+  unsigned long long ph_t = __builtin_amdgcn_s_memtime();
+#endif
   constexpr int MB = 2, NB = 4, TW = 64;
   constexpr int NL = C * (C + 1) / 2;
   // phase 2 goes chunk by chunk: (trait block mb) x (NBC marker blocks) with 1 + C accumulators per block -- four marker blocks for
@@ -961,14 +986,34 @@ __global__ void __launch_bounds__(256, 3) k_scan_lr3(LrArgs la, int ntile_i, int
   const uint32_t voffB = (uint32_t)(((int64_t)kk * a.ldx + wi * (16 * NB)) * 8) + mvoff<NB>(r);
   const int64_t sa = 4 * a.ldp, sb = 4 * a.ldx;
   const int KR = la.rk[4 * sgi + 1];
-  // first fragments of phase 2 on their way, then the staged tables to LDS
-  double c0[MB], d0[1 + C][NBC];
-  auto load2 = [&](double (&A)[MB], double (&B)[1 + C][NBC], int step, int nb0) {
-    bufload<MB>(A, make_srd(PC + (int64_t)step * sa), voffA);
-#pragma unroll
-    for (int q = 0; q <= C; ++q) bufload<NBC>(B[q], make_srd(PT + q * la.tstride + (int64_t)step * sb), voffB + (uint32_t)(8 * nb0));
+  // Operand fetches, one register group each, so that a group is requested again right behind the last MFMA that reads it: a wave
+  // issues in order and one of these MFMAs holds the pipe for 64 cycles -- loads written behind a whole step's MFMAs leave ~500
+  // cycles late and the next step waits for their round trip.  Phase 2: the trait value of row block mb (8 bytes, requested at the
+  // top of the step before into a second register) and the NBC marker values of product q.
+  double cA, cB, d0[1 + C][NBC];
+  auto ldc = [&](double& A, int step, int mb) {
+#ifdef LR_NOLOAD    // diagnostic: the matrix pipe alone (operands from registers)
+    A = lr3_regfed(1.0);
+    return;
+#endif
+    double t[1];
+    bufload<1>(t, make_srd(PC + (int64_t)step * sa), voffA + (uint32_t)(8 * mb));
+    A = t[0];
   };
-  if (KR > 0) load2(c0, d0, 0, 0);
+  auto ldd = [&](double (&B)[NBC], int q, int step, int nb0) {
+#ifdef LR_NOLOAD
+#pragma unroll
+    for (int u = 0; u < NBC; ++u) B[u] = lr3_regfed(q == 0 ? 1.0 : 1e-3 * (1 + ((lane + u + step + nb0) & 7)));
+    return;
+#endif
+    bufload<NBC>(B, make_srd(PT + q * la.tstride + (int64_t)step * sb), voffB + (uint32_t)(8 * nb0));
+  };
+  // first fragments of phase 2 on their way, then the staged tables to LDS
+  if (KR > 0) {
+    ldc(cA, 0, 0);
+#pragma unroll
+    for (int q = 0; q <= C; ++q) ldd(d0[q], q, 0, 0);
+  }
   __builtin_amdgcn_sched_barrier(0);
   lod_stage_store<256>(lst, s_lod, a.lodc[0]);
 #pragma unroll
@@ -982,6 +1027,7 @@ __global__ void __launch_bounds__(256, 3) k_scan_lr3(LrArgs la, int ntile_i, int
     for (int i = threadIdx.x; i < BLMM_PV_TABLE_N * (BLMM_PV_STRIDE / 2); i += 256) s_pv[i] = g[i];
   }
   __syncthreads();
+  LR3_MARK(0)
   d4 den[MB][NB];
 #pragma unroll
   for (int mb = 0; mb < MB; ++mb)
@@ -992,19 +1038,29 @@ __global__ void __launch_bounds__(256, 3) k_scan_lr3(LrArgs la, int ntile_i, int
       for (int q = 0; q <= C; ++q)
 #pragma unroll
         for (int nb = 0; nb < NBC; ++nb) sm[q][nb] = (d4){0, 0, 0, 0};
-      // one fragment set: the next step's loads go out right behind the MFMAs that read this step's (the matrix pipe drains them
-      // meanwhile, and two other waves share the SIMD); behind a chunk's last step, the first set of the next chunk
-      for (int ks = 0; ks < KR; ++ks) {
+      // one K step, q-major: the NBC MFMAs of product q, then the following set's d0[q] into the same registers.  The following set
+      // (nstep, nnb0, nmb) is the chunk's next step or, behind its last step, the first set of the next chunk (requested ahead of
+      // the conversion).  Each accumulator still receives its K steps in order.
+      auto step2 = [&](bool more, int nstep, int nnb0, int nmb) {
+        __builtin_amdgcn_sched_barrier(0);
+        if (more) ldc(cB, nstep, nmb);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int nb = 0; nb < NBC; ++nb)
+        for (int q = 0; q <= C; ++q) {
 #pragma unroll
-          for (int q = 0; q <= C; ++q) sm[q][nb] = __builtin_amdgcn_mfma_f64_16x16x4f64(c0[mb], d0[q][nb], sm[q][nb], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (ks + 1 < KR) load2(c0, d0, ks + 1, nb0);
-        else if (nb0 + NBC < NB) load2(c0, d0, 0, nb0 + NBC);
-        else if (mb + 1 < MB) load2(c0, d0, 0, 0);
+          for (int nb = 0; nb < NBC; ++nb) sm[q][nb] = __builtin_amdgcn_mfma_f64_16x16x4f64(cA, d0[q][nb], sm[q][nb], 0, 0, 0);
+          __builtin_amdgcn_sched_barrier(0);
+          if (more) ldd(d0[q], q, nstep, nnb0);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      };
+      const bool samerow = nb0 + NBC < NB, nxc = samerow || mb + 1 < MB;   // nxc: a chunk follows
+      for (int ks = 0; ks + 1 < KR; ++ks) {
+        step2(true, ks + 1, nb0, mb);
+        cA = cB;
       }
+      if (KR > 0) step2(nxc, 0, samerow ? nb0 + NBC : 0, samerow ? mb : mb + 1);
+      LR3_MARK(1)
 #pragma unroll
       for (int reg = 0; reg < 4; ++reg) {
         double li[NL];
@@ -1027,34 +1083,65 @@ __global__ void __launch_bounds__(256, 3) k_scan_lr3(LrArgs la, int ntile_i, int
       // the registers of Sxx and s alive through phase 1 (142 spilled dwords)
 #pragma unroll
       for (int nb = 0; nb < NBC; ++nb) asm volatile("" : "+v"(den[mb][nb0 + nb]));
+      if (nxc) {   // behind the conversion: by now the value has arrived
+        __builtin_amdgcn_sched_barrier(0);
+        cA = cB;
+      }
+      LR3_MARK(2)
     }
-  // ---- phase 1: num over n, one K step per fragment set
+  // ---- phase 1: num over n.  The trait pair (16 bytes) is requested at the top of the step before into a second register pair, the
+  //      two 16-byte halves of the marker fragment each behind the four MFMAs that read them, into the same registers
   d4 num[MB][NB];
 #pragma unroll
   for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) num[mb][nb] = (d4){0, 0, 0, 0};
   {
-    double a0[MB], b0[NB];
-    auto load1 = [&](double (&A)[MB], double (&B)[NB], int step) {
+    static_assert(NB == 4, "phase 1: two 16-byte halves of the marker fragment");
+    double aA[MB], aB[MB], b0[2][2];
+    auto lda = [&](double (&A)[MB], int step) {
+#ifdef LR_NOLOAD
+#pragma unroll
+      for (int u = 0; u < MB; ++u) A[u] = lr3_regfed(0.05);
+      return;
+#endif
       bufload<MB>(A, make_srd(PA + (int64_t)step * sa), voffA);
-      bufload_m<NB>(B, make_srd(PB + (int64_t)step * sb), voffB);
     };
-    auto mf1 = [&](const double (&A)[MB], const double (&B)[NB]) {
+    auto ldb = [&](double (&B)[2], int step, int h) {
+#ifdef LR_NOLOAD
 #pragma unroll
-      for (int mb = 0; mb < MB; ++mb)
+      for (int u = 0; u < 2; ++u) B[u] = lr3_regfed(0.03 * ((lane + u + 2 * h + step) & 15));
+      return;
+#endif
+      bufload<2>(B, make_srd(PB + (int64_t)step * sb), voffB + (uint32_t)(16 * h));
+    };
+    auto step1 = [&](bool more, int nstep) {
+      __builtin_amdgcn_sched_barrier(0);
+      if (more) lda(aB, nstep);
+      __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb) num[mb][nb] = __builtin_amdgcn_mfma_f64_16x16x4f64(A[mb], B[nb], num[mb][nb], 0, 0, 0);
+      for (int h = 0; h < 2; ++h) {
+#pragma unroll
+        for (int nb = 2 * h; nb < 2 * h + 2; ++nb)
+#pragma unroll
+          for (int mb = 0; mb < MB; ++mb) num[mb][nb] = __builtin_amdgcn_mfma_f64_16x16x4f64(aA[mb], b0[h][nb - 2 * h], num[mb][nb], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (more) ldb(b0[h], nstep, h);
+        __builtin_amdgcn_sched_barrier(0);
+      }
     };
     const int K = a.ks;
-    load1(a0, b0, 0);
-    for (int s1 = 0; s1 < K; ++s1) {
-      __builtin_amdgcn_sched_barrier(0);
-      mf1(a0, b0);
-      __builtin_amdgcn_sched_barrier(0);
-      if (s1 + 1 < K) load1(a0, b0, s1 + 1);
+    lda(aA, 0);
+    ldb(b0[0], 0, 0);
+    ldb(b0[1], 0, 1);
+    for (int s1 = 0; s1 + 1 < K; ++s1) {
+      step1(true, s1 + 1);
+#pragma unroll
+      for (int mb = 0; mb < MB; ++mb) aA[mb] = aB[mb];
     }
+    if (K > 0) step1(false, 0);
   }
+  LR3_MARK(3)
   // ---- epilogue
   const double scale = a.lodc[0];
   const LodPoly5 lp = lod_poly5_of(a.lodc);
@@ -1090,7 +1177,36 @@ __global__ void __launch_bounds__(256, 3) k_scan_lr3(LrArgs la, int ntile_i, int
       }
     }
   if (nnan) atomicAdd((unsigned long long*)&a.stat[ST_NAN_LOD], (unsigned long long)nnan);
+#ifdef LR_PHASE
+  LR3_MARK(4)
+  if (lane == 0) {
+#pragma unroll
+    for (int i = 0; i < 5; ++i) atomicAdd(&g_lr3_phase[i], ph_c[i]);
+    atomicAdd(&g_lr3_phase[5], 1ull);
+  }
+#endif
 }
+
+#ifdef LR_PHASE
+static void lr3_phase_reset(blmm_ctx* ctx) {
+  unsigned long long z[8] = {0};
+  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_lr3_phase), z, sizeof(z));
+  (void)hipStreamSynchronize(ctx->stream);
+}
+static void lr3_phase_print(blmm_ctx* ctx) {
+  unsigned long long z[8];
+  (void)hipStreamSynchronize(ctx->stream);
+  (void)hipMemcpyFromSymbol(z, HIP_SYMBOL(g_lr3_phase), sizeof(z));
+  if (z[5])
+    fprintf(stderr, "lr3 phase: %llu waves, avg cycles head %.0f | phase-2 loops %.0f | conversions %.0f | phase-1 loop %.0f | epilogue %.0f\n", z[5],
+            (double)z[0] / z[5], (double)z[1] / z[5], (double)z[2] / z[5], (double)z[3] / z[5], (double)z[4] / z[5]);
+}
+#endif
+
+// k_scan_lr3 serves n <= LR3_NMAX (make EXTRA=-DLR3_NMAX=...: re-measuring the gate with BLMM_LR3=0 / 1)
+#ifndef LR3_NMAX
+#define LR3_NMAX 128
+#endif
 
 template <int C, int MB>
 static int launch_scan_lr_t(blmm_ctx* ctx, const LrArgs& la) {
@@ -1110,19 +1226,20 @@ static int launch_scan_lr_t(blmm_ctx* ctx, const LrArgs& la) {
   unsigned long long zp[8] = {0};
   (void)hipMemcpyToSymbol(HIP_SYMBOL(g_lr_phase), zp, sizeof(zp));
   (void)hipStreamSynchronize(ctx->stream);
+  lr3_phase_reset(ctx);
 #endif
   // k_scan_lr3 (three waves per SIMD) is the default for c = 1 and n <= 128; BLMM_LR3=0: k_scan_lr (A/B testing).
   // One box, four alternating rounds: scan 1.164-1.183 against 1.206-1.240 ms, step 1.636-1.654 against 1.674-1.714.
   static const bool lr3 = !(dev_env("BLMM_LR3") && dev_env("BLMM_LR3")[0] == '0');
-  if (a.red.pmax && lr3 && C == 1 && MB == 2 && la.skip_shared && a.n <= 128)
+  if (a.red.pmax && lr3 && C == 1 && MB == 2 && la.skip_shared && a.n <= LR3_NMAX)
     hipLaunchKernelGGL((k_scan_lr3<1, false, true>), dim3((unsigned)nwg), dim3(256), 0, ctx->stream, la, (int)ntile_i, nwg);
   else if (a.red.pmax)
     hipLaunchKernelGGL((k_scan_lr<C, MB, NB, false, true>), dim3((unsigned)nwg), dim3(256), 0, ctx->stream, la, (int)ntile_i, nwg);
-  else if (a.Pv && lr3 && C == 1 && MB == 2 && la.skip_shared && a.n <= 128)
+  else if (a.Pv && lr3 && C == 1 && MB == 2 && la.skip_shared && a.n <= LR3_NMAX)
     hipLaunchKernelGGL((k_scan_lr3<1, true>), dim3((unsigned)nwg), dim3(256), 0, ctx->stream, la, (int)ntile_i, nwg);
   else if (a.Pv)
     hipLaunchKernelGGL((k_scan_lr<C, MB, NB, true>), dim3((unsigned)nwg), dim3(256), 0, ctx->stream, la, (int)ntile_i, nwg);
-  else if (lr3 && C == 1 && MB == 2 && la.skip_shared && a.n <= 128)   // beyond: phase 1 is long and its single fragment set shows (n = 200: +1.7 %, n = 500: +4 %; n = 124: -1 %, n = 79: -3.8 % of the scan)
+  else if (lr3 && C == 1 && MB == 2 && la.skip_shared && a.n <= LR3_NMAX)   // beyond: phase 1 is long and k_scan_lr's two fragment sets win (scan against k_scan_lr, with the operands reloaded behind their last MFMA: n = 124: -3.9 %, n = 200: +-0 (-0.7 % / +0.1 %), n = 500: +5 .. +7 %; profiles/lr3_reload_ab.json)
     hipLaunchKernelGGL((k_scan_lr3<1, false>), dim3((unsigned)nwg), dim3(256), 0, ctx->stream, la, (int)ntile_i, nwg);
   else
     hipLaunchKernelGGL((k_scan_lr<C, MB, NB>), dim3((unsigned)nwg), dim3(256), 0, ctx->stream, la, (int)ntile_i, nwg);
@@ -1133,6 +1250,7 @@ static int launch_scan_lr_t(blmm_ctx* ctx, const LrArgs& la) {
     if (zp[4 * cls + 3])
       fprintf(stderr, "lr phase: %s tiles: %llu waves, avg cycles K loops %.0f | barrier wait %.0f | epilogue %.0f\n", cls ? "rank-R" : "shared",
               zp[4 * cls + 3], (double)zp[4 * cls] / zp[4 * cls + 3], (double)zp[4 * cls + 1] / zp[4 * cls + 3], (double)zp[4 * cls + 2] / zp[4 * cls + 3]);
+  lr3_phase_print(ctx);
 #endif
 #ifdef LR_DIAG
   (void)hipStreamSynchronize(ctx->stream);
@@ -1153,7 +1271,7 @@ static int launch_scan_lr_t(blmm_ctx* ctx, const LrArgs& la) {
 template <int C>
 static bool lr3_covariates(blmm_ctx*, const LrArgs& la) {
   static const bool lr3 = !(dev_env("BLMM_LR3") && dev_env("BLMM_LR3")[0] == '0');
-  return lr3 && la.skip_shared && la.s.n <= 128;
+  return lr3 && la.skip_shared && la.s.n <= LR3_NMAX;
 }
 template <int C>
 static int launch_scan_lr3_c(blmm_ctx* ctx, const LrArgs& la) {
@@ -1162,9 +1280,15 @@ static int launch_scan_lr3_c(blmm_ctx* ctx, const LrArgs& la) {
   if (ntile_t * ntile_i <= 0) return BLMM_OK;
   const int64_t nwg = (ntile_t * ntile_i + 16 + 7) / 8 * 8;
   if (nwg > 0x7fffffffLL) return fail(ctx, BLMM_ERR_INVALID, "problem too large for one launch");
+#ifdef LR_PHASE
+  lr3_phase_reset(ctx);
+#endif
   if (a.red.pmax) hipLaunchKernelGGL((k_scan_lr3<C, false, true>), dim3((unsigned)nwg), dim3(256), 0, ctx->stream, la, (int)ntile_i, nwg);
   else if (a.Pv) hipLaunchKernelGGL((k_scan_lr3<C, true>), dim3((unsigned)nwg), dim3(256), 0, ctx->stream, la, (int)ntile_i, nwg);
   else hipLaunchKernelGGL((k_scan_lr3<C, false>), dim3((unsigned)nwg), dim3(256), 0, ctx->stream, la, (int)ntile_i, nwg);
+#ifdef LR_PHASE
+  lr3_phase_print(ctx);
+#endif
   KCHECK();
   return BLMM_OK;
 }
