@@ -184,12 +184,19 @@ int check_method(blmm_ctx* ctx, const blmm_opts* o) {
   return BLMM_OK;
 }
 
-int reset_stat(blmm_ctx* ctx, int64_t** stat) {
+// the host side of a fresh status block; the device words are zeroed by reset_stat's fill or by the call's first kernel
+// (prepare_eigen: k_eigf_reduce<true>)
+int reset_stat_host(blmm_ctx* ctx, int64_t** stat) {
   int rc = ensure(ctx, ctx->stat, sizeof(int64_t) * NSTAT);
   if (rc) return rc;
   *stat = ptr<int64_t>(ctx->stat);
   ctx->audit_ran = false;
   ctx->brent_cnt_used = false;
+  return BLMM_OK;
+}
+int reset_stat(blmm_ctx* ctx, int64_t** stat) {
+  int rc = reset_stat_host(ctx, stat);
+  if (rc) return rc;
   BLMM_HIP(hipMemsetAsync(*stat, 0, sizeof(int64_t) * NSTAT, ctx->stream));
   return BLMM_OK;
 }
@@ -313,9 +320,6 @@ int prepare_eigen(blmm_ctx* ctx, const blmm_opts* o, int64_t n, const double* dC
   if ((rc = ensure(ctx, ctx->Ks, sizeof(double) * n * n))) return rc;
   if ((rc = ensure(ctx, ctx->V, sizeof(double) * (n * n + 4 * n + 16)))) return rc;
   if ((rc = ensure(ctx, ctx->lraw, sizeof(double) * n))) return rc;
-  if ((rc = reset_stat(ctx, &P.stat))) return rc;
-  tm.mark();
-  if ((rc = launch_design(ctx, dK, nc.d, (int)nc.ncov, nc.add_int, dweights, (int)n, ptr<double>(ctx->Ks), ptr<double>(ctx->Zs)))) return rc;
   const double* evec = ptr<double>(ctx->V);
   // n <= 124: LDS Jacobi.  Beyond: the own tridiagonalisation + divide-and-conquer solver (kernels_eig.hip) up to n = 2048 (its
   // reduction keeps the matrix in LDS up to ~1450 and in L2-resident global memory beyond).  No vendor library: rocSOLVER's first
@@ -329,19 +333,32 @@ int prepare_eigen(blmm_ctx* ctx, const blmm_opts* o, int64_t n, const double* dC
   P.big = big;
   bool done = false, post_done = false;
   const bool want_dc = eig_env ? std::strcmp(eig_env, "dc") == 0 : big;
+  // n <= 124: the fast path first (tridiagonalisation, Sturm multi-section, twisted factorisation; kernels_eig.hip: k_eigf_*).
+  // It checks its own result on the device; the Jacobi behind it is a no-op when the checks passed and the whole solver when
+  // they did not (numerically repeated eigenvalues).  BLMM_EIGEN=jacobi: the Jacobi alone (A/B timing, tests).
+  const bool want_fast = !(eig_env && std::strcmp(eig_env, "jacobi") == 0) && n >= 3 && n <= eig_fast_max_n();
+  // Where the fast path is the call's first solver, its first kernel -- one workgroup that starts by loading the matrix -- builds
+  // Ks and Zs itself and zeroes the status block: no fill and no design launch in front of it (two dependent steps of a chain on
+  // which one workgroup runs at a time).  Every other route keeps both.
+  const DesignFold fold{dK, nc.d, dweights, ptr<double>(ctx->Ks), ptr<double>(ctx->Zs), (int)nc.ncov, nc.add_int};
+  const bool folded = want_fast && !want_dc;
+  auto design = [&]() { return launch_design(ctx, dK, nc.d, (int)nc.ncov, nc.add_int, dweights, (int)n, fold.Ks, fold.Zs); };
+  if ((rc = folded ? reset_stat_host(ctx, &P.stat) : reset_stat(ctx, &P.stat))) return rc;
+  tm.mark();
+  if (!folded && (rc = design())) return rc;
   if (!done && want_dc && n >= 3) {
     rc = launch_eig_dc(ctx, ptr<double>(ctx->Ks), (int)n, ptr<double>(ctx->lraw), ptr<double>(ctx->V), P.stat);
     if (rc == BLMM_OK) { done = true; P.big = true; }
     else if (rc != BLMM_ERR_UNSUPPORTED) return rc;
   }
   if (!done) {
-    // n <= 124: the fast path first (tridiagonalisation, Sturm multi-section, twisted factorisation; kernels_eig.hip: k_eigf_*).
-    // It checks its own result on the device; the Jacobi behind it is a no-op when the checks passed and the whole solver when
-    // they did not (numerically repeated eigenvalues).  BLMM_EIGEN=jacobi: the Jacobi alone (A/B timing, tests).
-    const bool want_fast = !(eig_env && std::strcmp(eig_env, "jacobi") == 0) && n >= 3 && n <= eig_fast_max_n();
     if (want_fast) {
-      rc = launch_eig_fast(ctx, ptr<double>(ctx->Ks), (int)n, ptr<double>(ctx->lraw), ptr<double>(ctx->V), P.stat);
+      rc = launch_eig_fast(ctx, ptr<double>(ctx->Ks), (int)n, ptr<double>(ctx->lraw), ptr<double>(ctx->V), P.stat, folded ? &fold : nullptr);
       if (rc != BLMM_OK && rc != BLMM_ERR_UNSUPPORTED) return rc;
+      if (rc == BLMM_ERR_UNSUPPORTED && folded) {    // (it launched nothing: the Jacobi alone, behind the fill and the design)
+        BLMM_HIP(hipMemsetAsync(P.stat, 0, sizeof(int64_t) * NSTAT, ctx->stream));
+        if ((rc = design())) return rc;
+      }
     }
     // (the post-eigen work rides in the tail of this launch where its LDS fits: one dependent-launch boundary less)
     if ((rc = launch_jacobi_post(ctx, ptr<double>(ctx->Ks), ptr<double>(ctx->V), (int)n, ptr<double>(ctx->lraw), P.stat, ptr<double>(ctx->Zs),

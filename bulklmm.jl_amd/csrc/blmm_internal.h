@@ -259,7 +259,10 @@ int launch_jacobi_post(blmm_ctx* ctx, double* A, double* V, int n, double* lraw,
 // kernels_eig.hip: tridiagonalisation + divide and conquer for n beyond the LDS Jacobi; A is not modified
 int launch_eig_dc(blmm_ctx* ctx, const double* A, int n, double* lraw, double* evec, int64_t* stat);
 int eig_dc_max_n(const blmm_ctx* ctx);
-int launch_eig_fast(blmm_ctx* ctx, const double* A, int n, double* lraw, double* evec, int64_t* stat);
+// fold != nullptr: the first kernel of the fast path does launch_design's work on its way in (A = fold->Ks is WRITTEN, from fold->K and
+// the weights, and so is fold->Zs) and zeroes the NSTAT words of stat: the caller then queues neither the design nor the memset.
+struct DesignFold { const double* K; const double* Covar; const double* wd; double* Ks; double* Zs; int ncov, add_intercept; };
+int launch_eig_fast(blmm_ctx* ctx, const double* A, int n, double* lraw, double* evec, int64_t* stat, const DesignFold* fold = nullptr);
 // ... for nb matrices in one set of launches (batch on blockIdx.y): matrix b at A + b sA -> lraw + b sL, evec + b sE, stat + b sS
 int launch_eig_fast_batch(blmm_ctx* ctx, const double* A, int64_t sA, int n, int nb, double* lraw, int64_t sL, double* evec, int64_t sE,
                           int64_t* stat, int64_t sS);

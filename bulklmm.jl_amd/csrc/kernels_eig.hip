@@ -1221,10 +1221,40 @@ struct SmallWs {   // LDS carve-up of the reduction (doubles); M2 optional (zero
 //         products the next correction needs (one wsum4 with |x|^2); v_(k-1), w_(k-1), v_k, tau live in its registers.
 //         waves 1-15 MEANWHILE: the rank-2 update of step k-1 on rows and columns >= k+2 (the pair is read from the parity
 //         buffer wave 0 wrote a step ago; wave 0 writes this step's pair to the other one): off the critical path.
-__device__ void small_sytrd(const SmallWs& w, const double* __restrict__ A, int n, double* __restrict__ Vg, double* s_sc) {
+//
+// FOLD (the single-matrix call, blmm_api.hip: prepare_eigen): the matrix is not there yet -- the load builds it, k_design's statements
+// in k_design's order (Ks = wd wd' .* K, bit for bit), and writes it to A = df.Ks for the Jacobi behind the fast path; the threads
+// from the top of the workgroup, which have one element less to load, write Zs, and wave 0 -- the wave that sets ST_EIG_FAST at the
+// end of the kernel, so the two stores to that word stay in order -- zeroes the status block: nothing in front of this kernel in
+// a call may touch it.
+template <bool FOLD>
+__device__ void small_sytrd(const SmallWs& w, const double* __restrict__ A, int n, double* __restrict__ Vg, double* s_sc,
+                            const DesignFold& df, int64_t* stat) {
   const int t = threadIdx.x, NT = blockDim.x, lane = t & 63, wave = t >> 6;
   double amax = 0.0;
-  for (int e0 = t; e0 < n * n; e0 += NT) { const double a = A[e0]; w.M1[e0] = a; if (w.M2) w.M2[e0] = 0.0; amax = fmax(amax, fabs(a)); }
+  for (int e0 = t; e0 < n * n; e0 += NT) {
+    double a;
+    if (FOLD) {
+      const int i = e0 % n, j = e0 / n;
+      double v = df.K[e0];
+      if (df.wd) v *= df.wd[i] * df.wd[j];
+      df.Ks[e0] = v;
+      a = v;
+    } else a = A[e0];
+    w.M1[e0] = a; if (w.M2) w.M2[e0] = 0.0; amax = fmax(amax, fabs(a));
+  }
+  if (FOLD) {
+    const int c = df.ncov + (df.add_intercept ? 1 : 0);
+    for (int e = NT - 1 - t; e < n * c; e += NT) {
+      const int i = e % n, q = e / n;
+      double v;
+      if (df.add_intercept) v = (q == 0) ? 1.0 : df.Covar[(int64_t)(q - 1) * n + i];
+      else v = df.Covar[(int64_t)q * n + i];
+      if (df.wd) v *= df.wd[i];
+      df.Zs[e] = v;
+    }
+    if (t < NSTAT) stat[t] = 0;
+  }
   for (int j = t; j < 2 * n; j += NT) { w.svp[j] = 0.0; w.swp[j] = 0.0; }
   amax = block_max(amax, w.red);                 // (two barriers inside)
   const double s1_negl = (EPS * amax) * (EPS * amax);   // see k_sytrd: no reflector for a column negligible against |A|
@@ -1408,7 +1438,8 @@ __device__ void small_sytrd(const SmallWs& w, const double* __restrict__ A, int 
 // ---------------------------------------------------------------------------------------------------------------------
 // 6. n <= 124, the FAST path (round 3), three launches:
 //   k_eigf_reduce (one workgroup)  Householder tridiagonalisation in LDS (small_sytrd); T cleaned of negligible off-diagonals,
-//                                  a copy scaled into [-1, 1], its Gershgorin interval -> a small global workspace
+//                                  a copy scaled into [-1, 1], its Gershgorin interval -> a small global workspace; in a single
+//                                  call (<true>) it first BUILDS the matrix: the design and the status reset ride in its load
 //   k_eigf_pairs  (n workgroups)   workgroup k: eigenvalue k by multi-section on Sturm counts (512 points per round, 7-8 rounds
 //                                  down to the grid of doubles), then ITS eigenvector of T by the twisted factorisation -- no
 //                                  iteration, no orthogonalisation --, and the residual of the pair
@@ -1476,8 +1507,11 @@ __host__ __device__ inline EigfWs eigf_ws(double* base, int n) {
 }
 
 // (batched over matrices on blockIdx.y: matrix b's A, workspace block and status words are sA, sW, sS further on; one matrix: 0)
+// FOLD: one matrix, built here from df (small_sytrd); the batched launch is the <false> instantiation, the kernel as it was.
+static_assert(NSTAT <= 64, "k_eigf_reduce<true>: wave 0 zeroes the status block, one word per lane");
+template <bool FOLD>
 __global__ void __launch_bounds__(1024) k_eigf_reduce(const double* __restrict__ A, int n, double* __restrict__ Vg, double* __restrict__ wsb,
-                                                      int64_t* stat, int64_t sA, int64_t sW, int64_t sS) {
+                                                      int64_t* stat, int64_t sA, int64_t sW, int64_t sS, DesignFold df) {
   extern __shared__ __attribute__((aligned(16))) double sh[];
   { const int64_t bi = blockIdx.y; A += bi * sA; Vg += bi * sW; wsb += bi * sW; stat += bi * sS; }
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -1490,7 +1524,7 @@ __global__ void __launch_bounds__(1024) k_eigf_reduce(const double* __restrict__
     w.part = q; q += 8 * 128;
     w.d = q; q += n; w.e = q; q += n; w.tau = q; q += n; w.red = q; q += 16;
   }
-  small_sytrd(w, A, n, Vg, s_sc);
+  small_sytrd<FOLD>(w, A, n, Vg, s_sc, df, stat);
 #ifdef SMALL_SYTRD_DBG      // tools/dbg_small_sytrd.sh: the tridiagonal matrix as the reduction left it
   if (t == 0) { for (int j = 0; j < n; ++j) printf("sytrd_dbg n %d j %d d %.17g e %.17g tau %.17g\n", n, j, w.d[j], (j < n - 1) ? w.e[j] : 0.0, (j < n - 2) ? w.tau[j] : 0.0); }
 #endif
@@ -1672,7 +1706,7 @@ int eig_fast_max_n() { return 124; }
 // its checks to stat + b sS; each gets its own workspace block in eigW and btG.  Per matrix the arithmetic is the single launch's
 // (a pointer offset on blockIdx.y): the eigenpairs are bit-identical to launch_eig_fast on the same matrix.
 static int eig_fast_impl(blmm_ctx* ctx, const double* A, int64_t sA, int n, int nb, double* lraw, int64_t sL, double* evec, int64_t sE,
-                         int64_t* stat, int64_t sS) {
+                         int64_t* stat, int64_t sS, const DesignFold* fold = nullptr) {
   if (nb < 1 || nb > 65535) return fail(ctx, BLMM_ERR_UNSUPPORTED, "eig_fast: 1 .. 65535 matrices per batched launch");
   if (n < 3 || n > eig_fast_max_n()) return BLMM_ERR_UNSUPPORTED;
   int rc;
@@ -1684,8 +1718,14 @@ static int eig_fast_impl(blmm_ctx* ctx, const double* A, int64_t sA, int n, int 
   double* Vg = ptr<double>(ctx->eigW);
   double* wsb = Vg + (size_t)n * n;
   const EigfWs g = eigf_ws(wsb, n);
-  BLMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_eigf_reduce), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k_eigf_reduce, dim3(1, nb), dim3(1024), lds, ctx->stream, A, n, Vg, wsb, stat, sA, sW, sS);
+  if (fold) {
+    if (nb != 1 || A != fold->Ks) return fail(ctx, BLMM_ERR_INVALID, "eig_fast: the design is folded into a single matrix's launch, A = fold->Ks");
+    BLMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_eigf_reduce<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_eigf_reduce<true>, dim3(1, 1), dim3(1024), lds, ctx->stream, A, n, Vg, wsb, stat, sA, sW, sS, *fold);
+  } else {
+    BLMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_eigf_reduce<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_eigf_reduce<false>, dim3(1, nb), dim3(1024), lds, ctx->stream, A, n, Vg, wsb, stat, sA, sW, sS, DesignFold{});
+  }
   KCHECK();
   // (256 threads: 512 / 1024 per workgroup -- more points per round, fewer rounds -- measured 0.265 / 0.286 ms of eigen phase against
   // 0.256: the waves sharing a SIMD slow each other's dependent chains)
@@ -1708,8 +1748,8 @@ static int eig_fast_impl(blmm_ctx* ctx, const double* A, int64_t sA, int n, int 
   return BLMM_OK;
 }
 
-int launch_eig_fast(blmm_ctx* ctx, const double* A, int n, double* lraw, double* evec, int64_t* stat) {
-  return eig_fast_impl(ctx, A, 0, n, 1, lraw, 0, evec, 0, stat, 0);
+int launch_eig_fast(blmm_ctx* ctx, const double* A, int n, double* lraw, double* evec, int64_t* stat, const DesignFold* fold) {
+  return eig_fast_impl(ctx, A, 0, n, 1, lraw, 0, evec, 0, stat, 0, fold);
 }
 
 int launch_eig_fast_batch(blmm_ctx* ctx, const double* A, int64_t sA, int n, int nb, double* lraw, int64_t sL, double* evec, int64_t sE,

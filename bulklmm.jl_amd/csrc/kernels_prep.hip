@@ -102,74 +102,112 @@ struct PostEigenArgs {
   const double* Zs; const double* wd; int c, npad, ldr, decomp, centered;
   double* lam; double* U; double* Z0; double* Rp; double* tmp;
 };
+// s = fma(a[i sa], b[i sb], s) (NEG: fma(-a, b, s)) for i = 0 .. len-1, ONE left-to-right chain -- the order the results are defined
+// by --, its operands fetched eight steps ahead: a step of the chain is an fma, not an LDS round trip
+template <bool NEG>
+__device__ __forceinline__ double fma_chain(double s, const double* a, int sa, const double* b, int sb, int len) {
+  int i = 0;
+  for (; i + 8 <= len; i += 8) {
+    double x[8], y[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) { x[u] = a[(size_t)(i + u) * sa]; y[u] = b[(size_t)(i + u) * sb]; }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) s = fma(NEG ? -x[u] : x[u], y[u], s);
+  }
+  for (; i < len; ++i) s = fma(NEG ? -a[(size_t)i * sa] : a[(size_t)i * sa], b[(size_t)i * sb], s);
+  return s;
+}
+
+// The whole workgroup works (n <= 128: an eigenvector or the eigenvalues are at most two values per lane of a wave):
+//   wave w takes the eigenvectors w, w + nw, ...: their rows of V straight from global memory, eight rows in flight; the rank of the
+//   eigenvalue from two ballots, the largest-magnitude component by a wave arg-max (ties to the smallest index: the first index at
+//   which a sequential scan's running maximum is strictly exceeded), the signed row to U in LDS and in global memory;
+//   Z0, the Gram matrix (its c (c + 1) / 2 different entries, mirrored), Bq and the centring of Rp: one fma_chain per thread.
+// Every sum keeps the order of its one chain: the results are those of the serial form, bit for bit.
 template <bool VLDS>
 __device__ __forceinline__ void post_eigen_body(const double* __restrict__ lraw_in, const double* __restrict__ Vg, int n, const PostEigenArgs& pa,
-                                                int64_t* stat, double* shv, double* Ginv /* CMAX x CMAX */, double* Gw /* CMAX x 2 CMAX */,
-                                                int* s_neg) {
+                                                int64_t* stat, double* shv, double* Ginv /* CMAX x CMAX */, double* Gw /* CMAX x 2 CMAX */) {
+  static_assert(VLDS, "post_eigen_body: U, Zs, Z0, Bq and the weights live in LDS (n beyond that budget: k_pe_*)");
   const double* __restrict__ Zs_g = pa.Zs; const double* __restrict__ wd = pa.wd;
-  const int c = pa.c, npad = pa.npad, ldr = pa.ldr, decomp = pa.decomp, centered = pa.centered;
+  const int c = pa.c, npad = pa.npad, ldr = pa.ldr, centered = pa.centered;
+  const bool svd = pa.decomp == BLMM_SVD;
   double* __restrict__ lam = pa.lam; double* __restrict__ Ug = pa.U; double* __restrict__ Z0g = pa.Z0; double* __restrict__ Rp = pa.Rp;
-  double* __restrict__ tmp = pa.tmp;
-  const int tid = threadIdx.x, nt = blockDim.x;
-  // VLDS: V, U, Zs, Z0, Bq and the raw eigenvalues live in LDS (the loops below walk them with stride n and would
-  // otherwise pay a global-memory round trip per phase); results are also written to their global buffers.
-  double* Vl = shv;                    // n x n
-  double* Ul = shv + (size_t)n * n;    // n x n
-  double* Zsl = Ul + (size_t)n * n;    // n x c
-  double* Z0l = Zsl + (size_t)n * c;   // n x c
-  double* Bql = Z0l + (size_t)n * c;   // c x n
-  double* lrl = Bql + (size_t)n * c;   // n
-  if (VLDS) {
-    for (int e = tid; e < n * n; e += nt) Vl[e] = Vg[e];
-    for (int e = tid; e < n * c; e += nt) Zsl[e] = Zs_g[e];
+  const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wave = tid >> 6, nw = nt >> 6;
+  // LDS behind a free n x n block (V was staged there before the waves read their rows themselves): U, Zs, Z0, Bq, the weights
+  double* U = shv + (size_t)n * n;     // n x n
+  double* Zs = U + (size_t)n * n;      // n x c
+  double* Z0 = Zs + (size_t)n * c;     // n x c
+  double* Bq = Z0 + (size_t)n * c;     // c x n : Ginv * (Zs' Wd)
+  double* wdl = Bq + (size_t)n * c;    // n : wd, or ones
+  for (int e = tid; e < n * c; e += nt) Zs[e] = Zs_g[e];
+  for (int i = tid; i < n; i += nt) wdl[i] = wd ? wd[i] : 1.0;
+  double lr[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) { const int j = lane + 64 * h; const double l = (j < n) ? lraw_in[j] : 0.0; lr[h] = svd ? fabs(l) : l; }
+  if (wave == 0) {
+    const int neg = __popcll(__ballot(lane < n && lr[0] < -1e-7)) + __popcll(__ballot(lane + 64 < n && lr[1] < -1e-7));
+    if (lane == 0 && neg) stat[ST_NEG_EIG] += neg;
   }
-  const double* V = VLDS ? Vl : Vg;
-  const double* Zs = VLDS ? Zsl : Zs_g;
-  double* U = VLDS ? Ul : Ug;
-  double* Z0 = VLDS ? Z0l : Z0g;
-  double* lraw = VLDS ? lrl : tmp;          // n
-  double* Bq = VLDS ? Bql : tmp + n;        // c x n : Ginv * (Zs' Wd)
-  if (tid == 0) *s_neg = 0;
-  for (int i = tid; i < n; i += nt) lraw[i] = (decomp == BLMM_SVD) ? fabs(lraw_in[i]) : lraw_in[i];
-  __syncthreads();
-  for (int i = tid; i < n; i += nt) {
-    const double li = lraw[i];
-    int rank = 0;
-    for (int j = 0; j < n; ++j) {
-      const double lj = lraw[j];
-      if (decomp == BLMM_SVD) rank += (lj > li) || (lj == li && j < i);
-      else rank += (lj < li) || (lj == li && j < i);
+  constexpr int RW = 8;                                // rows in flight per wave: n = 79 on 12 waves is one trip
+  for (int i0 = wave; i0 < n; i0 += RW * nw) {
+    double v[RW][2];
+#pragma unroll
+    for (int r = 0; r < RW; ++r) {
+      const int ic = min(i0 + r * nw, n - 1);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) { const int k = lane + 64 * h; v[r][h] = (k < n) ? Vg[(size_t)ic * n + k] : 0.0; }
     }
-    lam[rank] = li;
-    if (li < -1e-7) atomicAdd(s_neg, 1);
-    // deterministic sign: the largest-magnitude component of every eigenvector is positive (LAPACK leaves the
-    // sign unspecified; only the permutation test depends on it)
-    double big = 0.0;
-    for (int k = 0; k < n; ++k) { const double v = V[(size_t)i * n + k]; if (fabs(v) > fabs(big)) big = v; }
-    const double sg = (big < 0.0) ? -1.0 : 1.0;
-    for (int k = 0; k < n; ++k) U[(size_t)rank * n + k] = sg * V[(size_t)i * n + k];
+#pragma unroll
+    for (int r = 0; r < RW; ++r) {
+      const int i = i0 + r * nw;
+      if (i >= n) break;                               // (wave-uniform)
+      const double li = __shfl((i >> 6) ? lr[1] : lr[0], i & 63, 64);
+      int rank = 0;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int j = lane + 64 * h;
+        const double lj = lr[h];
+        const bool before = svd ? ((lj > li) || (lj == li && j < i)) : ((lj < li) || (lj == li && j < i));
+        rank += __popcll(__ballot(j < n && before));
+      }
+      // deterministic sign: the largest-magnitude component of every eigenvector is positive (LAPACK leaves the
+      // sign unspecified; only the permutation test depends on it)
+      double big = 0.0; int bk = (lane < n) ? lane : 0x7fffffff;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) { const double x = v[r][h]; if (fabs(x) > fabs(big)) { big = x; bk = lane + 64 * h; } }
+      double m = fabs(big);
+      for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
+      int wk = (fabs(big) == m) ? bk : 0x7fffffff;
+      for (int o = 32; o > 0; o >>= 1) wk = min(wk, __shfl_xor(wk, o, 64));
+      const double sg = (__shfl(big, wk & 63, 64) < 0.0) ? -1.0 : 1.0;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int k = lane + 64 * h;
+        if (k < n) { const double u = sg * v[r][h]; U[(size_t)rank * n + k] = u; Ug[(size_t)rank * n + k] = u; }
+      }
+      if (lane == 0) lam[rank] = li;
+    }
   }
   __syncthreads();
-  if (tid == 0 && *s_neg) stat[ST_NEG_EIG] += *s_neg;
-  if (VLDS) { for (int e = tid; e < n * n; e += nt) Ug[e] = Ul[e]; }
   // Z0[k,q] = sum_i U[i,k] Zs[i,q]
   for (int e = tid; e < n * c; e += nt) {
     const int k = e % n, q = e / n;
-    double s = 0;
-    for (int i = 0; i < n; ++i) s = fma(U[(size_t)k * n + i], Zs[(size_t)q * n + i], s);
+    const double s = fma_chain<false>(0.0, U + (size_t)k * n, 1, Zs + (size_t)q * n, 1, n);
     Z0[e] = s;
-    if (VLDS) Z0g[e] = s;
+    Z0g[e] = s;
+  }
+  __syncthreads();
+  // Gram = Z0'Z0 (entry (b, a) is entry (a, b): the same products in the same order), inverse by Gauss-Jordan (c <= CMAX)
+  auto G = [&](int r_, int c_) -> double& { return Gw[r_ * (2 * CMAX) + c_]; };   // (LDS: 16 KB at CMAX = 32 -- as a local array it would be scratch memory of every thread)
+  for (int e = tid; e < c * c; e += nt) {
+    const int a = e / c, b = e % c;
+    G(a, c + b) = (a == b) ? 1.0 : 0.0;
+    if (a > b) continue;
+    const double s = fma_chain<false>(0.0, Z0 + (size_t)a * n, 1, Z0 + (size_t)b * n, 1, n);
+    G(a, b) = s; G(b, a) = s;
   }
   __syncthreads();
   if (tid == 0) {
-    // Gram = Z0'Z0, inverse by Gauss-Jordan (c <= CMAX)
-    auto G = [&](int r_, int c_) -> double& { return Gw[r_ * (2 * CMAX) + c_]; };   // (LDS: 16 KB at CMAX = 32 -- as a local array it would be scratch memory of every thread)
-    for (int a = 0; a < c; ++a)
-      for (int b = 0; b < c; ++b) {
-        double s = 0;
-        for (int k = 0; k < n; ++k) s = fma(Z0[(size_t)a * n + k], Z0[(size_t)b * n + k], s);
-        G(a, b) = s; G(a, c + b) = (a == b) ? 1.0 : 0.0;
-      }
     for (int a = 0; a < c; ++a) {
       int piv = a;
       for (int r = a + 1; r < c; ++r) if (fabs(G(r, a)) > fabs(G(piv, a))) piv = r;
@@ -184,18 +222,16 @@ __device__ __forceinline__ void post_eigen_body(const double* __restrict__ lraw_
   // Bq[q,i] = sum_r Ginv[q,r] * (Z0' U' Wd)[r,i] = sum_r Ginv[q,r] * Zs[i,r] * wd_i   (U Z0 = Zs)
   for (int e = tid; e < n * c; e += nt) {
     const int i = e % n, q = e / n;
-    double s = 0;
-    for (int r = 0; r < c; ++r) s = fma(Ginv[q * CMAX + r], Zs[(size_t)r * n + i], s);
-    Bq[(size_t)q * n + i] = s * (wd ? wd[i] : 1.0);
+    const double s = fma_chain<false>(0.0, Ginv + q * CMAX, 1, Zs + i, n, c);
+    Bq[(size_t)q * n + i] = s * wdl[i];
   }
   __syncthreads();
   for (int e = tid; e < npad * ldr; e += nt) {
     const int k = e % ldr, i = e / ldr;
     double v = 0.0;
     if (i < n && k < n) {
-      v = U[(size_t)k * n + i] * (wd ? wd[i] : 1.0);
-      if (centered)
-        for (int q = 0; q < c; ++q) v = fma(-Z0[(size_t)q * n + k], Bq[(size_t)q * n + i], v);
+      v = U[(size_t)k * n + i] * wdl[i];
+      if (centered) v = fma_chain<true>(v, Z0 + k, n, Bq + i, n, c);
     }
     Rp[e] = v;
   }
@@ -206,9 +242,8 @@ __global__ void __launch_bounds__(1024) k_post_eigen(const double* __restrict__ 
                                                      int64_t* stat) {
   __shared__ double Ginv[CMAX * CMAX];
   __shared__ double Gw[CMAX * 2 * CMAX];
-  __shared__ int s_neg;
   extern __shared__ __attribute__((aligned(16))) double shv[];
-  post_eigen_body<VLDS>(lraw_in, Vg, n, pa, stat, shv, Ginv, Gw, &s_neg);
+  post_eigen_body<VLDS>(lraw_in, Vg, n, pa, stat, shv, Ginv, Gw);
 }
 
 __global__ void __launch_bounds__(1024) k_jacobi_lds(const double* __restrict__ Ag, double* __restrict__ Vg, int n,
@@ -216,11 +251,11 @@ __global__ void __launch_bounds__(1024) k_jacobi_lds(const double* __restrict__ 
                                                      int pe_off /* doubles: where the post-eigen work arrays start in smem */) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   __shared__ double s_anorm;
-  __shared__ int s_pe_neg, s_pe_last;
+  __shared__ int s_pe_last;
   // the fast path (kernels_eig.hip: k_eigf_*) ran ahead of this launch and its checks passed: no Jacobi (workgroup-uniform).
   // fuse_post: the first workgroup then does the post-eigen work (what the next launch used to do) instead of returning.
   if (stat[ST_EIG_FAST] == 1 && __longlong_as_double((long long)stat[ST_EIG_BAD]) <= 1.0) {
-    if (fuse_post && blockIdx.x == 0) post_eigen_body<true>(lraw, Vg, n, pa, stat, smem, smem + pe_off, smem + pe_off + CMAX * CMAX, &s_pe_neg);
+    if (fuse_post && blockIdx.x == 0) post_eigen_body<true>(lraw, Vg, n, pa, stat, smem, smem + pe_off, smem + pe_off + CMAX * CMAX);
     return;
   }
   const int tid = threadIdx.x, nt = blockDim.x;
@@ -524,7 +559,7 @@ __global__ void __launch_bounds__(1024) k_jacobi_lds(const double* __restrict__ 
   __syncthreads();
   if (!s_pe_last) return;
   __threadfence();
-  post_eigen_body<true>(lraw, Vg, n, pa, stat, smem, smem + pe_off, smem + pe_off + CMAX * CMAX, &s_pe_neg);
+  post_eigen_body<true>(lraw, Vg, n, pa, stat, smem, smem + pe_off, smem + pe_off + CMAX * CMAX);
 }
 
 // Global-memory variant for larger n (one workgroup; A, V in L2): the straightforward column/row form.
