@@ -27,7 +27,7 @@ EXPORTS = [
     "blmm_read_csv", "blmm_read_he", "blmm_table_rows", "blmm_table_cols", "blmm_table_copy", "blmm_table_free",
     "blmm_kinship_rounded", "blmm_scan_alt", "blmm_scan_alt_dev", "blmm_bulkscan_alt_exact", "blmm_bulkscan_alt_exact_dev",
     "blmm_prepare_dev", "blmm_rotated_rows", "blmm_rotate_block_dev", "blmm_bulkscan_prerotated_dev", "blmm_scan_perms_prerotated_dev",
-    "blmm_set_tuning", "blmm_get_tuning", "blmm_lowrank_columns", "blmm_bulkscan_reduced", "blmm_bulkscan_reduced_dev", "blmm_last_reduced_route",
+    "blmm_set_tuning", "blmm_get_tuning", "blmm_lowrank_columns", "blmm_bulkscan_reduced", "blmm_bulkscan_reduced_dev", "blmm_last_reduced_route", "blmm_last_front_route",
     "blmm_bulkscan_reduced_async", "blmm_bulkscan_perms", "blmm_bulkscan_perms_dev",
     "blmm_last_dims", "blmm_last_lod_colmax", "blmm_last_lod_columns", "blmm_multi_last_colmax", "blmm_multi_last_lod_threshold",
     "blmm_kinship_loco", "blmm_kinship_loco_dev", "blmm_bulkscan_loco", "blmm_bulkscan_loco_dev",
@@ -202,6 +202,7 @@ def load():
     lib.blmm_bulkscan_reduced.argtypes = [vp, op, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, i64, rp, vp, sp]
     lib.blmm_bulkscan_reduced_dev.argtypes = [vp, op, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, i64, rp, vp, sp]
     lib.blmm_last_reduced_route.argtypes = [vp]
+    lib.blmm_last_front_route.argtypes = [vp]
     lib.blmm_bulkscan_reduced_async.argtypes = [vp, op, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, i64, rp, vp, vp]
     lib.blmm_bulkscan_perms.argtypes = [vp, op, vp, i64, i64, vp, i64, vp, i64, vp, vp, i64, C.c_uint64, vp, vp, i64,
                                         vp, vp, vp, vp, vp, vp, vp, sp]

@@ -391,7 +391,12 @@ int rotate_markers(blmm_ctx* ctx, Pipe& P, const double* dG, int64_t p);
 // dG != nullptr: the marker rotation goes to the side stream as well, in front of the basis (the h2 search on the main stream needs
 // only the rotated traits; the marker-side products that follow the basis on the side stream and -- behind ev_join -- the scan
 // need Xt): 12 us less in front of k_brent at the BXD shape
-int start_wbasis(blmm_ctx* ctx, Pipe& P, const double* dG = nullptr, int64_t p = 0, bool xt_recorded = false) {
+// early_decomp >= 0: k_eigf_pairs has recorded ev_pairs (prepare): the basis is built from the solver's raw eigenvalues right behind
+// that kernel, ~50 us before the eigen phase ends, and a second launch behind the phase's end stands in for it should the device have
+// rejected the fast path (kernels_lowrank.hip: WbMode) -- the basis and the marker-side products behind it leave the critical path
+enum FrontRoute { FRONT_EARLY_WB = 1, FRONT_FUSED_ROT = 2, FRONT_WB_REBUILT = 8 };   // (bit 2: kept free for region 0's counts from k_brent)
+static bool front_switch(const char* name) { const char* e = dev_env(name); return !(e && e[0] == '0'); }
+int start_wbasis(blmm_ctx* ctx, Pipe& P, const double* dG = nullptr, int64_t p = 0, bool xt_recorded = false, int early_decomp = -1) {
   int rc;
   const int64_t n = P.n;
   const LrSeg seg = lr_segments(ctx, P.n);
@@ -413,10 +418,17 @@ int start_wbasis(blmm_ctx* ctx, Pipe& P, const double* dG = nullptr, int64_t p =
     // ask for phase timings: +35 us per call; profiles/r04_timeline_notiming_*.txt).  The marker-side products follow the basis
     // on ITS stream (lr_begin: no cross-queue wait between the two, each of which costs 14-20 us here) and wait there for
     // the rotation (ev_wb), which is done long before.
-    BLMM_HIP(hipStreamWaitEvent(ctx->side2, ctx->ev_xt, 0));
     ctx->wb_on_side2 = true;
     OnStream on(ctx, ctx->side2);
-    if ((rc = launch_wbasis(ctx, P.lam, (int)n, P.npad, seg, ptr<double>(ctx->wbW), ptr<double>(ctx->wbQ), ptr<int>(ctx->wbRk), P.stat))) return rc;
+    if (early_decomp >= 0) {
+      BLMM_HIP(hipStreamWaitEvent(ctx->side2, ctx->ev_pairs, 0));
+      if ((rc = launch_wbasis(ctx, P.lam, (int)n, P.npad, seg, ptr<double>(ctx->wbW), ptr<double>(ctx->wbQ), ptr<int>(ctx->wbRk), P.stat,
+                              WB_EARLY, ptr<double>(ctx->lraw), early_decomp))) return rc;
+      ctx->last_front_route |= FRONT_EARLY_WB;
+    }
+    BLMM_HIP(hipStreamWaitEvent(ctx->side2, ctx->ev_xt, 0));
+    if ((rc = launch_wbasis(ctx, P.lam, (int)n, P.npad, seg, ptr<double>(ctx->wbW), ptr<double>(ctx->wbQ), ptr<int>(ctx->wbRk), P.stat,
+                            early_decomp >= 0 ? WB_REDO : WB_LAM))) return rc;
   }
   OnStream on(ctx, ctx->side);
   if (ctx->in_wait) BLMM_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_in, 0));
@@ -454,9 +466,22 @@ int prepare(blmm_ctx* ctx, const blmm_opts* o, const double* dY, int64_t n, int6
   const bool forks = m > 0 && p > 0 && (early_wbasis || grid_side);
   ctx->stop_event_used = false;
   ctx->stop_event_next = forks ? ctx->ev_xt : nullptr;
+  // (BLMM_ROTATE_SIDE=0: the marker rotation stays on the main stream behind the traits' -- A/B testing)
+  static const bool rot_side = !(dev_env("BLMM_ROTATE_SIDE") && dev_env("BLMM_ROTATE_SIDE")[0] == '0');
+  // only where the rotation is the small latency-bound kernel (n <= 160): the GEMM of larger n fills the chip by itself, and behind it
+  // the basis and the marker-side products come later (n = 500 shard: 6.32 against 6.29 ms; BXD: 1.714 against 1.734 ms, 4 A/B rounds)
+  const bool side_g = early_wbasis && m > 0 && p > 0 && rot_side && n <= 160;
+  // the weight basis behind k_eigf_pairs: a single call's fast eigen route, the register-resident basis kernel on its own stream
+  // (BLMM_EARLY_WB=0: behind the eigen phase's end as before -- A/B testing)
+  static const char* mw_env = dev_env("BLMM_WBASIS");
+  ctx->last_front_route = 0;
+  ctx->pairs_event_used = false;
+  ctx->pairs_event_next = (side_g && !pre && n <= 80 && !(mw_env && std::strcmp(mw_env, "lds") == 0) && front_switch("BLMM_EARLY_WB")) ? ctx->ev_pairs : nullptr;
   int rc = prepare_eigen(ctx, o, n, dCovar, ncov, dK, dweights, centered, P, tm, pre);
   const bool xt_recorded = ctx->stop_event_used;
   ctx->stop_event_next = nullptr; ctx->stop_event_used = false;
+  const bool early_basis = ctx->pairs_event_used;
+  ctx->pairs_event_next = nullptr; ctx->pairs_event_used = false;
   if (rc) return rc;
   // (host entry points) the eigen phase is queued: now the traits and the markers go up, beside it; this stream reads them next
   if (ctx->up_pending) {
@@ -464,12 +489,7 @@ int prepare(blmm_ctx* ctx, const blmm_opts* o, const double* dY, int64_t n, int6
     BLMM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_inY, 0));
   }
   const bool up_flight = ctx->in_wait;
-  // (BLMM_ROTATE_SIDE=0: the marker rotation stays on the main stream behind the traits' -- A/B testing)
-  static const bool rot_side = !(dev_env("BLMM_ROTATE_SIDE") && dev_env("BLMM_ROTATE_SIDE")[0] == '0');
-  // only where the rotation is the small latency-bound kernel (n <= 160): the GEMM of larger n fills the chip by itself, and behind it
-  // the basis and the marker-side products come later (n = 500 shard: 6.32 against 6.29 ms; BXD: 1.714 against 1.734 ms, 4 A/B rounds)
-  const bool side_g = early_wbasis && m > 0 && p > 0 && rot_side && n <= 160;
-  if (early_wbasis && m > 0 && p > 0 && (rc = start_wbasis(ctx, P, side_g ? dG : nullptr, p, xt_recorded))) return rc;
+  if (early_wbasis && m > 0 && p > 0 && (rc = start_wbasis(ctx, P, side_g ? dG : nullptr, p, xt_recorded, early_basis ? (int)o->decomp_scheme : -1))) return rc;
   P.xt_side = side_g;
   // the grid methods (grid_side): the marker rotation and, later, the marker norms of every grid point (launch_isx) on the side stream,
   // beside the traits' rotation, the grid log-likelihoods and the trait panels on the main stream; joined in front of the scan
@@ -481,7 +501,15 @@ int prepare(blmm_ctx* ctx, const blmm_opts* o, const double* dY, int64_t n, int6
     if ((rc = rotate_markers(ctx, P, dG, p))) return rc;
     P.xt_side = true;
   }
-  if ((rc = rotate_traits(ctx, P, dY, m))) return rc;
+  // the single null-exact call at n <= 80: k_brent, the next kernel of this stream, rotates its traits itself (scan_pipeline hands it
+  // P.fuseY) -- no launch of its own, no write -> read round trip of Yt in front of the search (BLMM_FUSE_ROT=0: A/B testing)
+  if (early_wbasis && !pre && m > 0 && p > 0 && brent_fuses_rotation(P.n, P.c) && front_switch("BLMM_FUSE_ROT")) {
+    P.m = m; P.ldy = round_up(m, 128);
+    if ((rc = ensure(ctx, ctx->Yt, sizeof(double) * (size_t)P.npad * P.ldy))) return rc;
+    P.Yt = ptr<double>(ctx->Yt);
+    P.fuseY = dY;
+    ctx->last_front_route |= FRONT_FUSED_ROT;
+  } else if ((rc = rotate_traits(ctx, P, dY, m))) return rc;
   if (skip_markers) { P.p = p; P.ldx = round_up(p > 0 ? p : 1, 128); P.Xt = nullptr; }   // the caller rotates them itself (fp32 permutation path)
   else if (!P.xt_side) {
     if (up_flight) BLMM_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_in, 0));     // (the markers on this stream: they went up second)
@@ -830,6 +858,7 @@ int blmm_create(int device_id, void* hip_stream, blmm_ctx** out) {
       hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&ctx->ev_xt, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&ctx->ev_pairs, hipEventDisableTiming) != hipSuccess ||
       hipStreamCreateWithFlags(&ctx->side2, hipStreamNonBlocking) != hipSuccess ||
       hipEventCreateWithFlags(&ctx->ev_b1, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&ctx->ev_b2, hipEventDisableTiming) != hipSuccess ||
@@ -883,6 +912,7 @@ void blmm_destroy(blmm_ctx* ctx) {
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
   if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
   if (ctx->ev_xt) (void)hipEventDestroy(ctx->ev_xt);
+  if (ctx->ev_pairs) (void)hipEventDestroy(ctx->ev_pairs);
   if (ctx->ev_b1) (void)hipEventDestroy(ctx->ev_b1);
   if (ctx->ev_b2) (void)hipEventDestroy(ctx->ev_b2);
   if (ctx->ev_q) (void)hipEventDestroy(ctx->ev_q);
@@ -1246,7 +1276,10 @@ static int scan_pipeline(blmm_ctx* ctx, const blmm_opts* opts, Pipe& P, Timer& t
       const bool split_on = (ctx->red_cur.flags && P.c >= 2) ? false
                           : split_env ? split_env[0] != '0' : (ctx->tune.lr_split < 0 ? m >= 8192 : ctx->tune.lr_split != 0);
       BrentSplit sp;
-      if ((rc = launch_brent(ctx, nm, P.Yt, P.ldy, m, P.Z0, P.lam, dh2_out, nullptr, nullptr, P.stat, split_on ? 1 : 0, &sp))) return rc;
+      BrentRot rot;
+      if (P.fuseY) { rot.Y = P.fuseY; rot.Rp = ptr<double>(ctx->Rp); rot.Yt = P.Yt; rot.ldr = P.ldr; rot.npad = P.npad; rot.ncols_pad = P.ldy; }
+      if ((rc = launch_brent(ctx, nm, P.Yt, P.ldy, m, P.Z0, P.lam, dh2_out, nullptr, nullptr, P.stat, split_on ? 1 : 0, &sp, &rot))) return rc;
+      P.fuseY = nullptr;                       // Yt is written
       tm.mark();
       if (sp.active) { if ((rc = lr_finish_split(ctx, P, nm, dh2_out, dL_out, ldL, tm, sp))) return rc; }
       else if ((rc = lr_finish(ctx, P, nm, dh2_out, dL_out, ldL, tm))) return rc;
@@ -2091,6 +2124,21 @@ int blmm_bulkscan_reduced(blmm_ctx* ctx, const blmm_opts* opts, const double* Y,
 }
 
 int blmm_last_reduced_route(const blmm_ctx* ctx) { return ctx ? ctx->last_reduced_route : 0; }
+
+// Which parts of the shortened null-exact front the last call took: bit 0 the weight basis behind k_eigf_pairs, bit 1 the traits
+// rotated inside k_brent, bit 3 the basis was rebuilt behind the Jacobi fallback (read from the device: the basis kernel reports
+// it).  Waits for the stream.  < 0: an error code
+int blmm_last_front_route(blmm_ctx* ctx) {
+  if (!ctx) return BLMM_ERR_INVALID;
+  int route = ctx->last_front_route;
+  if ((route & FRONT_EARLY_WB) && ctx->wbRk.p) {
+    int rk[4] = {0, 0, 0, 0};
+    if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess ||
+        hipMemcpy(rk, ctx->wbRk.p, sizeof(rk), hipMemcpyDeviceToHost) != hipSuccess) return BLMM_ERR_HIP;
+    if (rk[3] == 1) route |= FRONT_WB_REBUILT;
+  }
+  return route;
+}
 
 // ---------------------------------------------------------------------------------------------------
 // Stream-ordered reduced bulkscan (include/bulklmm_hip.h: blmm_bulkscan_reduced_async).  The fused route does not speculate: the

@@ -78,6 +78,7 @@ struct Pipe {
   int64_t* stat = nullptr;
   bool big = false;                // n beyond the LDS Jacobi: the call ends with k_sticky
   bool xt_side = false;            // the marker rotation was enqueued on the side stream (in front of the weight basis): Xt is ordered there
+  const double* fuseY = nullptr;   // prepare() left the traits' rotation to the h2 search's kernel (BrentRot): the caller's Y, Yt not written yet
 };
 
 // Reduce-in-epilogue output of the scan kernels (blmm_bulkscan_reduced; SURVEY.md N1: "the matrix never has to leave HBM" -- here
@@ -130,6 +131,11 @@ struct blmm_ctx {
   // completion signal) instead of by a marker packet behind that kernel: a hipEventRecord between two dependent kernels of the main
   // stream cost 10-12 us of its critical path (profiles/r04_timeline_notiming_*.txt).  stop_event_used: the launch took it.
   hipEvent_t stop_event_next = nullptr; bool stop_event_used = false;
+  // ... and one for the fast eigen path's k_eigf_pairs (a single matrix's launch): the eigenvalues are final there unless the
+  // device rejects the path later, and the weight basis needs nothing else (blmm_api.hip: start_wbasis)
+  hipEvent_t ev_pairs = nullptr, pairs_event_next = nullptr; bool pairs_event_used = false;
+  // The null-exact front of the last call (blmm_last_front_route): FRONT_* bits known to the host
+  int last_front_route = 0;
   bool wb_on_side2 = false;            // start_wbasis: the weight basis went to the second side stream (lr_begin follows it there)
   // Host entry points (blmm_bulkscan, blmm_bulkscan_reduced): K, the covariates and the weights go up first, the eigen phase is
   // queued, and only then Y and G are copied -- on their own stream, beside the eigen kernels (0.23 ms at n = 79 that the caller
@@ -294,9 +300,14 @@ struct BrentSplit {
   const int* list = nullptr;
   const unsigned int* cnt = nullptr;
 };
+// The traits' rotation inside k_brent (four lanes per trait, register evaluator: n <= 80): every wave rotates its own 16 columns of
+// the caller's Y with k_rotate's arithmetic (rotate_wave), writes them to Yt -- rows up to npad, columns up to ncols_pad, as
+// launch_rotate does -- and straight into its LDS slab.  Y == nullptr: Yt holds the rotated traits already.
+struct BrentRot { const double* Y = nullptr; const double* Rp = nullptr; double* Yt = nullptr; int ldr = 0, npad = 0; int64_t ncols_pad = 0; };
+bool brent_fuses_rotation(int n, int c);     // launch_brent takes a BrentRot at this size
 int launch_brent(blmm_ctx* ctx, const NullModel& nm, const double* Yt, int64_t ldy, int64_t m, const double* Z0,
                  const double* lam, double* h2, double* sigma2, double* ell, int64_t* stat, int phase = 0,
-                 BrentSplit* sp = nullptr);
+                 BrentSplit* sp = nullptr, const BrentRot* rot = nullptr);
 // scan_alt: per-marker fitlmm on [Z0 x_i] and the LOD against the null model (the trait is column 0 of Yt)
 int launch_alt_brent(blmm_ctx* ctx, const NullModel& nm, const double* Yt, int64_t ldy, const double* Xt, int64_t ldx, int64_t p,
                      const double* Z0, const double* lam, const double* h2null, int true_w, double* lod, double* h2each,
@@ -481,7 +492,9 @@ inline int qr_workspace(blmm_ctx* ctx, int cols, int n, size_t* lds, double** sl
 // kernels_lowrank.hip
 // the segments a call with n individuals uses (one when the basis comes from the multi-workgroup / LDS kernels: n > 80)
 LrSeg lr_segments(const blmm_ctx* ctx, int n);
-int launch_wbasis(blmm_ctx* ctx, const double* lam, int n, int npad, const LrSeg& seg, double* Wk, double* Q, int* rk, int64_t* stat);
+enum WbMode { WB_LAM = 0, WB_EARLY = 1, WB_REDO = 2 };   // kernels_lowrank.hip: k_wbasis_reg
+int launch_wbasis(blmm_ctx* ctx, const double* lam, int n, int npad, const LrSeg& seg, double* Wk, double* Q, int* rk, int64_t* stat,
+                  int mode = WB_LAM, const double* lraw = nullptr, int decomp = 0);
 int launch_lr_tpanels(blmm_ctx* ctx, const double* Xt, int64_t ldx, int64_t p, int n, int c, int npad, const double* Z0,
                       const double* Q, const int* rk, const LrSeg& seg, double* T, int64_t tstride, double* den0);
 int launch_lr_panels(blmm_ctx* ctx, const NullModel& nm, const double* Yt, int64_t ldy, int64_t m, const double* Z0,
@@ -623,11 +636,13 @@ int launch_effects(blmm_ctx* ctx, EffArgs a);
 
 }  // namespace blmm
 
-// launch on ctx->stream; a pending ctx->stop_event_next is recorded by this kernel's completion (see blmm_ctx)
-#define BLMM_LAUNCH_STOP(ctx_, kernel_, grid_, block_, lds_, ...)                                                          \
+// launch on ctx->stream; a pending event in the slot (next_, used_) of ctx is recorded by this kernel's completion (see blmm_ctx)
+#define BLMM_LAUNCH_STOP_AT(ctx_, next_, used_, kernel_, grid_, block_, lds_, ...)                                         \
   do {                                                                                                                   \
-    if ((ctx_)->stop_event_next) {                                                                                       \
-      hipExtLaunchKernelGGL(kernel_, grid_, block_, (std::uint32_t)(lds_), (ctx_)->stream, nullptr, (ctx_)->stop_event_next, 0, __VA_ARGS__); \
-      (ctx_)->stop_event_next = nullptr; (ctx_)->stop_event_used = true;                                                 \
+    if ((ctx_)->next_) {                                                                                                 \
+      hipExtLaunchKernelGGL(kernel_, grid_, block_, (std::uint32_t)(lds_), (ctx_)->stream, nullptr, (ctx_)->next_, 0, __VA_ARGS__); \
+      (ctx_)->next_ = nullptr; (ctx_)->used_ = true;                                                                     \
     } else hipLaunchKernelGGL(kernel_, grid_, block_, lds_, (ctx_)->stream, __VA_ARGS__);                                 \
   } while (0)
+// ... the slot of the phase-ending launches: ctx->stop_event_next
+#define BLMM_LAUNCH_STOP(ctx_, ...) BLMM_LAUNCH_STOP_AT(ctx_, stop_event_next, stop_event_used, __VA_ARGS__)

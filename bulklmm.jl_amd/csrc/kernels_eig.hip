@@ -1732,8 +1732,10 @@ static int eig_fast_impl(blmm_ctx* ctx, const double* A, int64_t sA, int n, int 
   const int64_t sG = nb > 1 ? round_up((int64_t)8 * bt_groups(n), 32) : 0;
   if ((rc = ensure(ctx, ctx->btG, nb > 1 ? sizeof(double) * (size_t)nb * sG : sizeof(double) * 8 * (size_t)bt_groups(n)))) return rc;
   double* btG = ptr<double>(ctx->btG);
-  hipLaunchKernelGGL(k_eigf_pairs<256>, dim3(n + (bt_groups(n) + 3) / 4, nb), dim3(256), 0, ctx->stream, n, (const double*)wsb, lraw, stat,
-                     (const double*)Vg, btG, sW, sL, sS, sG);
+  if (nb != 1) ctx->pairs_event_next = nullptr;   // (only a single matrix's launch records it)
+  // (the kernel's own stop event: no marker packet behind it on this stream)
+  BLMM_LAUNCH_STOP_AT(ctx, pairs_event_next, pairs_event_used, k_eigf_pairs<256>, dim3(n + (bt_groups(n) + 3) / 4, nb), dim3(256), 0, n,
+                      (const double*)wsb, lraw, stat, (const double*)Vg, btG, sW, sL, sS, sG);
   KCHECK();
   static const bool bt_stage_off = dev_env("BLMM_BT_STAGE") && dev_env("BLMM_BT_STAGE")[0] == '0';
   const int stage_v = (bt_lds_staged(2, n) <= 158 * 1024 && !bt_stage_off) ? 1 : 0;

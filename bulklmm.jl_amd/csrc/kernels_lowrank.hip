@@ -179,9 +179,15 @@ __global__ void __launch_bounds__(WB_NS * TPS) k_wbasis(const double* __restrict
 // each), so the deflation of every column -- the bulk of an iteration -- touches LDS only for the new basis vector.  Same
 // greedy sequence as k_wbasis (same samples when that one runs with 256 of them, same pivot rule).
 // blockIdx.x = segment of the heritability axis (LrSeg): its own samples, its own basis Q + blockIdx.x * qstride, rk + 4 * blockIdx.x.
+// mode (WbMode): WB_LAM reads the sorted eigenvalues.  WB_EARLY runs behind k_eigf_pairs, before the post-eigen work has written
+// them: it reads the solver's raw eigenvalues and ranks them itself by post_eigen_body's rule (ascending, svd: |lambda| descending,
+// ties by index), so its LDS copy is bit for bit what lam will be; it leaves the rank word of the status block alone.  WB_REDO
+// runs behind the eigen phase's end: where the fast path stood it only publishes the ranks the early launch found; where the device
+// rejected it (the Jacobi has rewritten the eigenvalues since) it builds the basis again from the final lam and says so in rk[3].
 template <int NKR>
 __global__ void __launch_bounds__(1024) k_wbasis_reg(const double* __restrict__ lam, int n, double* __restrict__ Q,
-                                                     int* __restrict__ rk, int64_t* stat, int qcap, LrSeg seg, int64_t qstride) {
+                                                     int* __restrict__ rk, int64_t* stat, int qcap, LrSeg seg, int64_t qstride,
+                                                     const double* __restrict__ lraw, int decomp, int mode) {
   extern __shared__ __attribute__((aligned(16))) double sh[];
   constexpr int TPS = 4, NS = 256, NT = 1024;
   const int sg = blockIdx.x;
@@ -195,13 +201,38 @@ __global__ void __launch_bounds__(1024) k_wbasis_reg(const double* __restrict__ 
   __shared__ double s_piv_val;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, nwave = NT >> 6;
   const int s = t / TPS, part = t % TPS;
+  __shared__ double s_lam[TPS * NKR];
+  if (mode == WB_REDO && stat[ST_EIG_FAST] == 1 && __longlong_as_double((long long)stat[ST_EIG_BAD]) <= 1.0) {   // (workgroup-uniform)
+    if (t == 0) atomicMax((unsigned long long*)&stat[ST_LR_RANK], (unsigned long long)rk[0]);
+    return;
+  }
+  if (mode == WB_EARLY) {
+    // Where the device rejects the fast path, this launch's result may be garbage: lraw can hold NaN (every comparison false, all
+    // ranks 0, the rest of s_lam unwritten) and the Jacobi may rewrite it while it is read here.  Every loop below is bounded by n
+    // and qcap whatever s_lam holds, and the WB_REDO launch behind the eigen phase's end then rebuilds Q and rk from lam.
+    if (t < n) {
+      const bool svd = decomp == BLMM_SVD;
+      const double li = svd ? fabs(lraw[t]) : lraw[t];
+      int rank = 0;
+      for (int j = 0; j < n; ++j) {
+        const double lj = svd ? fabs(lraw[j]) : lraw[j];
+        rank += (svd ? ((lj > li) || (lj == li && j < t)) : ((lj < li) || (lj == li && j < t))) ? 1 : 0;
+      }
+      s_lam[rank] = li;
+    }
+  } else {
+    for (int k = t; k < n; k += NT) s_lam[k] = lam[k];
+  }
   if (t == 0) s_neg = 0;
   __syncthreads();
-  for (int k = t; k < n; k += NT) if (lam[k] < -1e-12) s_neg = 1;
+  for (int k = t; k < n; k += NT) if (s_lam[k] < -1e-12) s_neg = 1;
   __syncthreads();
   if (s_neg) {
     for (int e = t; e < n * n; e += NT) Q[e] = ((e / n) == (e % n)) ? 1.0 : 0.0;
-    if (t == 0) { rk[0] = n; rk[1] = (n + 3) / 4; stat[ST_LR_RANK] = n; }
+    if (t == 0) {
+      rk[0] = n; rk[1] = (n + 3) / 4; rk[3] = mode == WB_REDO;
+      if (mode != WB_EARLY) stat[ST_LR_RANK] = n;
+    }
     return;
   }
   // one segment: delta_0 = 0 (w = 1), then log-spaced over [1e-6, 1e9] (h2 from 1e-6 to 1 - 1e-9).  Several: sample 0 is the
@@ -219,7 +250,7 @@ __global__ void __launch_bounds__(1024) k_wbasis_reg(const double* __restrict__ 
 #pragma unroll
   for (int i = 0; i < NKR; ++i) {
     const int k = part + TPS * i;
-    wv[i] = (k < n) ? 1.0 / fma(delta, fabs(lam[k]), 1.0) : 0.0;
+    wv[i] = (k < n) ? 1.0 / fma(delta, fabs(s_lam[k]), 1.0) : 0.0;
     nrm = fma(wv[i], wv[i], nrm);
   }
   nrm += __shfl_xor(nrm, 1, 64); nrm += __shfl_xor(nrm, 2, 64);
@@ -305,7 +336,10 @@ __global__ void __launch_bounds__(1024) k_wbasis_reg(const double* __restrict__ 
     res2 = r2;
     __syncthreads();
   }
-  if (t == 0) { rk[0] = R; rk[1] = (R + 3) / 4; atomicMax((unsigned long long*)&stat[ST_LR_RANK], (unsigned long long)R); }   // the largest rank over the segments
+  if (t == 0) {
+    rk[0] = R; rk[1] = (R + 3) / 4; rk[3] = mode == WB_REDO;
+    if (mode != WB_EARLY) atomicMax((unsigned long long*)&stat[ST_LR_RANK], (unsigned long long)R);   // the largest rank over the segments
+  }
 }
 
 // Multi-workgroup variant for n beyond the single-workgroup LDS budget.  The 256 sample columns are dealt S per
@@ -476,7 +510,8 @@ LrSeg lr_segments(const blmm_ctx* ctx, int n) {
   return sg;
 }
 
-int launch_wbasis(blmm_ctx* ctx, const double* lam, int n, int npad, const LrSeg& seg, double* Wk, double* Q, int* rk, int64_t* stat) {
+int launch_wbasis(blmm_ctx* ctx, const double* lam, int n, int npad, const LrSeg& seg, double* Wk, double* Q, int* rk, int64_t* stat,
+                  int mode, const double* lraw, int decomp) {
   // LDS budget (156 KB dynamic): two work vectors, the sample columns when 256, 192 or 128 of them fit (padded to
   // ns + 16 per row) beside at least 16 mirrored basis vectors, then as many mirrored basis vectors as fit (<= WB_QCAP)
   const size_t budget = 156 * 1024, work = sizeof(double) * (size_t)2 * n, row = sizeof(double) * (size_t)n;
@@ -490,10 +525,12 @@ int launch_wbasis(blmm_ctx* ctx, const double* lam, int n, int npad, const LrSeg
     const int qcap = (int)std::min<size_t>(WB_QCAP, (budget - work) / row);
     const size_t lds = work + row * qcap;
     BLMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wbasis_reg<20>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_wbasis_reg<20>, dim3((unsigned)seg.S), dim3(1024), lds, ctx->stream, lam, n, Q, rk, stat, qcap, seg, (int64_t)npad * n);
+    hipLaunchKernelGGL(k_wbasis_reg<20>, dim3((unsigned)seg.S), dim3(1024), lds, ctx->stream, lam, n, Q, rk, stat, qcap, seg, (int64_t)npad * n,
+                       lraw, decomp, mode);
     KCHECK();
     return BLMM_OK;
   }
+  if (mode != WB_LAM) return fail(ctx, BLMM_ERR_INVALID, "launch_wbasis: only the register-resident basis kernel runs ahead of the eigenvalues' sort");
   if (seg.S != 1) return fail(ctx, BLMM_ERR_INVALID, "launch_wbasis: several segments need the register-resident basis kernel");
   if (ns) {
     const size_t wbytes = row * (size_t)(ns + 16);

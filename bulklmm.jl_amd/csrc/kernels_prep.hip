@@ -874,18 +874,15 @@ int launch_post_eigen(blmm_ctx* ctx, const double* lraw, const double* V, const 
 //   D: col = l&15, row = (l>>4) + 4*reg   (cdna_hip_programming.md §3, verified by tools/mb_f64.hip).
 // In is column-major n x ncols; Out is row-major (npad rows) with leading dimension ldo.
 // ------------------------------------------------------------------------------------------------
+// One wave's products: acc[b][r] = Out[row (rb0 + b) * 16 + (lane >> 4) + 4 r][col], col = the wave's first column + (lane & 15)
+// (colok: it exists; else zeros).  Shared by k_rotate and by k_brent's fused prologue: the same loads, the same MFMAs in the same
+// order, the same bits.
 template <int MBLK>
-__global__ void __launch_bounds__(256) k_rotate(const double* __restrict__ Rp, int ldr, int n, int npad,
-                                                const double* __restrict__ In, int64_t ncols,
-                                                double* __restrict__ Out, int64_t ldo, int64_t ncols_pad) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t col = ((int64_t)blockIdx.x * 4 + wave) * 16 + (lane & 15);
-  const int rb0 = blockIdx.y * MBLK;  // first 16-row block of this wave
+__device__ __forceinline__ void rotate_wave(const double* __restrict__ Rp, int ldr, int n, int npad, const double* __restrict__ In,
+                                            bool colok, int64_t col, int rb0, int lane, d4 (&acc)[MBLK]) {
   const int kk = lane >> 4;
-  d4 acc[MBLK];
 #pragma unroll
   for (int b = 0; b < MBLK; ++b) acc[b] = (d4){0, 0, 0, 0};
-  const bool colok = col < ncols;
   const double* pin = In + (colok ? col : 0) * (int64_t)n;
   // four K steps per trip, every operand load of the trip issued before its first MFMA: a load placed next to its use
   // exposes one L2 round trip per K step (the kernel runs at ~2 waves per SIMD)
@@ -907,6 +904,12 @@ __global__ void __launch_bounds__(256) k_rotate(const double* __restrict__ Rp, i
 #pragma unroll
       for (int b = 0; b < MBLK; ++b) acc[b] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u][b], bv[u], acc[b], 0, 0, 0);
   }
+}
+// ... and their way to Out (row-major, rows below npad, columns below ncols_pad)
+template <int MBLK>
+__device__ __forceinline__ void rotate_wave_store(const d4 (&acc)[MBLK], double* __restrict__ Out, int64_t ldo, int64_t ncols_pad, int npad,
+                                                  int64_t col, int rb0, int lane) {
+  const int kk = lane >> 4;
   if (col < ncols_pad) {
 #pragma unroll
     for (int b = 0; b < MBLK; ++b)
@@ -916,6 +919,18 @@ __global__ void __launch_bounds__(256) k_rotate(const double* __restrict__ Rp, i
         if (row < npad) Out[(int64_t)row * ldo + col] = acc[b][r];
       }
   }
+}
+
+template <int MBLK>
+__global__ void __launch_bounds__(256) k_rotate(const double* __restrict__ Rp, int ldr, int n, int npad,
+                                                const double* __restrict__ In, int64_t ncols,
+                                                double* __restrict__ Out, int64_t ldo, int64_t ncols_pad) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t col = ((int64_t)blockIdx.x * 4 + wave) * 16 + (lane & 15);
+  const int rb0 = blockIdx.y * MBLK;  // first 16-row block of this wave
+  d4 acc[MBLK];
+  rotate_wave<MBLK>(Rp, ldr, n, npad, In, col < ncols, col, rb0, lane, acc);
+  rotate_wave_store<MBLK>(acc, Out, ldo, ncols_pad, npad, col, rb0, lane);
 }
 
 // A handful of columns at large n (the single trait of scan / scan_perms): one matrix-vector product per column, rows of
@@ -1585,6 +1600,9 @@ __device__ __forceinline__ int brent_run(F& f, BrentState& S, int max_it) {
 // Continuation area of the two-kernel form: traits unfinished after BRENT_PHASE1 iterations are appended to `list`
 // with their Brent state (st[f * m + j], f < 12: the ten doubles of BrentState, the iteration count, the non-positive
 // weight flag) and finished by k_brent2 in densely packed lane groups.  list == nullptr: repack inside the workgroup.
+// Yt is __restrict__ and, with the fused rotation (rot.Y != nullptr), also written through rot.Yt: that holds only because the fused
+// branch reads nothing through Yt (stage_null_y is skipped, the slab comes from the accumulators).  A change that reads Yt in a
+// fused launch must drop the __restrict__ first.
 struct BrentCont {
   double* st;
   int* list;
@@ -1597,10 +1615,35 @@ __global__ void __launch_bounds__(256, BRENT_MINW) k_brent(NullModel nm, const d
                                                const double* __restrict__ Z0, const double* __restrict__ lam,
                                                const double* __restrict__ logtab, double* __restrict__ h2out,
                                                double* __restrict__ s2out, double* __restrict__ ellout, int64_t* stat,
-                                               BrentCont cont) {
+                                               BrentCont cont, BrentRot rot) {
   extern __shared__ __attribute__((aligned(16))) double sh[];
   __shared__ dpair s_ln[BLMM_LOG_TABLE_N];
   const int n = nm.n;
+  bool fused = false;
+  if constexpr (REG && LPT == 4) {
+    // The traits' rotation, fused (rot.Y; kernel-uniform): this wave's 16 traits are k_rotate<5>'s 16 columns of one wave, and that
+    // kernel's D layout -- row kk + 4 (r + 4 b) of trait l & 15 in lane 16 kk + (l & 15) -- is this kernel's lane ownership: kk is
+    // `sub`, r + 4 b the slab row i of stage_null_y, the trait's four lanes are the threads 4 (l & 15) + kk of the wave.  The grid
+    // covers the columns up to ncols_pad; a workgroup past the last trait only writes its zeros.
+    fused = rot.Y != nullptr;
+    if (fused) {
+      constexpr int RB = NULL_NK / 4;            // 16-row blocks: all of npad <= 80
+      const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, kk = lane >> 4;
+      const int64_t col = ((int64_t)blockIdx.x * 4 + wave) * 16 + (lane & 15);
+      d4 acc[RB];
+      rotate_wave<RB>(rot.Rp, rot.ldr, n, rot.npad, rot.Y, col < m, col, 0, lane, acc);
+      rotate_wave_store<RB>(acc, rot.Yt, ldy, rot.ncols_pad, rot.npad, col, 0, lane);
+      if ((int64_t)blockIdx.x * (256 / LPT) >= m) return;          // (workgroup-uniform, in front of every barrier)
+      double* sYw = sh + LPT * NULL_NK * (1 + C) + wave * 64 + (lane & 15) * LPT + kk;
+#pragma unroll
+      for (int b = 0; b < RB; ++b)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int i = r + 4 * b, k = kk + LPT * i;
+          sYw[i * 256] = (k < n && col < m) ? acc[b][r] : 0.0;      // (stage_null_y's condition)
+        }
+    }
+  }
   double* sLam = sh;       // n      (generic evaluator only)
   double* sZ = sh + n;     // C*n
   if (!REG) {
@@ -1621,7 +1664,7 @@ __global__ void __launch_bounds__(256, BRENT_MINW) k_brent(NullModel nm, const d
   EllOut fin;
   double* sY = sh + LPT * NULL_NK * (1 + C);
   if constexpr (REG) {
-    stage_null_y<LPT>(sY, ycol, ldy, sub, n, valid);   // own column only: no barrier needed before the lane reads it back
+    if (!fused) stage_null_y<LPT>(sY, ycol, ldy, sub, n, valid);   // own column only: no barrier needed before the lane reads it back
     __syncthreads();                                   // (the repacking path reads other lanes' columns later)
   }
   if constexpr (REG && (64 / LPT) > 1) {
@@ -1776,9 +1819,17 @@ __global__ void __launch_bounds__(256, BRENT_MINW2) k_brent2(NullModel nm, const
 // 2: k_brent2 (after a phase 1 with sp->active, same arguments)
 template <int C, int LPT, bool REG>
 static int launch_brent_t(blmm_ctx* ctx, const NullModel& nm, const double* Yt, int64_t ldy, int64_t m, const double* Z0,
-                          const double* lam, double* h2, double* sigma2, double* ell, int64_t* stat, int phase, BrentSplit* sp) {
+                          const double* lam, double* h2, double* sigma2, double* ell, int64_t* stat, int phase, BrentSplit* sp,
+                          const BrentRot* rot) {
   const int64_t threads = m * LPT;
-  const unsigned blocks = (unsigned)((threads + 255) / 256);
+  unsigned blocks = (unsigned)((threads + 255) / 256);
+  BrentRot br;
+  if (rot && rot->Y) {
+    if (!(REG && LPT == 4) || nm.npad > 4 * NULL_NK || rot->npad != nm.npad || rot->ncols_pad > ldy || rot->ncols_pad < m)
+      return fail(ctx, BLMM_ERR_INVALID, "launch_brent: the fused rotation needs the four-lane register form (brent_fuses_rotation)");
+    br = *rot;
+    blocks = (unsigned)((std::max<int64_t>(rot->ncols_pad, m) + 63) / 64);   // (64 traits per workgroup: the padding columns too)
+  }
   const size_t lds = REG ? sizeof(double) * ((size_t)LPT * NULL_NK * (1 + C) + (size_t)NULL_NK * 256) : sizeof(double) * (size_t)nm.n * (1 + C);
   if (lds > 48 * 1024)
     BLMM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_brent<C, LPT, REG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -1804,7 +1855,7 @@ static int launch_brent_t(blmm_ctx* ctx, const NullModel& nm, const double* Yt, 
   if (sp) { sp->active = two && phase == 1; sp->fin = cont.fin; sp->list = cont.list; sp->cnt = cont.cnt; }
   if (phase != 2) {
     hipLaunchKernelGGL((k_brent<C, LPT, REG>), dim3(blocks), dim3(256), lds, ctx->stream, nm, Yt, ldy, m, Z0, lam,
-                       ptr<double>(ctx->logtab), h2, sigma2, ell, stat, cont);
+                       ptr<double>(ctx->logtab), h2, sigma2, ell, stat, cont, br);
     KCHECK();
   }
   if (phase == 1 && two) return BLMM_OK;
@@ -1834,34 +1885,42 @@ static int launch_brent_t(blmm_ctx* ctx, const NullModel& nm, const double* Yt, 
   return BLMM_OK;
 }
 
+static int brent_lpt_env() {
+  static const int lpt_env = dev_env("BLMM_BRENT_LPT") ? atoi(dev_env("BLMM_BRENT_LPT")) : 0;
+  return lpt_env;
+}
+bool brent_fuses_rotation(int n, int c) { return c >= 1 && c <= 4 && n <= 4 * NULL_NK && brent_lpt_env() != 8 && brent_lpt_env() != 16; }
+
 template <int C>
 static int launch_brent_c(blmm_ctx* ctx, const NullModel& nm, const double* Yt, int64_t ldy, int64_t m, const double* Z0,
-                          const double* lam, double* h2, double* sigma2, double* ell, int64_t* stat, int phase, BrentSplit* sp) {
+                          const double* lam, double* h2, double* sigma2, double* ell, int64_t* stat, int phase, BrentSplit* sp,
+                          const BrentRot* rot) {
   const int n = nm.n;
-  static const int lpt_env = dev_env("BLMM_BRENT_LPT") ? atoi(dev_env("BLMM_BRENT_LPT")) : 0;
-  if (lpt_env == 8 && n <= 8 * NULL_NK) return launch_brent_t<C, 8, true>(ctx, nm, Yt, ldy, m, Z0, lam, h2, sigma2, ell, stat, phase, sp);
-  if (lpt_env == 16 && n <= 16 * NULL_NK) return launch_brent_t<C, 16, true>(ctx, nm, Yt, ldy, m, Z0, lam, h2, sigma2, ell, stat, phase, sp);
-  if (n <= 4 * NULL_NK) return launch_brent_t<C, 4, true>(ctx, nm, Yt, ldy, m, Z0, lam, h2, sigma2, ell, stat, phase, sp);
-  if (n <= 8 * NULL_NK) return launch_brent_t<C, 8, true>(ctx, nm, Yt, ldy, m, Z0, lam, h2, sigma2, ell, stat, phase, sp);
-  if (n <= 16 * NULL_NK) return launch_brent_t<C, 16, true>(ctx, nm, Yt, ldy, m, Z0, lam, h2, sigma2, ell, stat, phase, sp);
-  if (n <= 32 * NULL_NK) return launch_brent_t<C, 32, true>(ctx, nm, Yt, ldy, m, Z0, lam, h2, sigma2, ell, stat, phase, sp);
-  if (n <= 64 * NULL_NK) return launch_brent_t<C, 64, true>(ctx, nm, Yt, ldy, m, Z0, lam, h2, sigma2, ell, stat, phase, sp);
-  return launch_brent_t<C, BRENT_LPT, false>(ctx, nm, Yt, ldy, m, Z0, lam, h2, sigma2, ell, stat, phase, sp);
+  const int lpt_env = brent_lpt_env();
+  if (lpt_env == 8 && n <= 8 * NULL_NK) return launch_brent_t<C, 8, true>(ctx, nm, Yt, ldy, m, Z0, lam, h2, sigma2, ell, stat, phase, sp, rot);
+  if (lpt_env == 16 && n <= 16 * NULL_NK) return launch_brent_t<C, 16, true>(ctx, nm, Yt, ldy, m, Z0, lam, h2, sigma2, ell, stat, phase, sp, rot);
+  if (n <= 4 * NULL_NK) return launch_brent_t<C, 4, true>(ctx, nm, Yt, ldy, m, Z0, lam, h2, sigma2, ell, stat, phase, sp, rot);
+  if (n <= 8 * NULL_NK) return launch_brent_t<C, 8, true>(ctx, nm, Yt, ldy, m, Z0, lam, h2, sigma2, ell, stat, phase, sp, rot);
+  if (n <= 16 * NULL_NK) return launch_brent_t<C, 16, true>(ctx, nm, Yt, ldy, m, Z0, lam, h2, sigma2, ell, stat, phase, sp, rot);
+  if (n <= 32 * NULL_NK) return launch_brent_t<C, 32, true>(ctx, nm, Yt, ldy, m, Z0, lam, h2, sigma2, ell, stat, phase, sp, rot);
+  if (n <= 64 * NULL_NK) return launch_brent_t<C, 64, true>(ctx, nm, Yt, ldy, m, Z0, lam, h2, sigma2, ell, stat, phase, sp, rot);
+  return launch_brent_t<C, BRENT_LPT, false>(ctx, nm, Yt, ldy, m, Z0, lam, h2, sigma2, ell, stat, phase, sp, rot);
 }
 
 int launch_brent(blmm_ctx* ctx, const NullModel& nm, const double* Yt, int64_t ldy, int64_t m, const double* Z0,
-                 const double* lam, double* h2, double* sigma2, double* ell, int64_t* stat, int phase, BrentSplit* sp) {
+                 const double* lam, double* h2, double* sigma2, double* ell, int64_t* stat, int phase, BrentSplit* sp, const BrentRot* rot) {
   if (nm.c > CTPL && nm.c <= CMAX) {       // run-time covariate count: one kernel, never split
+    if (rot && rot->Y) return fail(ctx, BLMM_ERR_INVALID, "launch_brent: no fused rotation at a run-time covariate count");
     if (sp) sp->active = false;
     return phase == 2 ? BLMM_OK : launch_dyn_brent(ctx, nm, Yt, ldy, m, Z0, lam, h2, sigma2, ell, stat);
   }
   switch (nm.c) {
-    case 1: return launch_brent_c<1>(ctx, nm, Yt, ldy, m, Z0, lam, h2, sigma2, ell, stat, phase, sp);
-    case 2: return launch_brent_c<2>(ctx, nm, Yt, ldy, m, Z0, lam, h2, sigma2, ell, stat, phase, sp);
-    case 3: return launch_brent_c<3>(ctx, nm, Yt, ldy, m, Z0, lam, h2, sigma2, ell, stat, phase, sp);
-    case 4: return launch_brent_c<4>(ctx, nm, Yt, ldy, m, Z0, lam, h2, sigma2, ell, stat, phase, sp);
+    case 1: return launch_brent_c<1>(ctx, nm, Yt, ldy, m, Z0, lam, h2, sigma2, ell, stat, phase, sp, rot);
+    case 2: return launch_brent_c<2>(ctx, nm, Yt, ldy, m, Z0, lam, h2, sigma2, ell, stat, phase, sp, rot);
+    case 3: return launch_brent_c<3>(ctx, nm, Yt, ldy, m, Z0, lam, h2, sigma2, ell, stat, phase, sp, rot);
+    case 4: return launch_brent_c<4>(ctx, nm, Yt, ldy, m, Z0, lam, h2, sigma2, ell, stat, phase, sp, rot);
     // beyond CFAST: the generic evaluator (operands re-read per evaluation, libm log / IEEE division), one instantiation each
-#define BG(C) return launch_brent_t<C, 16, false>(ctx, nm, Yt, ldy, m, Z0, lam, h2, sigma2, ell, stat, phase, sp)
+#define BG(C) return launch_brent_t<C, 16, false>(ctx, nm, Yt, ldy, m, Z0, lam, h2, sigma2, ell, stat, phase, sp, rot)
     case 5: BG(5);
     case 6: BG(6);
     case 7: BG(7);

@@ -266,6 +266,11 @@ int blmm_bulkscan_reduced_dev(blmm_ctx* ctx, const blmm_opts* opts, const double
                               const double* h2_grid_host, int64_t ngrid, const blmm_reduced* out, double* dh2_out,
                               blmm_status* status);
 int blmm_last_reduced_route(const blmm_ctx* ctx);
+/* Diagnostic for tests: which parts of the shortened null-exact front the context's last call took.  Bit 0: the weight basis was
+ * built behind the eigenvalue kernel, ahead of the eigen phase's end; bit 1: the traits were rotated inside the h2 search's kernel;
+ * bit 2: unused; bit 3: the device rejected the fast eigen path and the basis was rebuilt from the Jacobi's eigenvalues (reported by
+ * the basis kernel itself).  Waits for the context's stream.  Negative: an error code. */
+int blmm_last_front_route(blmm_ctx* ctx);
 
 /* Stream-ordered form of blmm_bulkscan_reduced_dev (same arguments; `out` and dh2_out hold DEVICE pointers): the call only
  * enqueues on the context's stream and returns -- in steady state (the shapes of the previous call on this context) it makes
